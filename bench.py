@@ -2,6 +2,13 @@
 """Throughput of the pySDR receiver hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c1|c1synch|c2|c3|rx6|c4|c4mono|ft8tri|test2rx] [--ntaps N] [--split stream|rx]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the kernel times and rooflines
+sampled inside the timed steps).  --full adds what takes work of its own: the check of the last step against the oracle
+(--verify), the CPU baselines, the host-fed (PCIe) leg, the 20 Hz PSD duty, and for the default command the other
+configurations and the live rocprofv3 traffic passes; it also writes the verbose object to bench_full*.json.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 
 One "step" = one pass of the hot path over one device-resident batch of `--chunks` chunks of one
 synthetic wideband stream.  Default workload = SURVEY.md 8(d) config C3: the fused mix+decimate
@@ -105,20 +112,27 @@ def parse(argv=None):
                          "`value`; 0 = skip")
     ap.add_argument("--verify", dest="verify", action="store_true", default=None,
                     help="after the timed loop every rank checks the LAST step's device buffers against the float32 "
-                         "oracle (first 2 chunks per sub-receiver, PSD frame 0); default ON")
+                         "oracle (first 2 chunks per sub-receiver, PSD frame 0); default: on with --full, off without")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="default command only: do not measure the HBM traffic of this run in two rocprofv3 --pmc child passes "
+                    help="default command with --full only: do not measure the HBM traffic of this run in two rocprofv3 --pmc child passes "
                          "(the line then carries the stored figure of profiles/, guarded by source hashes)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default command (workload c3, 1 GPU) also runs c1, c2 and c4 at their default batch for --steps "
+                    help="with --full the default command (workload c3, 1 GPU) also runs c1, c2 and c4 at their default batch for --steps "
                          "steps each, in child processes AFTER its own timed loop, and reports them as `other_configs` "
                          "(never as `value`); this switch skips that")
+    ap.add_argument("--full", action="store_true",
+                    help="also verify against the oracle, time the CPU baselines, the host-fed leg and the 20 Hz PSD duty, run the "
+                         "other configurations and the live traffic passes, and write bench_full*.json; off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = MIN_STEPS.get(args.workload, 30)
     if args.warmup is None:
         args.warmup = MIN_WARMUP.get(args.workload, 5)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -590,6 +604,67 @@ def device_checksum(lib, device, d_ptr, nbytes, piece=256 << 20):
     return s, x
 
 
+DUMP_BYTES = 64 * 10 ** 6    # --dump-outputs: at most this much in all
+DUMP_SEED = 20240601         # the sample of chunks / PSD frames when a step's results are larger
+
+
+def dump_outputs(path, ctx, rx_ids, B, psd=None, prefix="", budget=DUMP_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<prefix><name>.npy.  Per sub-receiver r (ctx index
+    i, r its index in the workload): rx<r>_audio (float32; [n, 2] for complex audio), rx<r>_iq (baseband, float32 [n, 2]), and
+    for every chunk of the step rx<r>_counts (outputs per chunk, float64) and rx<r>_peak (input peak power, float32); psd (float32
+    [frames, PSD_NFFT], dB) with psd = (lib, device, d_psd, nframes).  When the whole step exceeds `budget` bytes, audio and IQ
+    are kept for a seeded sample of the chunks and the PSD for a seeded sample of its frames: `chunks` and `psd_frames`
+    (float64) hold the indices kept, the same on every run of the same arguments."""
+    from pysdr_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    fetched = [(r, ctx.fetch(i, B)) for i, r in rx_ids]
+    nframes = psd[3] if psd is not None else 0
+    frame_bytes = PSD_NFFT * 4
+    # counts + peaks of every chunk, the two index arrays and a .npy header per file come off the top
+    avail = budget - (len(fetched) * B * 12 + (B + nframes) * 8 + 128 * (4 * len(fetched) + 4))
+    # bytes of audio + IQ of every sub-receiver, chunk by chunk
+    per_chunk = np.zeros(B, np.int64)
+    for _r, (am, iq, cn, _pk) in fetched:
+        per_chunk += cn.astype(np.int64) * (am.itemsize + iq.itemsize)
+    rx_share = avail // 2 if nframes else avail
+    if int(per_chunk.sum()) <= rx_share:
+        chunks = np.arange(B)
+    else:
+        keep = max(0, min(B, rx_share // max(1, int(per_chunk.max()))))
+        chunks = np.sort(np.random.default_rng(DUMP_SEED).choice(B, keep, replace=False))
+    psd_share = avail - int(per_chunk[chunks].sum())
+    if nframes * frame_bytes <= psd_share:
+        frames = np.arange(nframes)
+    else:
+        keep = max(0, min(nframes, psd_share // frame_bytes))
+        frames = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(nframes, keep, replace=False))
+
+    def save(name, a):
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
+
+    if fetched:
+        save("chunks", chunks.astype(np.float64))
+    for r, (am, iq, cn, pk) in fetched:
+        off = np.concatenate([[0], np.cumsum(cn, dtype=np.int64)])
+
+        def pick(a):
+            return np.concatenate([a[:0]] + [a[off[k]:off[k + 1]] for k in chunks])
+
+        a = pick(am)
+        save(f"rx{r}_audio", a.view(np.float32).reshape(-1, 2) if np.iscomplexobj(a) else a.astype(np.float32))
+        save(f"rx{r}_iq", pick(iq).view(np.float32).reshape(-1, 2))
+        save(f"rx{r}_counts", cn.astype(np.float64))
+        save(f"rx{r}_peak", pk.astype(np.float32))
+    if nframes:
+        lib, device, d_psd, _n = psd
+        out = np.empty((len(frames), PSD_NFFT), np.float32)
+        for j, f in enumerate(frames):
+            _lib.check(lib.pysdr_dev_download(device, C.c_void_p(out[j].ctypes.data), C.c_void_p(d_psd.value + int(f) * frame_bytes),
+                                              frame_bytes), "download psd")
+        save("psd", out)
+        save("psd_frames", frames.astype(np.float64))
+
+
 def source_sha(name):
     try:
         return hashlib.sha256(open(os.path.join(ROOT, "pysdr_amd", "csrc", name), "rb").read()).hexdigest()[:16]
@@ -640,7 +715,7 @@ def live_traffic(args):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         td = tempfile.mkdtemp(prefix="pysdr_pmc_", dir="/tmp")
         cmd = [rp, "--pmc", ctr, "--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__),
-               "--no-cpu-baseline", "--no-host-fed", "--no-other-configs", "--no-verify", "--full-line", "--steps", "3", "--warmup", "1"]
+               "--full", "--no-cpu-baseline", "--no-host-fed", "--no-other-configs", "--no-verify", "--full-line", "--steps", "3", "--warmup", "1"]
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, TMPDIR="/tmp"))
             if p.returncode != 0:
@@ -673,7 +748,7 @@ def other_configs(args):
     res = {}
     for w in OTHER_CONFIGS:
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", str(max(args.steps, MIN_STEPS.get(w, 0))), "--warmup",
-               str(max(args.warmup, MIN_WARMUP.get(w, 0))), "--no-cpu-baseline", "--no-host-fed", "--no-other-configs", "--full-line"]
+               str(max(args.warmup, MIN_WARMUP.get(w, 0))), "--full", "--no-cpu-baseline", "--no-host-fed", "--no-other-configs", "--full-line"]
         if args.verify is not None:
             cmd.append("--verify" if args.verify else "--no-verify")
         t0 = time.time()
@@ -837,7 +912,7 @@ def main():
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
     split_rx = args.split == "rx"
-    do_verify = True if args.verify is None else bool(args.verify)
+    do_verify = args.full if args.verify is None else bool(args.verify)
     refuse = split_rx_refusal(split_rx, world, ndev)
     if refuse:
         raise SystemExit(refuse)
@@ -993,6 +1068,11 @@ def main():
         dist.all_gather(allt, torch.tensor([dt_local / args.steps * 1e3], dtype=torch.float64))
         per_rank_ms = [float(v.item()) for v in allt]
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, [] if args.no_demod else list(enumerate(rx_idx if rx_idx is not None else range(len(rxs)))),
+                     B, (lib, device, d_psd, nframes) if sp is not None else None,
+                     prefix=f"rank{rank}_" if world > 1 else "", budget=DUMP_BYTES // world)
+
     # ---- --verify: the LAST timed step's device buffers against the oracle, on every rank
     verify = None
     if do_verify and not args.no_demod:
@@ -1013,7 +1093,7 @@ def main():
     # takes one 32768-sample chunk per tick and flushes the backlog (pySDR.py:252-256, gui.py:1264-1267),
     # i.e. one 64k frame per SRATE/20 samples; everything else of the step is unchanged
     duty = None
-    if sp is not None and world == 1 and args.psd_hz > 0 and not args.no_demod and not args.overlap_psd:
+    if args.full and sp is not None and world == 1 and args.psd_hz > 0 and not args.no_demod and not args.overlap_psd:
         hop20 = int(round(cfg['fs'] / args.psd_hz))
         nf20 = (nsamp - PSD_CHUNK) // hop20 + 1
 
@@ -1182,11 +1262,11 @@ def main():
 
     # PCIe-inclusive figure (never `value`): the same chunks handed over as HOST arrays through the
     # ingest ring (N4), slots of 16 chunks, including the host memcpy that stands for readStream()
-    if rank == 0 and world == 1 and not args.no_host_fed and not split_rx and rxs and not is_wfm:
+    if args.full and rank == 0 and world == 1 and not args.no_host_fed and not split_rx and rxs and not is_wfm:
         out["host_fed"] = host_fed_rate(ctx, cfg, L, 16 if B >= 16 else B)
         out["host_fed_ms_per_chunk"] = out["host_fed"]["ms_per_chunk"]
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], used = cpu_baseline(cfg, args.cpu_chunks, with_psd, 10, args.cpu_seconds)
         if not args.no_cpu_mp and not is_wfm:
             out["cpu_baseline_per_rx_process"] = cpu_baseline_per_rx(args, cfg, used, with_psd, 10)
@@ -1207,7 +1287,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if (rank == 0 and world == 1 and args.workload == "c3" and not args.no_other_configs and not args.no_demod
+    if (args.full and rank == 0 and world == 1 and args.workload == "c3" and not args.no_other_configs and not args.no_demod
             and not args.nrx and not args.no_psd and not args.chunks and not args.ntaps):
         out["other_configs"] = other_configs(args)
         if not args.no_live_traffic:
@@ -1232,7 +1312,7 @@ def main():
         if args.full_line:
             print(json.dumps(out), flush=True)
         else:
-            full_path = write_full(out, args)
+            full_path = write_full(out, args) if args.full else None
             print(json.dumps(compact_line(out, full_path), separators=(",", ":")), flush=True)
     if verify is not None and verify["verified_ranks"] != world:
         print(f"bench.py: --verify FAILED on rank {rank}: {verify['verified_ranks']} of {world} ranks match the oracle "

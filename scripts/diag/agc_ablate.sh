@@ -7,7 +7,7 @@ for fl in "" "-DAGCX_NO_CHAIN" "-DAGCX_NO_ZERO" "-DAGCX_NO_LOAD" "-DAGCX_NO_CHAI
   PYSDR_STAGE2_FLAGS="-DPYSDR_ABLATE $fl" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $fl"; grep error /tmp/build.log | head -3; continue; }
   for w in ${WL:-c1 c2}; do
     O=gpurun_out/agc_kt/$w; rm -rf $O; mkdir -p $O
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
     python3 - "$O" "$fl" "$w" <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True):

@@ -17,18 +17,18 @@ PY
 for rep in 1 2; do
 for cfg in "1 1" "0 1" "1 0" "0 0"; do
   set -- $cfg
-  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 python3 bench.py --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 python3 bench.py --full --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   line direct=$1 seed=$2 overlapped
-  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   line direct=$1 seed=$2 single-stream
 done
 done
-python3 bench.py --workload c1 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+python3 bench.py --full --workload c1 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
 line c1 plain AM
 for s in "1 1" "0 0"; do
   set -- $s
   O=gpurun_out/am_direct_kt_$1$2; rm -rf $O; mkdir -p $O
-  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 > $O.log 2>&1
+  PYSDR_AM_DIRECT=$1 PYSDR_AM_SEED=$2 rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 > $O.log 2>&1
   echo "direct=$1 seed=$2 single-stream kernel averages:"
   python3 - $O <<'PY'
 import csv, glob, sys

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export PYSDR_TUNING=1
 for o in "" "--no-overlap"; do
-  python3 bench.py --workload c1synch $o --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  python3 bench.py --full --workload c1synch $o --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   python3 - "$o" <<'PY'
 import json,sys
 d=json.loads([l for l in open("/tmp/o.json") if l.startswith("{")][-1]); p=d["carrier_pll"]
@@ -11,7 +11,7 @@ print("%-13s %.1f GS/s %.4f ms %s verify %.2g lin %s join %s patched %s" % (sys.
 PY
 done
 O=gpurun_out/am_kt; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 "$@" > $O.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 "$@" > $O.log 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/*/*kernel_stats.csv"):

@@ -7,7 +7,7 @@ export PYSDR_TUNING=1
 N=${1:-6}
 for rep in $(seq 1 $N); do
   for d in 0 1; do
-    PYSDR_OVERLAP_ORDER=$d python3 bench.py --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs --no-verify > /tmp/o.json 2>/tmp/o.err
+    PYSDR_OVERLAP_ORDER=$d python3 bench.py --full --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs --no-verify > /tmp/o.json 2>/tmp/o.err
     python3 - $d <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

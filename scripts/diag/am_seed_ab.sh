@@ -16,19 +16,19 @@ PY
 for rep in 1 2; do
 for cfg in "1 1" "0 1" "1 0" "0 0"; do
   set -- $cfg
-  PYSDR_AM_SEED=$1 PYSDR_AM_PHASE_STREAM=$2 python3 bench.py --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  PYSDR_AM_SEED=$1 PYSDR_AM_PHASE_STREAM=$2 python3 bench.py --full --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   line seed=$1 phase_on_2=$2 overlapped
 done
 for s in 1 0; do
-  PYSDR_AM_SEED=$s python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  PYSDR_AM_SEED=$s python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   line seed=$s single-stream
 done
 done
-python3 bench.py --workload c1 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+python3 bench.py --full --workload c1 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
 line c1 plain AM
 for s in 1 0; do
   O=gpurun_out/am_seed_kt_$s; rm -rf $O; mkdir -p $O
-  PYSDR_AM_SEED=$s rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 > $O.log 2>&1
+  PYSDR_AM_SEED=$s rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 > $O.log 2>&1
   echo "seed=$s single-stream kernel averages:"
   python3 - $O <<'PY'
 import csv, glob, sys

@@ -16,9 +16,9 @@ PY
 for rep in 1 2; do
 for k in 2048 4096 8192; do
   for s in 1 0; do
-    PYSDR_AM_SEED=$s PYSDR_AM_PLL=16,5,4,$k,512 python3 bench.py --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    PYSDR_AM_SEED=$s PYSDR_AM_PLL=16,5,4,$k,512 python3 bench.py --full --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     line K=$k seed=$s overlapped
-    PYSDR_AM_SEED=$s PYSDR_AM_PLL=16,5,4,$k,512 python3 bench.py --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    PYSDR_AM_SEED=$s PYSDR_AM_PLL=16,5,4,$k,512 python3 bench.py --full --workload c1synch --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     line K=$k seed=$s single-stream
   done
 done

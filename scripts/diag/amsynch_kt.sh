@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for cfg in "${@:-default}"; do
   O=gpurun_out/amsynch_kt/$(echo $cfg | tr ',' '_'); rm -rf $O; mkdir -p $O
   if [ "$cfg" != default ]; then export PYSDR_TUNING=1 PYSDR_AM_PLL=$cfg; else unset PYSDR_TUNING PYSDR_AM_PLL; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs --steps 20 --warmup 4 > $O.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload c1synch --no-cpu-baseline --no-host-fed --no-other-configs --steps 20 --warmup 4 > $O.log 2>&1
   echo "== $cfg"
   python3 - $O $O.log <<'PY'
 import csv, glob, json, sys

@@ -6,7 +6,7 @@ for st in ${STRIDES:-64 32 16 64}; do
   PYSDR_STAGE2_FLAGS="-DPYSDR_BLK_STRIDE=$st" PYSDR_API_FLAGS="-DPYSDR_BLK_STRIDE=$st" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $st"; grep error /tmp/build.log | head -3; continue; }
   for w in c1 "c3 --no-psd"; do
     O=gpurun_out/blk_kt; rm -rf $O; mkdir -p $O
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
     python3 - "$O" "$st" "$w" <<'PY'
 import csv, glob, sys, json
 ver = json.loads(open(sys.argv[1] + '/bench.json').read().strip().splitlines()[-1]).get('verify_worst_rel')

@@ -8,7 +8,7 @@ for fl in "" "-DMM_C1_NBUF=3"; do
   PYSDR_MFMA_FLAGS="$fl" PYSDR_API_FLAGS="$fl" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $fl"; grep -i "error" /tmp/build.log | head -3; continue; }
   for w in c1 c1synch; do
   for mode in --no-overlap --overlap-all; do
-    python3 bench.py --workload $w $mode --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    python3 bench.py --full --workload $w $mode --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     python3 - "$fl" $w $mode <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

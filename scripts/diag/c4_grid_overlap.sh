@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"
 export PYSDR_TUNING=1
 for g in 256 248 240 224 192; do
-  PYSDR_MIXDEC_GRID=$g python3 bench.py --workload c4 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  PYSDR_MIXDEC_GRID=$g python3 bench.py --full --workload c4 --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   python3 - $g <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export PYSDR_TUNING=1
 for rep in 1 2; do
 for o in "" "--no-overlap"; do
-  python3 bench.py --workload c4 $o --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  python3 bench.py --full --workload c4 $o --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   python3 - "$o" <<'PY'
 import json,sys
 d=json.loads([l for l in open("/tmp/o.json") if l.startswith("{")][-1]); p=d["pilot_pll"]
@@ -13,7 +13,7 @@ PY
 done
 done
 O=gpurun_out/c4_kt; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload c4 --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 "$@" > $O.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload c4 --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 20 --warmup 4 "$@" > $O.log 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/*/*kernel_stats.csv"):

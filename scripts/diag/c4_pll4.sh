@@ -3,7 +3,7 @@
 for cfg in "" "20,13,5,3,1536,2048,5,4,4,0" "20,13,5,3,1536,2048,5,3,5,0" "20,13,5,3,1536,2048,5,0,0,4" "20,13,5,3,1536,2048,5,4,4,4" "20,13,4,3,1536,2048,5,0,0,0" "20,12,5,3,1536,2048,5,0,0,0" "20,14,5,3,1536,2048,5,0,0,0" ""; do
   echo "== PYSDR_WFM_PLL='$cfg'"
   if [ -n "$cfg" ]; then export PYSDR_TUNING=1 PYSDR_WFM_PLL=$cfg; else unset PYSDR_TUNING PYSDR_WFM_PLL; fi
-  python bench.py --workload c4 --no-cpu-baseline --no-host-fed --no-other-configs --steps 20 --warmup 4 2>/dev/null | python -c "
+  python bench.py --full --workload c4 --no-cpu-baseline --no-host-fed --no-other-configs --steps 20 --warmup 4 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 p = d.get('pilot_pll')

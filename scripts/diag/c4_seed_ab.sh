@@ -5,7 +5,7 @@ export PYSDR_TUNING=1
 for rep in 1 2; do
 for seed in 1 0 "1,1024"; do
   for ov in "" "--no-overlap"; do
-    PYSDR_WFM_SEED=$seed python3 bench.py --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    PYSDR_WFM_SEED=$seed python3 bench.py --full --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     python3 - "$seed" "$ov" <<'PY'
 import json,sys
 try:

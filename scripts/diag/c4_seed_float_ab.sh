@@ -7,7 +7,7 @@ for fl in "${@:-}"; do
   PYSDR_SEED_FLAGS="$fl" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $fl"; grep -i "error" /tmp/build.log | head -3; continue; }
   echo "== [$fl]"
   for ov in "" "--no-overlap"; do
-    python3 bench.py --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    python3 bench.py --full --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     python3 - "$ov" <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

@@ -5,7 +5,7 @@ export PYSDR_TUNING=1
 for cfg in default 20,13,4,3,2048,2048 20,13,4,3,3072,1024 20,13,4,3,4096,1024; do
   if [ "$cfg" != default ]; then export PYSDR_WFM_PLL=$cfg; else unset PYSDR_WFM_PLL; fi
   for ov in "" "--no-overlap"; do
-  python3 bench.py --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+  python3 bench.py --full --workload c4 $ov --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
   python3 - "$cfg" "$ov" <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

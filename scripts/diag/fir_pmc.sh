@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/fir_pmc; rm -rf $O; mkdir -p $O
 run() { local name=$1; shift
-  rocprofv3 --pmc "$@" --output-format csv -d $O/$name -- python3 bench.py --workload ${WL:-c2} --no-cpu-baseline --steps 3 --warmup 1 > $O/$name.log 2>&1
+  rocprofv3 --pmc "$@" --output-format csv -d $O/$name -- python3 bench.py --full --workload ${WL:-c2} --no-cpu-baseline --steps 3 --warmup 1 > $O/$name.log 2>&1
   python3 - "$O/$name" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

@@ -6,7 +6,7 @@ for t in 256 128 512 256; do
   PYSDR_STAGE2_FLAGS="-DFIRX_THREADS=$t" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $t"; grep error /tmp/build.log | head -3; continue; }
   for w in c1 c2 "c3 --no-psd" c4; do
     O=gpurun_out/fir_kt; rm -rf $O; mkdir -p $O
-    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --steps 10 --warmup 3 > $O/bench.json 2> $O/err.txt
     python3 - "$O" "$t" "$w" <<'PY'
 import csv, glob, sys, json
 ver = json.loads(open(sys.argv[1] + '/bench.json').read().strip().splitlines()[-1]).get('verify_worst_rel')

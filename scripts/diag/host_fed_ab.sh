@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"
 for i in 1 2; do
 for t in _r04 .; do
-  (cd $t && python3 bench.py --no-cpu-baseline --no-other-configs --steps 5 --warmup 2 > /tmp/o.json 2>/tmp/o.err; python3 - $t <<'PY'
+  (cd $t && python3 bench.py --full --no-cpu-baseline --no-other-configs --steps 5 --warmup 2 > /tmp/o.json 2>/tmp/o.err; python3 - $t <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])
 h=d['host_fed']

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for spec in "c1 1100" "c2 2200" "ft8tri 2200" "c1synch 1100" "c4 2200" "rx6 2200"; do
   set -- $spec
-  python3 bench.py --workload $1 --steps $2 --warmup 5 --no-cpu-baseline --no-host-fed --no-other-configs --full-line --verify 2>&1 | tail -1 | python3 -c "
+  python3 bench.py --full --workload $1 --steps $2 --warmup 5 --no-cpu-baseline --no-host-fed --no-other-configs --full-line --verify 2>&1 | tail -1 | python3 -c "
 import sys,json
 try:
     j=json.loads(sys.stdin.read().strip())

@@ -10,7 +10,7 @@ for rep in $(seq 1 ${REPS:-3}); do
  for w in ${WLS:-c1 c4 c1synch}; do
   for v in main ${VARIANTS:-flags}; do
    if [ "$v" = main ]; then e="PYSDR_X=0"; else e="PYSDR_TUNING=1 PYSDR_LIB_VARIANT=$v"; fi
-   env $e python3 bench.py --workload $w $B 2>&1 | tail -1 | python3 -c "
+   env $e python3 bench.py --full --workload $w $B 2>&1 | tail -1 | python3 -c "
 import sys,json
 try:
     j=json.loads(sys.stdin.read().strip()); r=j.get('roofline_mixdec') or {}

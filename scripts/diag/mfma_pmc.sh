@@ -6,9 +6,9 @@ rocprofv3 -L > $O/counters.txt 2>&1
 grep -i -o "SQ_[A-Z_0-9]*MFMA[A-Z_0-9]*" $O/counters.txt | sort -u > $O/mfma_counters.txt
 cat $O/mfma_counters.txt | head -40
 A="--workload c1 --no-cpu-baseline --no-host-fed --steps 3 --warmup 1"
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/p1 -- python3 bench.py $A > $O/p1.json 2> $O/p1.err
-rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS --output-format csv -d $O/p2 -- python3 bench.py $A > $O/p2.json 2> $O/p2.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py $A > $O/kt.json 2> $O/kt.err
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --output-format csv -d $O/p1 -- python3 bench.py --full $A > $O/p1.json 2> $O/p1.err
+rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_MFMA SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS --output-format csv -d $O/p2 -- python3 bench.py --full $A > $O/p2.json 2> $O/p2.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full $A > $O/kt.json 2> $O/kt.err
 python3 - <<'PY'
 import csv, glob, collections
 for p in ('p1', 'p2'):

@@ -10,7 +10,7 @@ for rep in 1 2 3 4; do
   for v in keep plain; do
     cp /tmp/$v.so pysdr_amd/libpysdr_hip.so
     for w in c1 c4mono; do
-      python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+      python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
       python3 - "$v" "$w" <<'PY'
 import json,sys
 d=json.loads([l for l in open("/tmp/o.json") if l.startswith("{")][-1])
@@ -23,7 +23,7 @@ for v in keep plain; do
   cp /tmp/$v.so pysdr_amd/libpysdr_hip.so
   for w in c1 c4mono; do
     O=gpurun_out/mm_part_pmc_${v}_$w; rm -rf $O; mkdir -p $O
-    rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $O -- python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 3 --warmup 1 > $O.log 2>&1
+    rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $O -- python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 3 --warmup 1 > $O.log 2>&1
     python3 - $O "$v" "$w" <<'PY'
 import csv, glob, sys, collections
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()

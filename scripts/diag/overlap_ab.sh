@@ -1,14 +1,14 @@
 #!/bin/bash
 # A/B of the two-stream call pipeline (pysdr_set_overlap): every single-GPU workload with and without it, same box.
-#   scripts/diag/overlap_ab.sh [workload ...]
+#   OUT=<output dir> scripts/diag/overlap_ab.sh [workload ...]
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/overlap_ab
+O=${OUT:?set OUT to an output directory}/overlap_ab; mkdir -p "$O"
 WL=("$@"); [ ${#WL[@]} -eq 0 ] && WL=(c1 c1synch c2 rx6 c4mono c4 c3)
 for w in "${WL[@]}"; do
   for mode in on off; do
     flag=""; [ $mode = off ] && flag="--no-overlap"
-    python3 bench.py --workload $w $flag --no-cpu-baseline --no-host-fed --no-other-configs > gpurun_out/overlap_ab/${w}_$mode.json 2> gpurun_out/overlap_ab/${w}_$mode.err
-    python3 - gpurun_out/overlap_ab/${w}_$mode.json $w $mode <<'PY'
+    python3 bench.py --full --workload $w $flag --no-cpu-baseline --no-host-fed --no-other-configs > "$O/${w}_$mode.json" 2> "$O/${w}_$mode.err"
+    python3 - "$O/${w}_$mode.json" $w $mode <<'PY'
 import json, sys
 try:
     d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

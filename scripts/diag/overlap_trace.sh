@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 W=${1:-c4}; shift
 O=gpurun_out/overlap_trace_$W; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --workload $W --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 8 --warmup 4 "$@" > $O.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --full --workload $W --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 8 --warmup 4 "$@" > $O.log 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 rows = []

@@ -6,7 +6,7 @@ cp pysdr_amd/libpysdr_hip.so /tmp/keep.so
 for pr in 3 0 1; do
   PYSDR_STAGE2_FLAGS="-DPLLX_PRIO=$pr" python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $pr"; grep -i "error" /tmp/build.log | head -3; continue; }
   for w in c1synch c4; do
-    python3 bench.py --workload $w --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
+    python3 bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs > /tmp/o.json 2>/tmp/o.err
     python3 - $pr $w <<'PY'
 import json,sys
 d=json.loads([l for l in open('/tmp/o.json') if l.startswith('{')][-1])

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for w in c1synch c4; do
   O=gpurun_out/pll_walk_pmc_$w; rm -rf $O; mkdir -p $O
-  rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O -- python3 bench.py --workload $w --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 3 --warmup 1 > $O.log 2>&1
+  rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE --output-format csv -d $O -- python3 bench.py --full --workload $w --no-overlap --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 3 --warmup 1 > $O.log 2>&1
   python3 - $O $w <<'PY'
 import csv, glob, sys, collections
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()

@@ -2,7 +2,7 @@
 # per-kernel times of the demod-only C3 step: stage2_kt.sh [bench args]
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/stage2_kt; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --no-psd --no-cpu-baseline --no-host-fed --steps 20 "$@" > $O.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 bench.py --full --no-psd --no-cpu-baseline --no-host-fed --steps 20 "$@" > $O.log 2>&1
 python3 - $O <<'PY'
 import csv, glob, sys
 for f in glob.glob(sys.argv[1] + "/*/*kernel_stats.csv"):

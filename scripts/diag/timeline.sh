@@ -2,7 +2,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 W=${1:-c1}
 O=gpurun_out/timeline_$W; rm -rf $O; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --workload $W --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 6 --warmup 2 > $O/b.json 2> $O/err.txt
+rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --full --workload $W --no-cpu-baseline --no-host-fed --no-other-configs --no-verify --steps 6 --warmup 2 > $O/b.json 2> $O/err.txt
 python3 - "$O" <<'PY'
 import csv, glob, sys
 rows = []

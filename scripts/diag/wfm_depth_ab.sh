@@ -9,7 +9,7 @@ for rep in 1 2 3 4; do
   for v in keep d1; do
     cp /tmp/$v.so pysdr_amd/libpysdr_hip.so
     for o in "" "--no-overlap"; do
-      python3 bench.py --workload c4 $o --no-cpu-baseline --no-host-fed --no-other-configs --no-verify > /tmp/o.json 2>/tmp/o.err
+      python3 bench.py --full --workload c4 $o --no-cpu-baseline --no-host-fed --no-other-configs --no-verify > /tmp/o.json 2>/tmp/o.err
       python3 - "$v" "$o" <<'PY'
 import json,sys
 d=json.loads([l for l in open("/tmp/o.json") if l.startswith("{")][-1])

@@ -8,7 +8,7 @@ B="--no-cpu-baseline --no-host-fed --no-other-configs --full-line --no-verify"
 for w in "c2" "c3 --no-psd" "rx6" "ft8tri"; do
   for yf in ${YFS:-0 1 2 3 5 8 16}; do
     if [ "$yf" = 0 ]; then e="PYSDR_X=0"; else e="PYSDR_TUNING=1 PYSDR_MIXDEC_YFLUSH=$yf"; fi
-    env $e python3 bench.py --workload $w $B 2>&1 | tail -1 | python3 -c "
+    env $e python3 bench.py --full --workload $w $B 2>&1 | tail -1 | python3 -c "
 import sys,json
 j=json.loads(sys.stdin.read().strip()); r=j.get('roofline_mixdec') or {}
 print('$w yflush=$yf', 'front', round(r.get('avg_launch_ms',0),4), 'ms frac', round(r.get('frac',0),3))

@@ -181,3 +181,63 @@ def test_live_traffic_falls_back_quietly_without_the_profiler(monkeypatch, tmp_p
     monkeypatch.setattr(subprocess, "run", fake_run)
     got = bench.live_traffic(None)
     assert got == {"mixdec_kernel": (2 * 100.0 + 10.0) * 1024.0}
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_the_budget(tmp_path):
+    """--dump-outputs writes what a caller of the batch path receives (audio, baseband IQ, per-chunk counts and peaks of
+    every sub-receiver, the PSD frames) as float32 / float64 .npy files: whole when the step fits the budget, otherwise
+    the same seeded sample of whole chunks and frames on every run, never more than the budget."""
+    import ctypes as C
+    rng = np.random.default_rng(3)
+    B, nframes = 40, 12
+    cn = [rng.integers(1900, 2100, B).astype(np.int32), rng.integers(900, 1100, B).astype(np.int32)]
+    outs = [((rng.standard_normal(int(c.sum())) + 1j * rng.standard_normal(int(c.sum()))).astype(np.complex64) if i else
+             rng.standard_normal(int(c.sum())).astype(np.float32),
+             (rng.standard_normal(int(c.sum())) + 1j * rng.standard_normal(int(c.sum()))).astype(np.complex64),
+             c, rng.random(B).astype(np.float32)) for i, c in enumerate(cn)]
+    psd = rng.standard_normal((nframes, bench.PSD_NFFT)).astype(np.float32)
+
+    class Ctx:
+        def fetch(self, i, nchunks):
+            assert nchunks == B
+            return outs[i]
+
+    class Lib:
+        def pysdr_dev_download(self, device, dst, src, n):
+            lo = psd.ctypes.data
+            assert lo <= src.value and src.value + n <= lo + psd.nbytes      # inside the PSD buffer
+            C.memmove(dst, src, n)
+            return 0
+
+    def dump(d, budget):
+        bench.dump_outputs(str(d), Ctx(), [(0, 3), (1, 5)], B, (Lib(), 0, C.c_void_p(psd.ctypes.data), nframes), budget=budget)
+        return {f.name[:-4]: np.load(f) for f in d.iterdir()}
+
+    whole = dump(tmp_path / "whole", bench.DUMP_BYTES)
+    assert set(whole) == {"chunks", "psd", "psd_frames"} | {f"rx{r}_{k}" for r in (3, 5) for k in ("audio", "iq", "counts", "peak")}
+    assert all(a.dtype in (np.float32, np.float64) for a in whole.values())
+    assert np.array_equal(whole["rx3_audio"], outs[0][0]) and np.array_equal(whole["rx5_audio"], outs[1][0].view(np.float32).reshape(-1, 2))
+    assert np.array_equal(whole["rx5_iq"], outs[1][1].view(np.float32).reshape(-1, 2)) and np.array_equal(whole["psd"], psd)
+    assert np.array_equal(whole["rx3_counts"], cn[0]) and np.array_equal(whole["rx5_peak"], outs[1][3])
+    assert np.array_equal(whole["chunks"], np.arange(B)) and np.array_equal(whole["psd_frames"], np.arange(nframes))
+
+    budget = 2 * 10 ** 6                                  # audio + IQ are 1.6 MB, the PSD 3.1 MB
+    part = dump(tmp_path / "part", budget)
+    assert sum(os.path.getsize(f) for f in (tmp_path / "part").iterdir()) <= budget
+    assert 0 < len(part["chunks"]) < B and 0 < len(part["psd_frames"]) < nframes
+    off = [np.r_[0, np.cumsum(c)] for c in cn]
+    assert np.array_equal(part["rx3_audio"], np.concatenate([outs[0][0][off[0][k]:off[0][k + 1]] for k in part["chunks"].astype(int)]))
+    assert np.array_equal(part["rx5_iq"], np.concatenate([outs[1][1][off[1][k]:off[1][k + 1]] for k in part["chunks"].astype(int)])
+                          .view(np.float32).reshape(-1, 2))
+    assert np.array_equal(part["psd"], psd[part["psd_frames"].astype(int)]) and np.array_equal(part["rx3_counts"], cn[0])
+    again = dump(tmp_path / "again", budget)
+    assert all(np.array_equal(again[k], part[k]) for k in part)
+
+
+def test_plain_run_does_only_the_timed_steps():
+    """Without --full the line needs nothing beyond the timed steps: no oracle check, no CPU baseline; --full keeps them on."""
+    plain, full = bench.parse(["--steps", "7", "--warmup", "2"]), bench.parse(["--full"])
+    assert (plain.steps, plain.warmup, plain.full, plain.verify, plain.dump_outputs) == (7, 2, False, None, None)
+    assert full.full and not full.no_cpu_baseline and not full.no_other_configs
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

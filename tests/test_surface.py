@@ -1,19 +1,20 @@
 """The drop-in boundary against the reference's own text: every `dsp.<name>`, `rx.<attr>...`,
-`psd.<attr>`, ring-buffer method and `lo.<attr>` that /root/reference uses exists on the objects
+`psd.<attr>`, ring-buffer method and `lo.<attr>` that the reference uses exists on the objects
 pysdr_amd.sig_proc provides (scripts/check_surface.py: `ast` only, nothing of the reference is
-imported).  Build-container only -- the reference does not travel to the GPU box."""
+imported).  What the reference uses is read from tests/golden/surface_ref.json, collected from its
+text by tests/golden/make_surface_golden.py."""
+import json
 import os
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = json.load(open(os.path.join(ROOT, "tests", "golden", "surface_ref.json")))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present (GPU box)")
-def test_every_sig_proc_name_the_reference_uses_exists():
+def test_every_sig_proc_name_the_reference_uses_exists(monkeypatch):
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     import check_surface
+    monkeypatch.setattr(check_surface, "collect", lambda: GOLD["uses"])
     rows, missing = check_surface.check()
     assert len(rows) >= 45
     kinds = {r[0] for r in rows}
@@ -27,24 +28,14 @@ def test_every_sig_proc_name_the_reference_uses_exists():
     assert not missing, missing
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present (GPU box)")
 def test_every_device_method_the_reference_calls_exists_on_the_synthetic_sdr():
     """`P.sdr.<method>(...)` / `sdr.<method>(...)` as the reference calls them -- the RX thread and the GUI's message pump in
     receiver.py, setupSDR / check_sdr_settings in utils.py:292-460, the canonical loop of soapy.py -- collected with `ast`
     (nothing of the reference is imported): the synthetic SoapySDR-shaped device answers every one of them, with the
     arities those call sites use, so that the reference's own device set-up could be pointed at it."""
-    import ast
     from pysdr_amd.stream import SOAPY_SDR_RX, SynthSDR
     from pysdr_amd.synth import CONFIGS
-    calls = {}
-    for fn, lo, hi in (("receiver.py", 1, 10 ** 6), ("utils.py", 292, 460), ("soapy.py", 1, 10 ** 6)):
-        tree = ast.parse(open(os.path.join("/root/reference", fn)).read())
-        for n in ast.walk(tree):
-            if not (isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and lo <= n.lineno <= hi):
-                continue
-            v = n.func.value
-            if (isinstance(v, ast.Attribute) and v.attr == "sdr") or (isinstance(v, ast.Name) and v.id == "sdr"):
-                calls.setdefault(n.func.attr, set()).add(len(n.args))
+    calls = GOLD["sdr_calls"]
     assert len(calls) >= 30 and {"readStream", "getGainRange", "hasGainMode", "getGainMode", "setupStream"} <= set(calls)
     dev = SynthSDR(CONFIGS['C2'], nsamp=4096)
     missing = [m for m in calls if not callable(getattr(dev, m, None))]
