@@ -78,8 +78,8 @@ def needs_build():
 
 
 def build_variant(name, verbose=True):
-    """A/B builds without a hipcc on the critical path of a GPU call: ``PYSDR_TUNING=1 PYSDR_MIXDEC_FLAGS=-DMD_LONG_TPB=512
-    python -m pysdr_amd.build --variant tpb512`` compiles ONLY the sources that got extra flags (into ``*.<name>.o``), links
+    """A/B builds without a hipcc on the critical path of a GPU call: ``PYSDR_TUNING=1 PYSDR_MFMA_FLAGS=-DMM_C1_NBUF=3
+    python -m pysdr_amd.build --variant nbuf3`` compiles ONLY the sources that got extra flags (into ``*.<name>.o``), links
     them with the shipped objects of the others into ``libpysdr_hip_<name>.so``; ``PYSDR_TUNING=1 PYSDR_LIB_VARIANT=<name>``
     loads it (``_lib.py``).  Variant libraries are never loaded otherwise and are git-ignored like every ``.so``."""
     build(force=False, verbose=verbose)

@@ -79,12 +79,9 @@ struct MixDecArgs {
   int dq_last, dr_last;   // divmod((tile_out-1)*down, up)
   int yflush, ycap;       // LDS output stage: flushed every yflush tiles; ycap = yflush*tile_out per RX
   int taps_lds;           // 1: the taps are staged in LDS ([nrx][up][kpad] behind the tile buffers); 0: every wave holds its taps in
-                          // registers for the whole launch and reads them from memory once (mixdec_variant: the host guarantees hold mode)
+                          // registers for the whole launch and reads them from memory once (plan_mixdec: the host guarantees hold mode)
 };
-struct MixdecVariant { int tpb, can_hold, nh; };
-MixdecVariant mixdec_variant(int nrx, int up, int kpad, int threads);
-int launch_mixdec(const MixDecArgs& a, int threads, int grid, hipStream_t st);
-size_t mixdec_lds_bytes(const MixDecArgs& a);
+// the plan and the launch of the mix + decimate kernel: mixdec_plan.h
 
 // one RX, short prototype, small DOWN/UP, no raw peak (resamp_small.hip): the fs1 -> FS_OUT stage of broadcast FM
 int resamp_small_span(int up, int down, int kpad);   // LDS samples a workgroup stages; 0 = shape not eligible
@@ -165,7 +162,7 @@ int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t st
 
 // ---- compile-time experiment switches ----------------------------------------------------
 // The kernel sources carry A/B switches only: every one of them keeps the results right (MM_EPI_PLAIN, MM_*_PRIO, MM_C1_* /
-// MM_C4_* shapes, MM_NTX, MM_PART_PLAIN, MD_* of mixdec.hip, FIRX_THREADS, PSDX_WAVE_SCALE, PLLX_PRIO, PYSDR_BLK_STRIDE, ...);
+// MM_C4_* shapes, MM_NTX, MM_PART_PLAIN, FIRX_THREADS, PSDX_WAVE_SCALE, PLLX_PRIO, PYSDR_BLK_STRIDE, ...);
 // `build.py` reads extra -D flags only under PYSDR_TUNING=1 and `pysdr_build_flags_hash()` / the bench line show what a
 // library was built with.  The work-skipping ABLATION branches that rounds 3-5 timed kernels with (MM_NO_*, MM_EPI_ZERO /
 // NO_STORE / WIDE / SAMEPLACE, FIRX_NO_*, AGCX_NO_*, PSDX_NO_*: results WRONG by design) are no longer in the sources: they are

@@ -28,6 +28,7 @@
 //                rows (DOWN samples apart) overlap on few banks.
 #include "common.h"
 #include "mixdec_geom.h"
+#include "mixdec_plan.h"
 #include "hist_roll.h"
 
 namespace pysdr {
@@ -317,9 +318,7 @@ __device__ __forceinline__ void fold_rotate_stage(const float2 (&A)[N], const fl
   }
 }
 
-// Compile-time shape of one instantiation.  NJ = kpad/16 known at compile time (fully unrolled tap loop) or 0 for a runtime
-// loop; TPB = threads per workgroup (the register budget of a wave follows from it: 128 at 1024 threads, 168 at 768);
-// NHX = RX groups a tile's work is dealt out in (0: the default of that TPB).
+// Compile-time shape of one instantiation (mixdec_plan.h: MdKey, PYSDR_MIXDEC_SHAPES, the traits):
 //   TPB = 1024 (the BASELINE configurations, 255-tap prototypes): up to 24 tap pairs per lane are held in registers, the
 //        sub-receivers split into two halves above 4.
 //   TPB = 768 (round 6: the reference's DEFAULT 1001-tap prototype with SEVERAL sub-receivers -- FT8tri:47-74, TEST:30,
@@ -327,45 +326,6 @@ __device__ __forceinline__ void fold_rotate_stage(const float2 (&A)[N], const fl
 //        (126 registers), so one LDS read of x still serves every RX of the group; with the taps in LDS (<R,0>, where these
 //        shapes ran until now) every tap step was 1 + R LDS reads: ft8tri 0.50, 4 RX 0.44, 6 RX 0.30 of the HBM peak
 //        (profiles/r06_baseline_long_prototype_multirx.txt).
-#ifndef MD_LONG_TPB
-#define MD_LONG_TPB 768      // threads of the long-prototype multi-RX shapes (A/B: 512, 768, 1024)
-#endif
-#ifndef MD_LONG_MM
-#define MD_LONG_MM 1         // the long-prototype shapes of 2 - 4 sub-receivers on the matrix cores (A/B: 0 = vector form)
-#endif
-#ifndef MD_STEADY_VEC1
-#define MD_STEADY_VEC1 1     // steady runs for the vector shape <1,11> (1 MS/s x 1 RX: front end 0.376 -> 0.402 of HBM, 5 MS/s x 1: 0.735 -> 0.743; A/B: 0)
-#endif
-#ifndef MD_UP6_MM
-#define MD_UP6_MM 2          // 1001 taps at UP = 6: the matrix-core form from this many sub-receivers (0: never).  One box, front end as a fraction
-                             // of HBM, matrix cores / vector form: 1 MS/s x 1 RX 0.32 / 0.375, x 2 0.31 / 0.27, x 3 0.245 / 0.187; 5 MS/s x 2 0.66 / 0.67,
-                             // x 4 0.61 / 0.445; 7 MS/s x 3 0.73 / 0.61 (scripts/diag/up6_mm_ab.sh, profiles/r06_launch_script_rates.txt)
-#endif
-#ifndef MD_UP6_HOLD
-#define MD_UP6_HOLD 1        // 1001 taps at UP = 6, one or two sub-receivers: taps held in registers (A/B: 0 = the generic form, taps in LDS)
-#endif
-#ifndef MD_STEADY
-#define MD_STEADY 1          // matrix-core shapes: runs of full interior tiles through the add-only tile loop (A/B: 0 = the generic body for every tile)
-#endif
-#ifndef MD_MM_EPCONST
-#define MD_MM_EPCONST -1     // matrix-core shapes: the epilogue lane's LO constants looked up per task (1) or held in registers (0); -1: held
-                             // up to 2 RX (hipcc then hoists more of the task's index arithmetic out of the tile loop: test2rx 0.55 -> 0.58), looked up from 3 (registers)
-#endif
-#ifndef MD_MM_ONEACC
-#define MD_MM_ONEACC 1       // matrix-core shapes with >= 2 RX pairs: one accumulator per pair (0: one per chain; A/B)
-#endif
-#ifndef MD_PHASE_ORDERS
-#define MD_PHASE_ORDERS 2    // matrix-core shapes: how many different phase orders the three waves of a SIMD run (A/B: 1, 2, 3)
-#endif
-#ifndef MD_LONG_NH
-#define MD_LONG_NH 0         // their RX groups: 0 = as few as the registers allow, n = n groups (A/B)
-#endif
-#ifndef MD_XAHEAD
-#define MD_XAHEAD 8          // matrix-core shapes: reads of x in flight ahead of the MFMAs (A/B)
-#endif
-#ifndef MD_XGROUP
-#define MD_XGROUP 7          // x reads per group of the register-tight shapes (A/B)
-#endif
 //   MM = 1 (round 6, the same shapes): the dot products of a task on the MATRIX cores, v_mfma_f32_4x4x1_16b_f32 -- sixteen
 //        independent 4x4 blocks with K = 1.  A task is still (branch, quad of outputs); the sixteen blocks are the sixteen tap
 //        residues k mod 16 (what the sixteen lanes of a DPP row are in the vector form), the four ROWS of a block the four
@@ -377,23 +337,15 @@ __device__ __forceinline__ void fold_rotate_stage(const float2 (&A)[N], const fl
 //        waves fit with nothing spilled; the 16 block sums meet through two DPP row rotations and three permlane swaps.
 //        Why: the vector form at these shapes is bound by how many INSTRUCTIONS its few, register-heavy waves can issue
 //        (126 packed FMAs per task at 3 RX; profiles/r06_long_multirx_variants.txt), not by arithmetic throughput.
-template <int R, int NJ, int TPB, int NHX, int MM = 0>
+template <int R, int NJ, int TPB, int MM>
 struct MdShape {
+  static constexpr MdKey kKey{R, NJ, TPB, MM};
   static constexpr bool kMm = MM != 0;
-  static constexpr int G = (R + 1) / 2;                       // MM: pairs of sub-receivers = 4-column groups
-  static constexpr int kBudget = TPB > 768 ? 128 : (TPB > 512 ? 168 : 256);     // registers per lane
-  static constexpr int kMaxHeld = TPB > 768 ? 24 : (kBudget - 80) / 2;          // tap pairs per lane that may stay in registers (everything else
-                                                                                // of the tile loop takes ~75: <1,21> = 42 + 75)
-  static constexpr int nh_default() {
-    if (MM) return 1;
-    if (TPB > 768) return R > 4 ? 2 : 1;
-    int nh = 1;
-    while (NJ > 0 && ((R + nh - 1) / nh) * NJ > kMaxHeld && nh < R) ++nh;
-    return nh;
-  }
-  static constexpr int NH = NHX > 0 ? NHX : nh_default();     // RX groups
-  static constexpr int RH = (R + NH - 1) / NH;                // RX per task in hold mode
-  static constexpr bool kCanHold = (NJ > 0) && (MM ? (2 * G * NJ + 60 <= kBudget) : (RH * NJ <= kMaxHeld));
+  static constexpr int G = md_g(kKey);
+  static constexpr int kBudget = md_budget(kKey);
+  static constexpr int NH = md_nh(kKey);
+  static constexpr int RH = md_rh(kKey);
+  static constexpr bool kCanHold = md_can_hold(kKey);
 };
 
 typedef float md_f4 __attribute__((ext_vector_type(4)));
@@ -456,17 +408,17 @@ __device__ __forceinline__ void mm_fold_rotate_stage(const md_f4 (&acc)[G], int 
 // an RX pair; xr = this lane's LDS pointer (block b, row i: x[n_i - b - 16 (NJ - 1)], so that step jj reads element 16 (NJ - 1 - jj)).
 // G = 1: the Re x chain and the Im x chain have an accumulator each (a chain on ONE accumulator issues every 15 cycles instead of
 // 8: scripts/diag/mfma4x4_probe.hip); G >= 2: the pairs alternate, one accumulator per pair is enough.
-// The reads of x go through a RING of kXA register pairs, kXA steps ahead of the MFMAs that use them, pinned by
+// The reads of x go through a RING of kXA = 8 register pairs, kXA steps ahead of the MFMAs that use them, pinned by
 // sched_group_barrier: left alone hipcc reuses four registers and puts a full s_waitcnt lgkmcnt(0) in front of every four MFMAs --
 // one exposed LDS latency per 40 cycles of matrix work (the same finding as mixdec_mfma.hip's consumer).
 template <int G, int NJ>
 __device__ __forceinline__ void mm_task_dots(lds_cf2 xr, const float (&bre)[G][NJ], const float (&bim)[G][NJ], md_f4 (&acc)[G]) {
-  constexpr int kNA = (G == 1 || !MD_MM_ONEACC) ? 2 * G : G;
+  constexpr int kNA = (G == 1) ? 2 * G : G;
   md_f4 accs[kNA];
 #pragma unroll
   for (int q = 0; q < kNA; ++q) accs[q] = (md_f4){0.f, 0.f, 0.f, 0.f};
   constexpr int kTop = 16 * (NJ - 1);
-  constexpr int kXA = (MD_XAHEAD < NJ) ? MD_XAHEAD : NJ;
+  constexpr int kXA = (8 < NJ) ? 8 : NJ;
   float2 ring[kXA];
 #pragma unroll
   for (int u = 0; u < kXA; ++u) ring[u] = lds_ld(xr, kTop - 16 * u);
@@ -523,8 +475,11 @@ __device__ __forceinline__ void vec_task_dots(lds_cf2 xr, const float2 (&greg)[R
   }
 }
 
+// (NHX: 0 in every instantiation -- the retired override of MdShape::NH -- kept in the signature so that the kernels' symbol
+//  names, which tests/test_isa_checks.py and the stored profiles match, stay as they were)
 template <int R, int NJ, int TPB, int NHX, int MM>
 __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
+  static_assert(NHX == 0, "the RX groups follow from the shape (md_nh)");
   extern __shared__ __attribute__((aligned(16))) float2 lds[];
   float2* const buf0 = lds;                    // [tile_cap]
   float2* const buf1 = lds + a.tile_cap;       // [tile_cap]
@@ -549,7 +504,7 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
 
   // ---- stage the LO-modulated taps once
   if (!a.taps_lds) {
-    // (hold mode guaranteed by the host, mixdec_variant(): every wave reads its own taps straight from memory below)
+    // (hold mode guaranteed by the host, plan_mixdec(): every wave reads its own taps straight from memory below)
   } else if (a.aligned16) {
     const int nt4 = (R * a.up * a.kpad) >> 1;                   // taps as 16-B slots
     const float4* src = reinterpret_cast<const float4*>(a.taps);
@@ -568,9 +523,11 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
   // reads of a C3 task disappear).  For that the tasks are dealt out by (branch, RX half): wave w
   // belongs to group w % (UP*NH), works on that group's branch and -- above 4 RX -- on one half
   // of the sub-receivers only, and walks the quads with stride nwaves / (UP*NH).
-  typedef MdShape<R, NJ, TPB, NHX, MM> Sh;
+  typedef MdShape<R, NJ, TPB, MM> Sh;
   constexpr bool kMm = Sh::kMm;
-  constexpr bool kEpConst = (MD_MM_EPCONST < 0) ? (R >= 3) : (MD_MM_EPCONST != 0);
+  // matrix-core form: the epilogue lane's LO constants held in registers up to 2 RX (hipcc then hoists more of the task's index
+  // arithmetic out of the tile loop: test2rx 0.55 -> 0.58), looked up per task from 3 RX (held, they spilled)
+  constexpr bool kEpConst = R >= 3;
   constexpr int NH = Sh::NH;                            // RX groups (halves at 1024 threads)
   constexpr int RH = Sh::RH;                            // RX per task in hold mode
   constexpr bool kCanHold = Sh::kCanHold;
@@ -665,9 +622,10 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
     // longest stretch of tiles from here that are full, not at either end of the call or of this workgroup's share, copied whole
     // (LDS-DMA pieces inside the call) and owned by ONE chunk (fast peak) is found by two divisions, its per-lane constants are
     // set up once, and its tiles run a loop that only adds.  Same reads, same MFMA chains, same block reduction, same phases:
-    // bit for bit the generic body's results (tests: every cut-independence test crosses both paths; MD_STEADY=0 for the A/B).
-    constexpr bool kSteadyVec = !kMm && kCanHold && R == 1 && NJ == 11 && MD_STEADY_VEC1;     // ... and one vector shape, below
-    if constexpr ((kMm && MD_STEADY) || kSteadyVec) {
+    // bit for bit the generic body's results (tests: every cut-independence test crosses both paths).
+    // ... and one vector shape, below (1 MS/s x 1 RX: front end 0.376 -> 0.402 of HBM, 5 MS/s x 1: 0.735 -> 0.743)
+    constexpr bool kSteadyVec = !kMm && kCanHold && R == 1 && NJ == 11;
+    if constexpr (kMm || kSteadyVec) {
       int run = 0;
       const int dq = a.dq_tile;
       const int npieces_s = (cur.npairs + 63) >> 6;
@@ -726,7 +684,7 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
           const float4* const xs_v = (const float4*)(const __attribute__((address_space(3))) float4*)(size_t)xs_b;
           dma_wait();
           __syncthreads();
-          const int ord_s = (kMm && MD_PHASE_ORDERS > 1) ? ((MD_PHASE_ORDERS == 2) ? ((wave >> 2) & 1) : (wave >> 2) % 3) : 0;
+          const int ord_s = kMm ? ((wave >> 2) & 1) : 0;
           if (ord_s != 1) steady_stage(src_next, voff0, xn_b, npieces_s, wave, nwaves);
           if (ord_s == 0) pk_run = steady_peak(xs_v, pk_p0, pk_phi, nthr, pk_run);
           {
@@ -793,9 +751,8 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
     // Matrix-core shapes: the three waves that share a SIMD (w, w + 4, w + 8) would run their MFMA chains at the same time, and
     // the matrix pipe then idle through everybody's copy / peak phases (scripts/diag/mixdec_stamps.py ft8tri,
     // profiles/r06_ft8tri_stamps.txt: the dot-product phase of a task took 2800 cycles where 84 MFMAs alone take ~900).
-    // Each of the three takes the phases of a tile in its own order:  0: copies, peak, DOTS   1: DOTS, copies, peak
-    // 2: copies, DOTS, peak   (MD_PHASE_ORDERS = 1: all of them order 0, 2: orders 0 1 0; A/B)
-    const int ord = (kMm && MD_PHASE_ORDERS > 1) ? ((MD_PHASE_ORDERS == 2) ? ((wave >> 2) & 1) : (wave >> 2) % 3) : 0;
+    // So they take the phases of a tile in the orders 0, 1, 0:  0: copies, peak, DOTS   1: DOTS, copies, peak
+    const int ord = kMm ? ((wave >> 2) & 1) : 0;
     const bool have_next = tb + 1 < t_end;
     if (have_next) {
       nxt = (tb + 2 < a.ntiles) ? tile_advance(a, cur) : tile_geometry(a, tb + 1);
@@ -942,7 +899,7 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
         // Where the taps leave few registers (three RX x 21 tap pairs = 126 of 168) the reads of x come in GROUPS of kXG with a
         // compiler fence between them: left alone hipcc hoists all 21 reads to the top (42 more registers) and spills.
         constexpr int kNJ = kCanHold ? NJ : 1;
-        constexpr int kXG = (Sh::kBudget - 2 * RH * NJ < 64) ? MD_XGROUP : kNJ;
+        constexpr int kXG = (Sh::kBudget - 2 * RH * NJ < 64) ? 7 : kNJ;
 #pragma unroll
         for (int j0 = 0; j0 < kNJ; j0 += kXG) {
           float2 xg[kXG];
@@ -1007,15 +964,11 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
           int r = 0, c2 = ch;
           while (c2 >= cpr) { c2 -= cpr; ++r; }
           const int j = c2 * 64 + lane;
-#ifdef MD_Y_PLAIN                     // A/B: plain stores
-          if (j < n_st) a.y[r][i_base + j] = ys[r * a.ycap + j];
-#else
           if (j < n_st) {
             typedef float md_f2 __attribute__((ext_vector_type(2)));
             const float2 v = ys[r * a.ycap + j];
             __builtin_nontemporal_store((md_f2){v.x, v.y}, (md_f2*)(a.y[r] + i_base + j));
           }
-#endif
         }
       i_base = cur.i_first + cur.tile_n;
     }
@@ -1026,7 +979,7 @@ __global__ __launch_bounds__(TPB) void mixdec_kernel(const MixDecArgs a) {
   if (lane == 63 && pk_run > 0.f) atomicMax(a.peak + pk_chunk, __float_as_uint(pk_run));
 }
 
-template <int R, int NJ, int TPB, int NHX, int MM>
+template <int R, int NJ, int TPB, int MM>
 int launch_rj(const MixDecArgs& a, int threads, int grid, size_t lds, hipStream_t st) {
   // the attribute is per (function, device): one bit per device, guarded against contexts on
   // other threads / other devices of the same process (P.GPU_DEVICE, cfg.device)
@@ -1037,110 +990,24 @@ int launch_rj(const MixDecArgs& a, int threads, int grid, size_t lds, hipStream_
     PYSDR_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(attr_mu);
     if (!((attr_done >> (dev & 63)) & 1ull)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mixdec_kernel<R, NJ, TPB, NHX, MM>),
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mixdec_kernel<R, NJ, TPB, 0, MM>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) {
-        set_last_error("hipFuncSetAttribute(mixdec<%d,%d,%d,%d,%d>): %s", R, NJ, TPB, NHX, MM, hipGetErrorString(e));
+        set_last_error("hipFuncSetAttribute(mixdec<%d,%d,%d,%d>): %s", R, NJ, TPB, MM, hipGetErrorString(e));
         return PYSDR_ERR_HIP;
       }
       attr_done |= 1ull << (dev & 63);
     }
   }
   if (threads > TPB) threads = TPB;
-  hipLaunchKernelGGL((mixdec_kernel<R, NJ, TPB, NHX, MM>), dim3(grid), dim3(threads), lds, st, a);
+  hipLaunchKernelGGL((mixdec_kernel<R, NJ, TPB, 0, MM>), dim3(grid), dim3(threads), lds, st, a);
   PYSDR_HIP_CHECK(hipGetLastError());
   return PYSDR_OK;
 }
 
-// Which instantiation a decimator's shape runs on -- ONE table for the launch and for the host's plan (mixdec_variant).
-//   f.template go<R, NJ, TPB, NHX, MM>()
-template <int R, class F>
-int md_dispatch_r(int up, int kpad, int threads, F& f) {
-  // 255-tap prototypes at UP = 3 (the BASELINE configurations) have 96 taps per branch
-  if (kpad == 96) return f.template go<R, 6, 1024, 0, 0>();
-  // the default 1001-tap prototype at UP = 6 (1, 5, 7 MS/s -> 48 kHz: FT8:42, FT8FT4:34, FT8dual:43): 167 taps per branch, eleven
-  // tap pairs per lane held in registers by six groups of waves (one sub-receiver; two with MD_UP6_MM > 2) ...
-#if MD_UP6_MM
-  // ... and on the matrix cores (12 waves, two per branch) from MD_UP6_MM sub-receivers
-  if constexpr (R >= MD_UP6_MM && R <= 6) {
-    if (kpad == 176 && up == 6 && threads == 1024) return f.template go<R, 11, 768, 0, 1>();
-  }
-#endif
-#if MD_UP6_HOLD
-  if constexpr (R <= 2 && (MD_UP6_MM == 0 || R < MD_UP6_MM)) {
-    if (kpad == 176 && up == 6 && threads == 1024) return f.template go<R, 11, 1024, 0, 0>();
-  }
-#endif
-  // single-RX long filters: the 255-tap video filter of the broadcast-FM front end (UP = 1, 256
-  // taps in one branch) and the reference's default 1001-tap prototype at UP = 3 (336 per branch)
-  if constexpr (R == 1) {
-    // the fs1 -> FS_OUT resampler of broadcast FM: 24/125 with 64 taps per branch (more branches than waves: generic
-    // task order, but a compile-time tap loop)
-    if (kpad == 64) return f.template go<R, 4, 1024, 0, 0>();
-    if (kpad == 256) return f.template go<R, 16, 1024, 0, 0>();
-    if (kpad == 336) return f.template go<R, 21, 1024, 0, 0>();
-  }
-  // the default 1001-tap prototype at UP = 3 with several sub-receivers (8 and 4 MS/s -> 48 kHz: FT8tri, TEST): 12 waves that
-  // hold their taps.  Only with the default thread count: pysdr_set_tile(threads) asks for the generic form (A/B).
-  if constexpr (R >= 2 && R <= 6) {
-    if (kpad == 336 && up == 3 && threads == 1024) {
-#if MD_LONG_MM
-      // 2 - 4 RX: 12 waves; 5, 6 RX (three RX pairs = 126 registers of tap operands): 8 waves of up to 256 registers
-      if constexpr (R <= 4) return f.template go<R, 21, 768, 0, 1>();
-      else return f.template go<R, 21, 512, 0, 1>();
-#else
-      return f.template go<R, 21, MD_LONG_TPB, (MD_LONG_NH <= R ? MD_LONG_NH : R), 0>();
-#endif
-    }
-  }
-  return f.template go<R, 0, 1024, 0, 0>();
-}
-template <class F>
-int md_dispatch(int nrx, int up, int kpad, int threads, F& f) {
-  switch (nrx) {
-    case 1: return md_dispatch_r<1>(up, kpad, threads, f);
-    case 2: return md_dispatch_r<2>(up, kpad, threads, f);
-    case 3: return md_dispatch_r<3>(up, kpad, threads, f);
-    case 4: return md_dispatch_r<4>(up, kpad, threads, f);
-    case 5: return md_dispatch_r<5>(up, kpad, threads, f);
-    case 6: return md_dispatch_r<6>(up, kpad, threads, f);
-    case 7: return md_dispatch_r<7>(up, kpad, threads, f);
-    case 8: return md_dispatch_r<8>(up, kpad, threads, f);
-    default: set_last_error("mixdec: nrx=%d", nrx); return PYSDR_ERR_ARG;
-  }
-}
-
-struct MdLaunch {
-  const MixDecArgs& a; int threads, grid; size_t lds; hipStream_t st;
-  template <int R, int NJ, int TPB, int NHX, int MM> int go() { return launch_rj<R, NJ, TPB, NHX, MM>(a, threads, grid, lds, st); }
-};
-struct MdQuery {
-  MixdecVariant v;
-  template <int R, int NJ, int TPB, int NHX, int MM> int go() {
-    typedef MdShape<R, NJ, TPB, NHX, MM> Sh;
-    v.tpb = TPB;
-    v.can_hold = Sh::kCanHold ? 1 : 0;
-    v.nh = Sh::NH;
-    return PYSDR_OK;
-  }
-};
-
 }  // namespace
 
-size_t mixdec_lds_bytes(const MixDecArgs& a) {
-  return (2 * (size_t)a.tile_cap + (a.taps_lds ? (size_t)a.nrx * a.up * a.kpad : 0) + (size_t)a.nrx * a.ycap) * sizeof(float2);
-}
-
-// What the host's plan needs to know about the instantiation a shape runs on: its thread count, and whether its waves hold
-// their taps in registers when there are at least up * nh of them and tile_out is a multiple of up (then the taps need no LDS).
-MixdecVariant mixdec_variant(int nrx, int up, int kpad, int threads) {
-  MdQuery q;
-  q.v.tpb = 1024; q.v.can_hold = 0; q.v.nh = 1;
-  (void)md_dispatch(nrx, up, kpad, threads, q);
-  return q.v;
-}
-
-int launch_mixdec(const MixDecArgs& a, int threads, int grid, hipStream_t st) {
+int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStream_t st) {
   const size_t lds = mixdec_lds_bytes(a);
   if (lds > 160 * 1024) {
     set_last_error("mixdec: LDS request %zu > 160 KiB", lds);
@@ -1148,8 +1015,12 @@ int launch_mixdec(const MixDecArgs& a, int threads, int grid, hipStream_t st) {
   }
   if (grid > a.ntiles) grid = a.ntiles;
   if (grid < 1) grid = 1;
-  MdLaunch l{a, threads, grid, lds, st};
-  return md_dispatch(a.nrx, a.up, a.kpad, threads, l);
+#define PYSDR_MIXDEC_LAUNCH(R, NJ, TPB, MM) \
+  if (key == MdKey{R, NJ, TPB, MM}) return launch_rj<R, NJ, TPB, MM>(a, threads, grid, lds, st);
+  PYSDR_MIXDEC_SHAPES(PYSDR_MIXDEC_LAUNCH)
+#undef PYSDR_MIXDEC_LAUNCH
+  set_last_error("mixdec: no instantiation <%d,%d,%d,%d>", key.r, key.nj, key.tpb, key.mm);
+  return PYSDR_ERR_ARG;
 }
 
 }  // namespace pysdr

@@ -1,9 +1,9 @@
-# output stores of the two mix + decimate kernels: nontemporal (shipped) against plain, all four configurations, twice
+# output stores of the matrix-core mix + decimate kernel (mixdec_mfma.hip): nontemporal (shipped) against plain, all four configurations, twice
 export PYSDR_TUNING=1   # build.py reads PYSDR_*_FLAGS only under the tuning master switch (round 5)
 cp pysdr_amd/libpysdr_hip.so /tmp/keep.so
 for rep in 1 2; do
 for fl in "nt" "plain"; do
-  if [ $fl = plain ]; then export PYSDR_MIXDEC_FLAGS="-DMD_Y_PLAIN" PYSDR_MFMA_FLAGS="-DMM_EPI_PLAIN"; else export PYSDR_MIXDEC_FLAGS="" PYSDR_MFMA_FLAGS=""; fi
+  if [ $fl = plain ]; then export PYSDR_MFMA_FLAGS="-DMM_EPI_PLAIN"; else export PYSDR_MFMA_FLAGS=""; fi
   python -m pysdr_amd.build --force > /tmp/build.log 2>&1 || { echo "build failed: $fl"; grep -i "error" /tmp/build.log | head -3; continue; }
   for w in c1 c2 c3 c4; do
   timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-host-fed --no-other-configs --steps 15 --warmup 3 2>/dev/null | python -c "

@@ -3,7 +3,8 @@
 // (stub_kernels.cpp) -- every BASELINE rate, ragged call lengths, every setter between calls, the
 // lazily allocated buffers (AM-Synch, WFM), the spectrum object on both its paths, the ingest ring's
 // slot state machine with its misuse errors.  `san_main race` runs pysdr_process on one thread against
-// the setters on another (the reference's RX thread vs Qt thread) for ThreadSanitizer.
+// the setters on another (the reference's RX thread vs Qt thread) for ThreadSanitizer.  The mix + decimate
+// planner (pysdr_amd/csrc/mixdec_plan.h) is also swept directly over every shape, tile override and thread count.
 //   build + run: tests/host_san/run.sh   (tests/test_host_sanitizers.py does that)
 #include <atomic>
 #include <cmath>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "../../include/pysdr_hip.h"
+#include "mixdec_plan.h"
 
 #define OK(expr)                                                                                    \
   do {                                                                                              \
@@ -298,6 +300,36 @@ static void spectrum() {
   OK(pysdr_fir_real(0, xx.data(), hh.data(), 255, yy.data(), 500));
 }
 
+// plan_mixdec over 1 - 8 sub-receivers, the decimator shapes of the library, every tile override and thread count
+namespace pysdr { void check_mixdec_plan(const MixDecArgs& a, MdKey key, int threads); }
+static void planner_sweep() {
+  int d1 = 0, up2 = 0, down2 = 0;
+  OK(pysdr_wfm_params(10e6, 48000.0, &d1, &up2, &down2));
+  struct Shape { int up, down, ntaps; };
+  const Shape shapes[] = {{3, 500, 255}, {3, 128, 255}, {3, 500, 1001}, {3, 250, 1001}, {6, 125, 1001}, {3, 128, 1001},
+                          {1, d1, 255}, {up2, down2, 64 * up2}};      // broadcast FM: the IF front end, the fs1 -> FS_OUT resampler
+  int nplans = 0;
+  for (const Shape& sh : shapes)
+    for (int nrx = 1; nrx <= PYSDR_MAX_RX; ++nrx)
+      for (int tile_bytes : {0, 4096, 12288, 32768, 150 * 1024})
+        for (int threads : {1024, 512, 64})
+          for (int n_out : {0, 12345}) {
+            pysdr::MixDecArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.nrx = nrx; a.up = sh.up; a.down = sh.down; a.n_out = n_out;
+            a.kpad = ((sh.ntaps + sh.up - 1) / sh.up + 15) / 16 * 16;
+            pysdr::MdKey key;
+            if (!pysdr::plan_mixdec(a, tile_bytes, threads, 1, 0, key)) {
+              std::fprintf(stderr, "planner: no plan for %d RX, %d/%d, %d taps, tile %d, %d threads\n", nrx, sh.up, sh.down, sh.ntaps,
+                           tile_bytes, threads);
+              std::exit(1);
+            }
+            pysdr::check_mixdec_plan(a, key, threads);
+            ++nplans;
+          }
+  std::printf("planner sweep: %d plans\n", nplans);
+}
+
 static void race() {
   // one thread processes chunks, another turns the knobs (receiver.py RX thread vs the Qt thread)
   const Rate r = kRates[2];
@@ -345,6 +377,7 @@ int main(int argc, char** argv) {
   OK(pysdr_device_count(&ndev));
   FAILS(pysdr_create(nullptr, nullptr));
   FAILS(pysdr_set_overlap(nullptr, 1));
+  planner_sweep();
   for (int pass = 0; pass < 3; ++pass) {
   g_overlap = pass == 0 ? 0 : (pass == 1 ? 2 : 1);
   for (const Rate& r : kRates) {

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "mixdec_geom.h"
 #include "mixdec_mfma_geom.h"
+#include "mixdec_plan.h"
 
 namespace pysdr {
 
@@ -48,37 +49,30 @@ bool same_tile(const Tile& a, const Tile& b) {
 
 }  // namespace
 
-size_t mixdec_lds_bytes(const MixDecArgs& a) {
-  return (2 * (size_t)a.tile_cap + (a.taps_lds ? (size_t)a.nrx * a.up * a.kpad : 0) + (size_t)a.nrx * a.ycap) * sizeof(float2);
-}
-
-// The host's view of which instantiation a shape runs on (mixdec.hip md_dispatch / MdShape, restated: the templates do not
-// compile without hipcc): the long-prototype multi-RX shapes are 12 (2-4 RX) or 8 (5, 6 RX) waves that hold their taps.
-MixdecVariant mixdec_variant(int nrx, int up, int kpad, int threads) {
-  MixdecVariant v{1024, 0, 1};
-  if (kpad == 336 && up == 3 && threads == 1024 && nrx >= 2 && nrx <= 6) { v.tpb = (nrx <= 4) ? 768 : 512; v.can_hold = 1; v.nh = 1; }
-  else if (kpad == 96) { v.nh = (nrx > 4) ? 2 : 1; v.can_hold = 1; }
-  else if (nrx == 1 && (kpad == 64 || kpad == 256 || kpad == 336)) v.can_hold = 1;
-  return v;
-}
-
 static void roll_on_host(const float2* x, const float2* hist_old, float2* hist_new, int hist_len, uint32_t n_total, unsigned* zero, int zero_n);
-int launch_mixdec(const MixDecArgs& a, int threads, int grid, hipStream_t) {
-  if (a.hist_new) roll_on_host(a.x, a.hist, a.hist_new, a.hist_len, a.n_total, a.zero, a.zero_n);
+// What every plan_mixdec result must satisfy (launch_mixdec below; the planner sweep of san_main.cpp): an instantiation that
+// exists; waves that hold their taps (taps_lds = 0) and the matrix-core form only in hold mode, with the instantiation's own
+// thread count (mixdec.hip: `hold`); the LDS budget; a tile and output stage the kernel can walk.
+void check_mixdec_plan(const MixDecArgs& a, MdKey key, int threads) {
   SAN_CHECK(threads >= 64 && threads <= 1024 && (threads & 63) == 0, "threads %d", threads);
-  if (!a.taps_lds) {
-    // the waves hold their taps (no LDS copy of them): the plan must guarantee hold mode for the instantiation's own thread count
-    const MixdecVariant v = mixdec_variant(a.nrx, a.up, a.kpad, threads);
-    const int nwaves = std::min(threads, v.tpb) / 64;
-    SAN_CHECK(v.tpb != 1024 && v.can_hold && a.up * v.nh <= nwaves && a.tile_out % a.up == 0, "taps_lds = 0 without hold mode (tile_out %d, %d waves)", a.tile_out, nwaves);
-  }
-  SAN_CHECK(grid >= 1, "grid %d", grid);
+  SAN_CHECK(md_listed(key), "no instantiation <%d,%d,%d,%d>", key.r, key.nj, key.tpb, key.mm);
+  SAN_CHECK(key.r == a.nrx, "instantiation for %d RX, plan for %d", key.r, a.nrx);
+  const int nwaves = std::min(threads, key.tpb) / 64;
+  const bool hold = md_can_hold(key) && a.up * md_nh(key) <= nwaves && a.tile_out % a.up == 0;
+  SAN_CHECK(hold || (a.taps_lds && !key.mm), "taps_lds %d, <%d,%d,%d,%d> without hold mode (tile_out %d, %d waves)", a.taps_lds,
+            key.r, key.nj, key.tpb, key.mm, a.tile_out, nwaves);
   SAN_CHECK(mixdec_lds_bytes(a) <= 160 * 1024, "LDS %zu", mixdec_lds_bytes(a));
   SAN_CHECK(a.nrx >= 1 && a.nrx <= PYSDR_MAX_RX && a.up >= 1 && a.down >= 1 && a.kpad % 16 == 0, "shape");
-  SAN_CHECK(a.hist_len >= a.kpad + 2 && (a.hist_len & 1) == 0, "hist_len %d kpad %d", a.hist_len, a.kpad);
   SAN_CHECK(a.tile_out >= 2 && (a.tile_out & 1) == 0 && a.ycap == a.yflush * a.tile_out && a.yflush >= 1, "tile_out %d", a.tile_out);
   SAN_CHECK(a.ntiles >= 1 && (long long)a.ntiles * a.tile_out >= a.n_out && (long long)(a.ntiles - 1) * a.tile_out <= std::max(a.n_out, 1), "ntiles");
   SAN_CHECK(a.dq_tile == (int)(((long long)a.tile_out * a.down) / a.up) && a.dr_tile == (int)(((long long)a.tile_out * a.down) % a.up), "tile step");
+}
+
+int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStream_t) {
+  if (a.hist_new) roll_on_host(a.x, a.hist, a.hist_new, a.hist_len, a.n_total, a.zero, a.zero_n);
+  check_mixdec_plan(a, key, threads);
+  SAN_CHECK(grid >= 1, "grid %d", grid);
+  SAN_CHECK(a.hist_len >= a.kpad + 2 && (a.hist_len & 1) == 0, "hist_len %d kpad %d", a.hist_len, a.kpad);
   // every byte the kernel may read or write exists
   read_all(a.x, a.n_total);
   read_all(a.hist, (size_t)a.hist_len);

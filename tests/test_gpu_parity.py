@@ -94,10 +94,13 @@ def nfm_rounding_allowance(ro, iq_all):
     return np.convolve(a, np.abs(np.asarray(ro.demod.taps, np.complex128)), mode='valid')
 
 
-def run_both(cfg, chunks, seed, check_every=True):
+def run_both(cfg, chunks, seed, check_every=True, tile=None):
     x = so.synth_iq(cfg, sum(chunks), seed)
     L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
     P, g = make_gpu_receivers(cfg, max_batch_chunks=-(-max(chunks) // L))
+    if tile:                                   # pysdr_set_tile(tile_bytes, threads) on the shared context
+        from pysdr_amd import _lib
+        _lib.check(_lib.lib().pysdr_set_tile(P._pysdr_stream.h, *tile), "pysdr_set_tile")
     o = so.make_receivers(cfg, np.float32)
     pos = 0
     worst = {}
@@ -551,6 +554,16 @@ def test_reference_launch_scripts_multi_rx_1001_taps(name):
     cfg = so.CONFIGS[name]
     L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
     run_both(cfg, [L, L, 1000, 7, L - 13, 2 * L + 5, 333], seed=41)
+
+
+@pytest.mark.parametrize("name", ["FT8TRI", "TEST2RX"])
+def test_multi_rx_1001_taps_with_tiles_too_small_to_hold_the_taps(name):
+    """pysdr_set_tile(12288, 1024) leaves FT8TRI 4 and TEST2RX 10 outputs per tile: not a multiple of UP = 3, so the waves of the
+    matrix-core shapes cannot hold their taps, and the plan runs the generic instantiation with the taps in LDS (mixdec_plan.h;
+    ADVICE round 6: the matrix-core instantiation ran instead, with its own lane mapping).  Every sample against the oracle."""
+    cfg = so.CONFIGS[name]
+    L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
+    run_both(cfg, [L, L, 1000, 7, L - 13, 2 * L + 5, 333], seed=43, tile=(12288, 1024))
 
 
 @pytest.mark.parametrize("grid", [0, 3])

@@ -29,10 +29,13 @@ def _run(which, tmp_path):
     return p.stdout
 
 
-def test_host_half_under_address_and_ub_sanitizers(tmp_path):
+def test_host_half_and_mixdec_plans_under_address_and_ub_sanitizers(tmp_path):
+    """The launch layer checks every mix + decimate launch against the library's own plan header
+    (pysdr_amd/csrc/mixdec_plan.h); the driver also sweeps the planner over every shape, tile override and thread count."""
     out = _run("asan", tmp_path)
     assert "HOST_SAN_OK" in out and "HOST_SAN_RACE_OK" in out
+    assert "planner sweep: 1920 plans" in out
 
 
-def test_setters_against_process_under_thread_sanitizer(tmp_path):
+def test_setters_against_process_under_thread_sanitizer_over_the_shared_plan(tmp_path):
     assert "HOST_SAN_RACE_OK" in _run("tsan", tmp_path)
