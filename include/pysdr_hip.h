@@ -263,6 +263,25 @@ int  pysdr_waterfall_image_rows(pysdr_waterfall* wf, float pan_dr, int npsd, flo
 int  pysdr_waterfall_peaks(pysdr_waterfall* wf, const float* line, int n, double height, int distance, int* idx_out, int cap,
                            int* n_out);
 
+/* ---- wideband RTTY decoder bank (RTTY_Decoder.decode, rtty.py:483-565,609-700; find_sigs :744-764) ----------------
+ * One Baudot decoder per mark bin b in [bin_lo, bin_hi) (space bin b + nbins_shift) and the signal finder over the mark
+ * bins [find_lo, find_hi) (may be empty), fed the filterbank lines [nlines][nfft] of pysdr_spectrum_batch: flipped = 1 is
+ * the reference's np.flipud order (what RTTY_Filterbank.push returns), flipped = 0 the unflipped order it leaves in device
+ * memory.  Both ranges lie inside [0, nfft - nbins_shift); nlines <= max_lines <= 32768.  Lines are numbered 1, 2, ...
+ * across calls (pysdr_rtty_reset starts again at 1 with zeroed history); any cut of a stream into calls gives the same
+ * results bit for bit.  decode reports, for every decision the call completes (lines n = 30 j; *n_dec of them, at most
+ * nlines / 30 + 1) and every decoder, row-major [decision][bin - bin_lo]: codes (-1 nothing emitted, else
+ * sym + 32 * FIGS shift), t (the timing line minus one, rtty.py:554) and snr2 (NaN where t - tlast < 25: no symbol
+ * decided).  ndet[nlines]: the finder's count per line.  isym / best [nlines][nbins] (NULL skips them): the best
+ * symbol and its score per line.  Host buffers; lines is a device pointer when on_device != 0. */
+typedef struct pysdr_rtty pysdr_rtty;
+int  pysdr_rtty_create(int device, int nfft, int nbins_shift, int bin_lo, int bin_hi, int find_lo, int find_hi,
+                       int max_lines, pysdr_rtty** out);
+void pysdr_rtty_destroy(pysdr_rtty* rt);
+int  pysdr_rtty_reset(pysdr_rtty* rt);
+int  pysdr_rtty_decode(pysdr_rtty* rt, const float* lines, int nlines, int on_device, int flipped, int* codes,
+                       long long* t, double* snr2, int* n_dec, int* ndet, int* isym, float* best);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

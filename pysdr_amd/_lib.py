@@ -105,6 +105,10 @@ PROTOTYPES = {
     "pysdr_waterfall_image": (_i, [_vp, _f, _pf, _pf, _pf]),
     "pysdr_waterfall_image_rows": (_i, [_vp, _f, _i, _pf, _pf, _pf]),
     "pysdr_waterfall_peaks": (_i, [_vp, _pf, _i, C.c_double, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
+    "pysdr_rtty_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "pysdr_rtty_destroy": (None, [_vp]),
+    "pysdr_rtty_reset": (_i, [_vp]),
+    "pysdr_rtty_decode": (_i, [_vp, _vp, _i, _i, _i, _pi, C.POINTER(C.c_longlong), _pd, _pi, _pi, _pi, _pf]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),
@@ -165,3 +169,7 @@ def as_pd(a):
 
 def as_pf(a):
     return a.ctypes.data_as(_pf)
+
+
+def as_pi(a):
+    return a.ctypes.data_as(_pi)
