@@ -82,7 +82,10 @@ def build_variant(name, verbose=True):
     python -m pysdr_amd.build --variant nbuf3`` compiles ONLY the sources that got extra flags (into ``*.<name>.o``), links
     them with the shipped objects of the others into ``libpysdr_hip_<name>.so``; ``PYSDR_TUNING=1 PYSDR_LIB_VARIANT=<name>``
     loads it (``_lib.py``).  Variant libraries are never loaded otherwise and are git-ignored like every ``.so``."""
-    build(force=False, verbose=verbose)
+    if needs_build():
+        # (building it from here would compile the SHIPPED library with the variant's PYSDR_*_FLAGS still in the environment)
+        raise RuntimeError("the shipped library is missing or older than its sources: run `python -m pysdr_amd.build` "
+                           "without PYSDR_TUNING / PYSDR_*_FLAGS first, then build the variant")
     hipcc = os.path.join(ROCM, "bin", "hipcc")
     extra, fhash = extra_flags(False)
     objs, procs = [], []

@@ -25,7 +25,10 @@ inline rocfft_status rocfft_execution_info_create(rocfft_execution_info* i) { *i
 inline rocfft_status rocfft_execution_info_destroy(rocfft_execution_info i) { delete i; return 0; }
 inline rocfft_status rocfft_execution_info_set_work_buffer(rocfft_execution_info i, void* w, size_t n) { i->work = w; i->work_bytes = n; return 0; }
 inline rocfft_status rocfft_execution_info_set_stream(rocfft_execution_info i, void* s) { i->st = (hipStream_t)s; return 0; }
-inline rocfft_status rocfft_execute(rocfft_plan p, void** in, void**, rocfft_execution_info) {
+inline rocfft_status rocfft_execute(rocfft_plan p, void** in, void**, rocfft_execution_info info) {
+  if (fake_hip::tracing())
+    fake_hip::Line("rocfft_execute").st(info ? info->st : nullptr).i("n", (long long)p->n).i("batch", (long long)p->batch).p("buf", in[0])
+        .p("work", info ? info->work : nullptr).i("work_bytes", info ? (long long)info->work_bytes : 0);
   // touch the whole in-place buffer the plan was made for: n x batch complex floats
   float2* b = static_cast<float2*>(in[0]);
   for (size_t i = 0; i < p->n * p->batch; ++i) b[i].x += 0.f;

@@ -4,17 +4,21 @@
 // lazily allocated buffers (AM-Synch, WFM), the spectrum object on both its paths, the ingest ring's
 // slot state machine with its misuse errors.  `san_main race` runs pysdr_process on one thread against
 // the setters on another (the reference's RX thread vs Qt thread) for ThreadSanitizer.  The mix + decimate
-// planner (pysdr_amd/csrc/mixdec_plan.h) is also swept directly over every shape, tile override and thread count.
+// planner (pysdr_amd/csrc/mixdec_plan.h) is also swept directly over every shape, tile override and thread count, and the
+// plans of the two serial loops (pysdr_amd/csrc/host_plan.h) over rates, call lengths and tunings.  `san_main allocfail`
+// runs a short scenario over every object kind with the n-th allocation / event / stream creation failing, n = 1, 2, ...
 //   build + run: tests/host_san/run.sh   (tests/test_host_sanitizers.py does that)
 #include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/pysdr_hip.h"
+#include "host_plan.h"
 #include "mixdec_plan.h"
 
 #define OK(expr)                                                                                    \
@@ -330,6 +334,147 @@ static void planner_sweep() {
   std::printf("planner sweep: %d plans\n", nplans);
 }
 
+// plan_am_pll / plan_wfm_pll: what the segment kernels rely on, over the harness's rates, ragged call lengths up to
+// max_chunks * in_chunk, pysdr_set_pll_segments 0 / 1 / 7, the default tuning and the two tuning strings of run.sh
+static void check_pll_plan(const pysdr::PllPlan& p, int n, int pll_kmax, bool carrier, const char* what) {
+  const bool ok = p.K >= 1 && p.K <= pysdr::kPllSegMax && (long long)p.K * p.T >= n && p.T % 64 == 0 && p.W % 64 == 0 && p.Wfast % 64 == 0 &&
+                  p.Wexact % 64 == 0 && p.Wc_hi % 64 == 0 && p.Wc_mid % 64 == 0 && p.Wseed % 64 == 0 && p.Wexact <= p.W &&
+                  (!carrier || p.Wseed <= std::max(0, p.W - 64)) && (pll_kmax != 1 || p.K == 1);
+  if (!ok) {
+    std::fprintf(stderr, "%s plan for n %d, kmax %d: K %d T %d W %d Wfast %d Wexact %d Wc %d/%d Wseed %d\n", what, n, pll_kmax, p.K, p.T, p.W,
+                 p.Wfast, p.Wexact, p.Wc_hi, p.Wc_mid, p.Wseed);
+    std::exit(1);
+  }
+}
+struct ScopedEnv {             // a variable set for the lifetime of the object, then put back
+  std::string name, old; bool had;
+  ScopedEnv(const char* n, const char* v) : name(n) { const char* o = getenv(n); had = o != nullptr; if (o) old = o; setenv(n, v, 1); }
+  ~ScopedEnv() { if (had) setenv(name.c_str(), old.c_str(), 1); else unsetenv(name.c_str()); }
+};
+static void pll_plan_sweep() {
+  std::vector<pysdr::Tuning> tunings{pysdr::Tuning()};
+  {
+    ScopedEnv on("PYSDR_TUNING", "1"), wfm("PYSDR_WFM_PLL", "20,13,4,3,1536,2048,5,4,4,4"), am("PYSDR_AM_PLL", "14,4,4,1024,256");
+    tunings.push_back(pysdr::Tuning::from_env());
+    if (tunings[1].am_taus != 14.0 || tunings[1].am_tmin != 256 || tunings[1].wfm_tail_cap != 4) { std::fprintf(stderr, "tuning strings not parsed\n"); std::exit(1); }
+  }
+  std::vector<uint32_t> seg(1);          // (the plans only carry the pointer)
+  int nplans = 0;
+  for (const pysdr::Tuning& t : tunings)
+    for (const Rate& r : kRates)
+      for (int max_chunks : {1, 3, 64, 2048}) {
+        const long long L = r.in_chunk, cap = L * max_chunks;
+        int d1 = 1, up2 = 0, down2 = 0;
+        const double fs_out = std::floor(r.fs * r.up / r.down);
+        OK(pysdr_wfm_params(r.fs, fs_out, &d1, &up2, &down2));
+        for (long long n : {1LL, 17LL, L - 7, L, L + 11, cap / 2 + 1, cap - 5, cap}) {
+          if (n < 1 || n > cap) continue;
+          for (int kmax : {0, 1, 7}) {
+            const int n_out = (int)((n * r.up + r.down - 1) / r.down), n1 = (int)((n + d1 - 1) / d1);
+            check_pll_plan(pysdr::plan_am_pll(t, n_out, fs_out, kmax, seg.data()), n_out, kmax, true, "carrier-loop");
+            check_pll_plan(pysdr::plan_wfm_pll(t, n1, r.fs / d1, kmax, seg.data()), n1, kmax, false, "pilot-loop");
+            nplans += 2;
+          }
+        }
+      }
+  std::printf("pll plan sweep: %d plans\n", nplans);
+}
+
+// ---- `san_main allocfail`: the n-th hipMalloc / hipHostMalloc / event / stream creation of a run fails (fake_hip).  Every
+// step of the scenario that fails must leave a message, and must succeed when it is simply called again -- a half-built
+// object was destroyed by its create function, a half-added receiver slot is taken over by the next pysdr_rx_add, a
+// half-allocated lazy buffer set is completed by the next call -- and everything is destroyed at the end under
+// AddressSanitizer / LeakSanitizer.  (A malloc that returns an error in a CPU process: nothing here can run on a device.)
+static int g_failed_steps = 0;
+#define STEP(expr)                                                                                                      \
+  do {                                                                                                                  \
+    int rc_ = (expr);                                                                                                   \
+    if (rc_ != 0) {                                                                                                     \
+      if (!fake_hip::state().fail_hit) { std::fprintf(stderr, "%s:%d %s -> %d (%s) without an injected failure\n", __FILE__, __LINE__, #expr, rc_, pysdr_last_error()); std::exit(1); } \
+      if (!*pysdr_last_error()) { std::fprintf(stderr, "%s:%d %s -> %d without a message\n", __FILE__, __LINE__, #expr, rc_); std::exit(1); } \
+      ++g_failed_steps;                                                                                                 \
+      rc_ = (expr);                                                                                                     \
+      if (rc_ != 0) { std::fprintf(stderr, "%s:%d %s fails again after the injected failure -> %d (%s)\n", __FILE__, __LINE__, #expr, rc_, pysdr_last_error()); std::exit(1); } \
+    }                                                                                                                   \
+  } while (0)
+
+static void allocfail_scenario() {
+  const int ntaps = 255, L = 8192, max_chunks = 2;
+  const auto h = taps(ntaps), af = taps(2 * ntaps);
+  std::vector<float> x(2 * (size_t)max_chunks * L, 0.2f), am(4 * 4096), iq(4 * 4096);
+  int n_out = 0, cx = 0;
+  // narrow band, overlapped: AM-Synch (its loop walks on the second stream) beside NFM with the ratio squelch, then an ingest ring
+  pysdr_cfg cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.srate = 2.048e6; cfg.up = 3; cfg.down = 128; cfg.in_chunk = L; cfg.max_chunks = max_chunks; cfg.ntaps_dec = ntaps; cfg.ntaps_af = ntaps;
+  pysdr_ctx* c = nullptr;
+  STEP(pysdr_create(&cfg, &c));
+  STEP(pysdr_set_overlap(c, 1));
+  int irx = -1;
+  STEP(pysdr_rx_add(c, PYSDR_AM_SYNCH, 100e3, h.data(), af.data(), 0.0, &irx));
+  STEP(pysdr_rx_add(c, PYSDR_NFM, -50e3, h.data(), af.data(), 0.0, &irx));
+  if (irx != 1) { std::fprintf(stderr, "second receiver got slot %d\n", irx); std::exit(1); }
+  std::vector<float> lp(63, 1.0f / 63), hp(63, 0.f);
+  STEP(pysdr_set_squelch_ratio(c, 1, 2.0f, lp.data(), hp.data(), 63));
+  for (int k = 0; k < 3; ++k) STEP(pysdr_process_batch(c, x.data(), max_chunks, L, 0));
+  STEP(pysdr_fetch(c, 0, am.data(), iq.data(), 4096, &n_out, &cx, nullptr, nullptr));
+  pysdr_ingest* g = nullptr;
+  STEP(pysdr_ingest_create_batched(c, 2, 1, &g));
+  float* buf = nullptr;
+  size_t cap = 0;
+  STEP(pysdr_ingest_buffer(g, 0, &buf, &cap));
+  for (size_t i = 0; i < 2 * (size_t)L; ++i) buf[i] = 0.1f;
+  STEP(pysdr_ingest_submit(g, 0, L));
+  pysdr_out outs[2];
+  OK(pysdr_ingest_collect(g, 0, outs));
+  pysdr_ingest_destroy(g);
+  pysdr_destroy(c);
+  // broadcast FM stereo, overlapped: the lazily allocated IF buffers, resampler, seeds
+  int d1 = 0, up2 = 0, down2 = 0;
+  OK(pysdr_wfm_params(cfg.srate, 48000.0, &d1, &up2, &down2));
+  const auto res = taps(64 * up2);
+  c = nullptr;
+  STEP(pysdr_create(&cfg, &c));
+  STEP(pysdr_set_overlap(c, 1));
+  STEP(pysdr_rx_add(c, PYSDR_WFM2, 300e3, h.data(), af.data(), 0.0, &irx));
+  OK(pysdr_set_wfm_taps(c, 0, h.data(), ntaps, res.data(), 64 * up2));
+  for (int k = 0; k < 3; ++k) STEP(pysdr_process_batch(c, x.data(), max_chunks, L, 0));
+  STEP(pysdr_fetch(c, 0, am.data(), iq.data(), 4096, &n_out, &cx, nullptr, nullptr));
+  pysdr_destroy(c);
+  // a spectrum on both paths (PYSDR_PSD_GROUP=4 below: 8 frames are dealt out over the side streams)
+  std::vector<float> win(32768, 1.0f);
+  pysdr_spectrum* sp = nullptr;
+  void *d_x = nullptr, *d_o = nullptr;
+  STEP(pysdr_spectrum_create(0, 32768, 65536, 8, win.data(), &sp));
+  STEP(pysdr_dev_alloc(0, (size_t)8 * 32768 * 8, &d_x));
+  STEP(pysdr_dev_alloc(0, (size_t)8 * 65536 * 4, &d_o));
+  STEP(pysdr_spectrum_batch(sp, d_x, 8, 32768, d_o));
+  pysdr_spectrum_destroy(sp);
+  OK(pysdr_dev_free(0, d_x));
+  OK(pysdr_dev_free(0, d_o));
+  sp = nullptr;
+  std::vector<float> xin(2 * 4096, 0.1f), out(2 * 4096);
+  STEP(pysdr_spectrum_create(0, 4096, 8192, 2, win.data(), &sp));
+  STEP(pysdr_spectrum_frame(sp, xin.data(), 1, 1, out.data(), &n_out));
+  pysdr_spectrum_destroy(sp);
+}
+
+static void allocfail() {
+  ScopedEnv on("PYSDR_TUNING", "1"), grp("PYSDR_PSD_GROUP", "4");
+  for (long n = 1;; ++n) {
+    fake_hip::State& f = fake_hip::state();
+    f.creations = 0; f.fail_at = n; f.fail_hit = false;
+    g_failed_steps = 0;
+    allocfail_scenario();
+    if (!f.fail_hit) {           // the scenario has fewer than n creations: every one of them has failed once
+      f.fail_at = 0;
+      std::printf("HOST_SAN_ALLOCFAIL_OK: %ld injected failures\n", n - 1);
+      return;
+    }
+    if (g_failed_steps != 1) { std::fprintf(stderr, "creation %ld failed and %d steps reported it\n", n, g_failed_steps); std::exit(1); }
+  }
+}
+
 static void race() {
   // one thread processes chunks, another turns the knobs (receiver.py RX thread vs the Qt thread)
   const Rate r = kRates[2];
@@ -373,11 +518,16 @@ int main(int argc, char** argv) {
     std::puts("HOST_SAN_RACE_OK");
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "allocfail") == 0) {
+    allocfail();
+    return 0;
+  }
   int ndev = 0;
   OK(pysdr_device_count(&ndev));
   FAILS(pysdr_create(nullptr, nullptr));
   FAILS(pysdr_set_overlap(nullptr, 1));
   planner_sweep();
+  pll_plan_sweep();
   for (int pass = 0; pass < 3; ++pass) {
   g_overlap = pass == 0 ? 0 : (pass == 1 ? 2 : 1);
   for (const Rate& r : kRates) {

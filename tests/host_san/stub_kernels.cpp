@@ -7,10 +7,13 @@
 //     (pysdr_amd/csrc/mixdec_geom.h): the incremental step must equal the division, the LDS image must
 //     fit the tile buffer and stay inside history + call, outputs and owned samples must partition the
 //     call exactly.
+//   * with HOST_SAN_TRACE set (fake_hip/hip/hip_runtime.h) adds one line per launch to the queue trace: its name, stream and
+//     the scalars and buffers that define it.
 // No DSP is computed: parity is the GPU tests' business.  Not part of the product.
 #include <cassert>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <utility>
 
 #include "common.h"
@@ -42,6 +45,50 @@ template <class T> void read_all(const T* p, size_t n) {
 }
 template <class T> void write_all(T* p, size_t n) { std::memset(p, 0, n * sizeof(T)); }
 
+// ---- the queue trace
+using fake_hip::Line;
+std::string rk(const char* k, int r) { return std::string(k) + std::to_string(r); }
+void tr_plan(Line& l, const PllPlan& p) {
+  l.i("K", p.K).i("T", p.T).i("W", p.W).i("Wfast", p.Wfast).i("Wexact", p.Wexact).i("coarse", p.coarse_sweeps).i("Wc_hi", p.Wc_hi)
+      .i("Wc_mid", p.Wc_mid).i("seeded", p.seeded).i("Wseed", p.Wseed).i("direct", p.direct).i("tail_cap", p.tail_cap)
+      .i("exact_cap", p.exact_cap).p("seg", p.seg).p("lin", p.lin);
+}
+void tr_stage2(const char* what, const Stage2Args& a, hipStream_t st, const EpilogueArgs* e = nullptr) {
+  if (!fake_hip::tracing()) return;
+  Line l(what);
+  l.st(st).i("nrx", a.nrx).i("n_out", a.n_out).i("ntaps", a.ntaps).i("hy", a.hy).i("t0", a.t0).i("up", a.up).i("down", a.down)
+      .i("chunk_len", a.chunk_len).i("nchunks", a.nchunks).i("m0_lo", a.m0_lo).f("fm_scale", a.fm_scale).f("kp", a.pll_kp).f("ki", a.pll_ki)
+      .i("spread", a.single_spread).i("sq_ntaps", a.sq_ntaps).p("sqtaps", a.sqtaps).p("blknoise2", a.blknoise2).p("blknoise", a.blknoise)
+      .p("blkcnt", a.blkcnt).p("blkpeak", a.blkpeak).p("gain", a.gain).p("state", a.state);
+  for (int r = 0; r < a.nrx; ++r) {
+    l.p(rk("y", r).c_str(), a.y[r]).p(rk("ypll", r).c_str(), a.ypll[r]).p(rk("aftaps", r).c_str(), a.aftaps[r]).i(rk("real", r).c_str(), a.taps_real[r])
+        .p(rk("a", r).c_str(), a.a[r]).p(rk("am", r).c_str(), a.am[r]).i(rk("det", r).c_str(), a.det[r]).i(rk("cx", r).c_str(), a.out_complex[r])
+        .i(rk("fcx", r).c_str(), a.fir_complex[r]).i(rk("single", r).c_str(), a.single_block[r]).i(rk("matrix", r).c_str(), a.matrix[r])
+        .i(rk("bfo", r).c_str(), a.bfo_fword[r]).f(rk("sq", r).c_str(), a.sq_thresh[r]).i(rk("sqr", r).c_str(), a.sq_ratio[r]);
+    if (e) l.p(rk("ybase", r).c_str(), e->ybase[r]).p(rk("ydst", r).c_str(), e->ydst[r]).p(rk("ypllbase", r).c_str(), e->ypllbase[r])
+               .p(rk("yplldst", r).c_str(), e->yplldst[r]);
+  }
+  if (e) l.i("e_nrx", e->nrx).i("e_n_out", e->n_out).i("e_hy", e->hy);
+  tr_plan(l, a.pll);
+}
+void tr_wfm(const char* what, const WfmArgs& a, hipStream_t st) {
+  if (!fake_hip::tracing()) return;
+  Line l(what);
+  l.st(st).i("nrx", a.nrx).i("n1", a.n1).f("scale", a.scale).f("kp", a.kp).f("ki", a.ki).f("norm", a.norm).f("rad2word", a.rad2word)
+      .i("fword0", a.fword0).p("state", a.state).i("pass", a.pll_pass);
+  for (int r = 0; r < a.nrx; ++r)
+    l.p(rk("y1", r).c_str(), a.y1[r]).p(rk("y1base", r).c_str(), a.y1base[r]).p(rk("y1dst", r).c_str(), a.y1dst[r]).p(rk("w", r).c_str(), a.w[r])
+        .i(rk("stereo", r).c_str(), a.stereo[r]).p(rk("seed", r).c_str(), a.seed[r]).p(rk("mnT", r).c_str(), a.mnT[r]);
+  tr_plan(l, a.pll);
+}
+void tr_mixdec(const MixDecArgs& a, hipStream_t st, Line& l) {
+  l.st(st).i("n_total", a.n_total).i("n_out", a.n_out).i("t0", a.t0).i("up", a.up).i("down", a.down).i("kpad", a.kpad).i("nrx", a.nrx)
+      .i("hist_len", a.hist_len).i("aligned16", a.aligned16).i("tile_out", a.tile_out).i("tile_cap", a.tile_cap).i("ntiles", a.ntiles)
+      .i("yflush", a.yflush).i("taps_lds", a.taps_lds).i("chunk_len", a.chunk_len).i("zero_n", a.zero_n).i("dbg", a.dbg)
+      .p("x", a.x).p("hist", a.hist).p("hist_new", a.hist_new).p("taps", a.taps).p("peak", a.peak).p("zero", a.zero);
+  for (int r = 0; r < a.nrx; ++r) l.p(rk("y", r).c_str(), a.y[r]).i(rk("phase", r).c_str(), a.phase0[r]).i(rk("fword", r).c_str(), a.fword[r]);
+}
+
 bool same_tile(const Tile& a, const Tile& b) {
   return a.i_first == b.i_first && a.tile_n == b.tile_n && a.rel_f == b.rel_f && a.p_f == b.p_f && a.rel_l == b.rel_l &&
          a.lo == b.lo && a.hi == b.hi && a.own_lo == b.own_lo && a.own_hi == b.own_hi && a.npairs == b.npairs;
@@ -68,7 +115,12 @@ void check_mixdec_plan(const MixDecArgs& a, MdKey key, int threads) {
   SAN_CHECK(a.dq_tile == (int)(((long long)a.tile_out * a.down) / a.up) && a.dr_tile == (int)(((long long)a.tile_out * a.down) % a.up), "tile step");
 }
 
-int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStream_t) {
+int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStream_t st) {
+  if (fake_hip::tracing()) {
+    Line l("launch_mixdec");
+    tr_mixdec(a, st, l);
+    l.i("key_r", key.r).i("key_nj", key.nj).i("key_tpb", key.tpb).i("key_mm", key.mm).i("threads", threads).i("grid", grid);
+  }
   if (a.hist_new) roll_on_host(a.x, a.hist, a.hist_new, a.hist_len, a.n_total, a.zero, a.zero_n);
   check_mixdec_plan(a, key, threads);
   SAN_CHECK(grid >= 1, "grid %d", grid);
@@ -120,7 +172,12 @@ int resamp_small_span(int up, int down, int kpad) {
   return (int)span;
 }
 int g_small_launches = 0;
-int launch_resamp_small(const MixDecArgs& a, int, int, hipStream_t) {
+int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st) {
+  if (fake_hip::tracing()) {
+    Line l("launch_resamp_small");
+    tr_mixdec(a, st, l);
+    l.i("grid_cap", grid_cap).i("plain", plain);
+  }
   ++g_small_launches;
   if (a.hist_new && a.n_out > 0) roll_on_host(a.x, a.hist, a.hist_new, a.hist_len, a.n_total, a.zero, a.zero_n);   // the real launcher starts no kernel without outputs
   const int span = resamp_small_span(a.up, a.down, a.kpad);
@@ -241,7 +298,12 @@ bool mixdec_mfma_plan(int shape, unsigned long long s0, unsigned long long m0, u
   return false;
 }
 int g_mfma_launches = 0;
-int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t) {
+int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_mixdec_mfma").st(st).i("shape", shape).i("grid", grid).i("n_total", a.n_total).i("n_out", a.n_out).i("hist_len", a.hist_len)
+        .i("origin_rel0", a.origin_rel0).i("d", a.d).i("nrel0", a.nrel0).i("mrel0", a.mrel0).i("ntiles", a.ntiles).i("kpad", a.kpad)
+        .i("phase", a.phase0).i("fword", a.fword).i("chunk_len", a.chunk_len).i("zero_n", a.zero_n).p("x", a.x).p("hist", a.hist)
+        .p("hist_new", a.hist_new).p("taps", a.taps).p("y", a.y).p("peak", a.peak).p("zero", a.zero);
   ++g_mfma_launches;
   if (a.hist_new) roll_on_host(a.x, a.hist, a.hist_new, a.hist_len, a.n_total, a.zero, a.zero_n);
 #define PYSDR_MFMA_LAUNCH(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
@@ -252,7 +314,10 @@ int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t) {
   return PYSDR_ERR_ARG;
 }
 
-int launch_hist_roll(const float2* x, const float2* hist_old, float2* hist_new, int hist_len, uint32_t n_total, unsigned* zero, int zero_n, hipStream_t) {
+int launch_hist_roll(const float2* x, const float2* hist_old, float2* hist_new, int hist_len, uint32_t n_total, unsigned* zero, int zero_n, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_hist_roll").st(st).i("hist_len", hist_len).i("n_total", n_total).i("zero_n", zero_n).p("x", x).p("hist", hist_old)
+        .p("hist_new", hist_new).p("zero", zero);
   roll_on_host(x, hist_old, hist_new, hist_len, n_total, zero, zero_n);
   return PYSDR_OK;
 }
@@ -264,7 +329,8 @@ static void check_plan(const PllPlan& p, int n, int nrx) {
   write_all(p.seg, (size_t)nrx * p.K * 4);
 }
 
-int launch_am_phase(const Stage2Args& a, hipStream_t) {
+int launch_am_phase(const Stage2Args& a, hipStream_t st) {
+  tr_stage2("launch_am_phase", a, st);
   for (int r = 0; r < a.nrx; ++r)
     if (a.det[r] == kDetPll) {
       SAN_CHECK(a.ypll[r] != nullptr, "AM-Synch rx %d has no PLL buffer", r);
@@ -274,7 +340,8 @@ int launch_am_phase(const Stage2Args& a, hipStream_t) {
   return PYSDR_OK;
 }
 
-int launch_pll(const Stage2Args& a, hipStream_t) {
+int launch_pll(const Stage2Args& a, hipStream_t st) {
+  tr_stage2("launch_pll", a, st);
   check_plan(a.pll, a.n_out, a.nrx);
   for (int r = 0; r < a.nrx; ++r)
     if (a.det[r] == kDetPll) {
@@ -296,7 +363,8 @@ int launch_pll(const Stage2Args& a, hipStream_t) {
   return PYSDR_OK;
 }
 
-int launch_demod_fir(const Stage2Args& a, hipStream_t) {
+int launch_demod_fir(const Stage2Args& a, hipStream_t st) {
+  tr_stage2("launch_demod_fir", a, st);
   for (int r = 0; r < a.nrx; ++r) {
     const float2* src = (a.det[r] == kDetPll) ? a.ypll[r] : a.y[r];
     read_all(src - a.hy, (size_t)a.hy + a.n_out);                  // history prefix + the call
@@ -318,7 +386,8 @@ int launch_demod_fir(const Stage2Args& a, hipStream_t) {
 }
 
 static int stub_epilogue(const EpilogueArgs& a);
-int launch_agc_scan(const Stage2Args& a, const EpilogueArgs& e, hipStream_t) {
+int launch_agc_scan(const Stage2Args& a, const EpilogueArgs& e, hipStream_t st) {
+  tr_stage2("launch_agc_scan", a, st, &e);
   for (int r = 0; r < a.nrx; ++r) {
     for (int k = 0; k < a.nchunks; ++k) g_sink = (float)a.blkpeak[((size_t)r * a.nchunks + k) * kBlkStride];
     write_all(a.gain + (size_t)r * a.nchunks, (size_t)a.nchunks);
@@ -327,7 +396,8 @@ int launch_agc_scan(const Stage2Args& a, const EpilogueArgs& e, hipStream_t) {
   return stub_epilogue(e);
 }
 
-int launch_apply(const Stage2Args& a, hipStream_t) {
+int launch_apply(const Stage2Args& a, hipStream_t st) {
+  tr_stage2("launch_apply", a, st);
   for (int r = 0; r < a.nrx; ++r) {
     read_all(a.a[r], (size_t)a.n_out);
     write_all(a.am[r], (size_t)a.n_out * (a.out_complex[r] ? 2 : 1));
@@ -350,7 +420,8 @@ static int stub_epilogue(const EpilogueArgs& a) {
   return PYSDR_OK;
 }
 
-int launch_wfm_disc(const WfmArgs& a, hipStream_t) {
+int launch_wfm_disc(const WfmArgs& a, hipStream_t st) {
+  tr_wfm("launch_wfm_disc", a, st);
   for (int r = 0; r < a.nrx; ++r) {
     SAN_CHECK(a.y1[r] == a.y1base[r] + 2, "IF buffer layout");
     read_all(a.y1[r] - 1, (size_t)a.n1 + 1);
@@ -386,6 +457,7 @@ bool wfm_any_stereo(const WfmArgs& a) {
 }
 
 int launch_wfm_pll(const WfmArgs& a, hipStream_t st) {
+  tr_wfm("launch_wfm_pll", a, st);
   check_plan(a.pll, a.n1, a.nrx);
   if (a.pll.seeded && a.pll.K > 1) { const int rc = launch_wfm_seed(a, st); if (rc) return rc; }
   for (int r = 0; r < a.nrx; ++r)
@@ -394,13 +466,15 @@ int launch_wfm_pll(const WfmArgs& a, hipStream_t st) {
   return PYSDR_OK;
 }
 
-int launch_quad_mixer(const float2* x, float2* y, size_t n, uint32_t, uint32_t, hipStream_t) {
+int launch_quad_mixer(const float2* x, float2* y, size_t n, uint32_t phase0, uint32_t fword, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_quad_mixer").st(st).i("n", (long long)n).i("phase", phase0).i("fword", fword).p("x", x).p("y", y);
   read_all(x, n);
   write_all(y, n);
   return PYSDR_OK;
 }
 
-int launch_fir_real(const float* xx, const float* h, int nt, float* y, int n, hipStream_t) {
+int launch_fir_real(const float* xx, const float* h, int nt, float* y, int n, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_fir_real").st(st).i("nt", nt).i("n", n).p("x", xx).p("h", h).p("y", y);
   read_all(xx, (size_t)n + nt - 1);
   read_all(h, (size_t)nt);
   write_all(y, (size_t)n);
@@ -408,7 +482,10 @@ int launch_fir_real(const float* xx, const float* h, int nt, float* y, int n, hi
 }
 
 int launch_psd_pre(const float2* x, size_t hop, int nframes, int chunk, int nfft, const float* win, float2* work, int is_complex,
-                   hipStream_t) {
+                   hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_psd_pre").st(st).i("hop", (long long)hop).i("nframes", nframes).i("chunk", chunk).i("nfft", nfft).i("complex", is_complex)
+        .p("x", x).p("win", win).p("work", work);
   read_all(win, (size_t)chunk);
   for (int f = 0; f < nframes; ++f) {
     if (is_complex) read_all(x + (size_t)f * hop, (size_t)chunk);
@@ -418,13 +495,18 @@ int launch_psd_pre(const float2* x, size_t hop, int nframes, int chunk, int nfft
   return PYSDR_OK;
 }
 
-int launch_psd_post(const float2* work, int nframes, int nfft, int half, int, float* out, hipStream_t) {
+int launch_psd_post(const float2* work, int nframes, int nfft, int half, int db, float* out, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_psd_post").st(st).i("nframes", nframes).i("nfft", nfft).i("half", half).i("db", db).p("work", work).p("out", out);
   read_all(work, (size_t)nframes * nfft);
   write_all(out, (size_t)nframes * (half ? nfft / 2 : nfft));
   return PYSDR_OK;
 }
 
-int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work, float* out, int, hipStream_t, int) {
+int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work, float* out, int db, hipStream_t st, int packed) {
+  if (fake_hip::tracing())
+    Line("launch_psd64k").st(st).i("hop", (long long)hop).i("nframes", nframes).i("db", db).i("packed", packed).p("x", x).p("win", win)
+        .p("work", work).p("out", out);
   read_all(win, 32768);
   for (int f = 0; f < nframes; ++f) read_all(x + (size_t)f * hop, 32768);
   write_all(work, (size_t)nframes * 65536);

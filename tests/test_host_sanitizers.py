@@ -35,6 +35,8 @@ def test_host_half_and_mixdec_plans_under_address_and_ub_sanitizers(tmp_path):
     out = _run("asan", tmp_path)
     assert "HOST_SAN_OK" in out and "HOST_SAN_RACE_OK" in out
     assert "planner sweep: 1920 plans" in out
+    assert "pll plan sweep:" in out
+    assert "HOST_SAN_ALLOCFAIL_OK" in out
 
 
 def test_setters_against_process_under_thread_sanitizer_over_the_shared_plan(tmp_path):
