@@ -197,6 +197,29 @@ int pysdr_set_tile(pysdr_ctx* ctx, int tile_bytes, int threads);
  * long single-RX prototypes on the matrix cores 0/1}. */
 int pysdr_get_tuning(pysdr_ctx* ctx, int32_t out[8]);
 
+/* ---- the front end's decision, without a device ----------------------------------
+ * Which form of the mix + decimate front end a decimator of this shape runs on, and with what plan.  Pure
+ * arithmetic: needs no device and no context, and is the helper every launch takes its decision from, so what
+ * it reports is what a context with this tuning runs.  nrx sub-receivers share a decimator UP/DOWN with an
+ * ntaps-tap prototype; tile_bytes, threads, wgs_per_cu, yflush_cap, mfma_enable as pysdr_get_tuning reports them
+ * (defaults 0, 1024, 1, 0, 1); want_peak = the raw chunk peak is wanted (1 for a context's main decimator).
+ * out = {form, fits (0: the vector plan does not fit the LDS -- such a call is refused),
+ *        R, NJ, TPB, MM of the vector instantiation mixdec_kernel<R, NJ, TPB, 0, MM>,
+ *        matrix-core shape id (-1 unless form = PYSDR_FORM_MFMA),
+ *        taps_lds (1: taps staged in LDS, 0: held in registers), tile_out (outputs per tile),
+ *        yflush (tiles per flush of the output stage), tile_cap (samples per LDS tile buffer),
+ *        kpad (taps per polyphase branch, padded to 16)}.
+ * With PYSDR_FORM_MFMA the vector fields (R .. tile_cap) are 0: that form has a fixed geometry per shape. */
+#define PYSDR_FORM_VECTOR 0 /* mixdec_kernel: any number of sub-receivers */
+#define PYSDR_FORM_MFMA 1   /* one sub-receiver, long prototype, on the matrix cores */
+#define PYSDR_FORM_SMALL 2  /* one sub-receiver, short prototype, small DOWN/UP, no raw peak */
+int pysdr_front_end_plan(int nrx, int up, int down, int ntaps, int tile_bytes, int threads, int wgs_per_cu,
+                         int yflush_cap, int mfma_enable, int want_peak, int32_t out[12]);
+/* What is compiled.  family = PYSDR_FORM_VECTOR: entry `index` = {R, NJ, TPB, MM}; PYSDR_FORM_MFMA: {shape id, UP,
+ * DOWN, taps per polyphase branch}.  *count (if not null) = entries of the family; index outside 0 .. count-1 with a
+ * null `out` only counts. */
+int pysdr_front_end_shapes(int family, int index, int32_t out[4], int* count);
+
 /* ---- signal_generator.quad_mixer (receiver.py:552-553,822) --------------------
  * y = x * exp(+j*phi_n), 32-bit phase accumulator, returns phase after n samples */
 int pysdr_quad_mixer(int device, const float* x, float* y, size_t n, uint32_t phase0,

@@ -344,11 +344,21 @@ int decim_run(pysdr_ctx* c, Decim& d, const float2* d_x, size_t n, int nrx, floa
   const int n_out = (int)(m1 - m0);
   if (n_out > y_cap) { set_last_error("decimator: n_out %d > capacity %d", n_out, y_cap); return PYSDR_ERR_STATE; }
   if ((double)n * up + down >= 2147483647.0) { set_last_error("decimator: call too long for 31-bit indices"); return PYSDR_ERR_ARG; }
-  // One RX with a long prototype at a rate that has an instantiation: the matrix-core form (mixdec_mfma.hip).  The
-  // choice depends on the decimator's shape only -- never on the call -- so every call of a stream sums in the
-  // same order (batch == chunk by chunk bit for bit), whatever the alignment of the caller's device pointer (the
-  // LDS-DMA takes any 4-byte aligned source: scripts/diag/glds_align_test.hip).
-  const int mshape = (nrx == 1 && c->tune.mfma_enable) ? mixdec_mfma_shape(up, down, d.kdec) : -1;
+  // Which form runs -- the matrix-core one (one RX, a long prototype at a rate that has an instantiation), the small resampler
+  // (one RX, no raw peak wanted, short prototype and a small DOWN/UP: the fs1 -> FS_OUT stage of broadcast FM) or the vector
+  // kernel with its plan -- is plan_front_end's decision (mixdec_plan.h; pysdr_front_end_plan reports the same).  It depends
+  // on the decimator's shape and its call site only -- never on the call -- so every call of a stream sums in the same order
+  // (batch == chunk by chunk bit for bit), whatever the alignment of the caller's device pointer (the LDS-DMA takes any
+  // 4-byte aligned source: scripts/diag/glds_align_test.hip).
+  MixDecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n_out = n_out;
+  a.up = up; a.down = down;
+  a.kpad = d.kpad;
+  a.nrx = nrx;
+  const FrontEndPlan fe = plan_front_end(a, d.kdec, peak != nullptr, c->tune.tile_bytes, c->tune.threads, c->tune.wgs_per_cu,
+                                         c->tune.yflush_cap, c->tune.mfma_enable);
+  const int mshape = fe.mshape;
   MfmaPlan plan;
   if (mshape >= 0 && !mixdec_mfma_plan(mshape, s0, m0, n, &plan)) {
     // (falling through to the vector form here would sum THIS call in another order than its neighbours: an error instead)
@@ -390,27 +400,19 @@ int decim_run(pysdr_ctx* c, Decim& d, const float2* d_x, size_t n, int nrx, floa
     if (res) { res->n_out = n_out; res->t0 = (uint32_t)(m0 * down - s0 * up); res->m0 = m0; }
     return PYSDR_OK;
   }
-  // one RX, no raw peak wanted, short prototype and a small DOWN/UP (the fs1 -> FS_OUT stage of broadcast FM): one thread
-  // per output (resamp_small.hip).  Decided by the decimator's shape and its call site only, never by the call.
-  const bool small = (nrx == 1 && !peak && resamp_small_span(up, down, d.kpad) > 0);
-  MixDecArgs a;
-  memset(&a, 0, sizeof(a));
+  const bool small = fe.form == PYSDR_FORM_SMALL;      // one thread per output (resamp_small.hip)
+  const MdKey key = fe.key;
+  if (!fe.fits) {
+    set_last_error("decimator: filter (%d taps, %d rx, up %d) does not fit LDS", d.ntaps, nrx, up);
+    return PYSDR_ERR_ARG;
+  }
   a.x = d_x;
   a.hist = d.d_hist.buf(d.hist_cur);
   a.hist_len = d.hist_len;
   a.aligned16 = ((reinterpret_cast<uintptr_t>(d_x) & 15u) == 0) ? 1 : 0;
   a.n_total = (uint32_t)n;
   a.t0 = (uint32_t)(m0 * down - s0 * up);
-  a.n_out = n_out;
-  a.up = up; a.down = down;
-  a.kpad = d.kpad;
   a.magic = (up == 1) ? 0u : (uint32_t)(4294967296ULL / (unsigned)up) + 1u;
-  a.nrx = nrx;
-  MdKey key;
-  if (!plan_mixdec(a, c->tune.tile_bytes, c->tune.threads, c->tune.wgs_per_cu, c->tune.yflush_cap, key)) {
-    set_last_error("decimator: filter (%d taps, %d rx, up %d) does not fit LDS", d.ntaps, nrx, up);
-    return PYSDR_ERR_ARG;
-  }
   a.taps = d.d_taps.get();
   for (int r = 0; r < nrx; ++r) { a.y[r] = y[r]; a.phase0[r] = phase0[r]; a.fword[r] = fword[r]; }
   a.peak = peak ? peak : c->d_peak_scratch.get();
@@ -1048,6 +1050,47 @@ int pysdr_set_tile(pysdr_ctx* c, int tile_bytes, int threads) {
     return PYSDR_ERR_ARG;
   c->tune.tile_bytes = tile_bytes;
   c->tune.threads = threads;
+  return PYSDR_OK;
+}
+
+int pysdr_front_end_plan(int nrx, int up, int down, int ntaps, int tile_bytes, int threads, int wgs_per_cu, int yflush_cap,
+                         int mfma_enable, int want_peak, int32_t out[12]) {
+  if (!out || nrx < 1 || nrx > PYSDR_MAX_RX || up < 1 || down < 1 || ntaps < 1 || wgs_per_cu < 1 || yflush_cap < 0 ||
+      (tile_bytes != 0 && (tile_bytes < 4096 || tile_bytes > 150 * 1024)) || threads < 64 || threads > 1024 || (threads & 63))
+    return PYSDR_ERR_ARG;
+  // the shape as decim_init derives it, the decision as decim_run takes it
+  const int kdec = (ntaps + up - 1) / up;
+  MixDecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.nrx = nrx; a.up = up; a.down = down;
+  a.kpad = (kdec + 15) / 16 * 16;
+  const FrontEndPlan fe = plan_front_end(a, kdec, want_peak != 0, tile_bytes, threads, wgs_per_cu, yflush_cap, mfma_enable);
+  const bool vec = fe.form != PYSDR_FORM_MFMA;
+  out[0] = fe.form; out[1] = fe.fits ? 1 : 0;
+  out[2] = vec ? fe.key.r : 0; out[3] = vec ? fe.key.nj : 0; out[4] = vec ? fe.key.tpb : 0; out[5] = vec ? fe.key.mm : 0;
+  out[6] = fe.mshape;
+  out[7] = a.taps_lds; out[8] = a.tile_out; out[9] = a.yflush; out[10] = a.tile_cap; out[11] = a.kpad;
+  return PYSDR_OK;
+}
+
+int pysdr_front_end_shapes(int family, int index, int32_t out[4], int* count) {
+  static const int32_t vec[][4] = {
+#define PYSDR_SHAPE_ROW(R, NJ, TPB, MM) {R, NJ, TPB, MM},
+      PYSDR_MIXDEC_SHAPES(PYSDR_SHAPE_ROW)
+#undef PYSDR_SHAPE_ROW
+  };
+  static const int32_t mm[][4] = {
+#define PYSDR_SHAPE_ROW(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) {ID, UP, DOWN, KT},
+      PYSDR_MFMA_SHAPES(PYSDR_SHAPE_ROW)
+#undef PYSDR_SHAPE_ROW
+  };
+  if (family != PYSDR_FORM_VECTOR && family != PYSDR_FORM_MFMA) return PYSDR_ERR_ARG;
+  const int32_t (*tab)[4] = family == PYSDR_FORM_VECTOR ? vec : mm;
+  const int n = family == PYSDR_FORM_VECTOR ? (int)(sizeof(vec) / sizeof(vec[0])) : (int)(sizeof(mm) / sizeof(mm[0]));
+  if (count) *count = n;
+  if (index < 0 || index >= n) return (out == nullptr && count != nullptr) ? PYSDR_OK : PYSDR_ERR_ARG;
+  if (!out) return PYSDR_ERR_ARG;
+  for (int j = 0; j < 4; ++j) out[j] = tab[index][j];
   return PYSDR_OK;
 }
 

@@ -84,7 +84,15 @@ struct MixDecArgs {
 // the plan and the launch of the mix + decimate kernel: mixdec_plan.h
 
 // one RX, short prototype, small DOWN/UP, no raw peak (resamp_small.hip): the fs1 -> FS_OUT stage of broadcast FM
-int resamp_small_span(int up, int down, int kpad);   // LDS samples a workgroup stages; 0 = shape not eligible
+constexpr int kRsThreads = 256;                      // threads = outputs per workgroup of its one-output-per-thread form
+// span of input samples kRsThreads consecutive outputs need (+ the filter): what the launch reserves in LDS; 0 = shape not
+// eligible.  Plain arithmetic, here and not in resamp_small.hip: the front end's decision (plan_front_end, mixdec_plan.h) needs it
+inline int resamp_small_span(int up, int down, int kpad) {
+  const long span = ((long)kRsThreads * down + up - 1) / up + kpad + 4;
+  const long bytes = (span + (long)up * (kpad + 1)) * (long)sizeof(float2);
+  if (span > 4096 || bytes > 60 * 1024) return 0;
+  return (int)span;
+}
 int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st);   // grid_cap > 0: at most that many workgroups (tests); plain: 0 = wave per branch with scalar taps, 1 = one output per thread, 2 = half-wave per branch (A/B)
 
 // ---- mix + decimate on the matrix cores, one RX with a long prototype (mixdec_mfma.hip) ----
@@ -156,7 +164,14 @@ struct MixMfmaArgs {
   X(4, 3, 112, 2, 334, 1, 8, 8, 4, 1 | MM_NTX) \
   X(5, 1, 32, 8, 1001, 1, 8, 4, 3, 0 | MM_NTX) \
   X(6, 1, 40, 6, 1001, 1, 8, 4, 3, 0 | MM_NTX)
-int mixdec_mfma_shape(int up, int down, int kdec);   // -1: none
+// which (UP, DOWN, taps per branch) have an instantiation; -1: none
+inline int mixdec_mfma_shape(int up, int down, int kdec) {
+#define PYSDR_MFMA_MATCH(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
+  if (up == UP && down == DOWN && kdec == KT) return ID;
+  PYSDR_MFMA_SHAPES(PYSDR_MFMA_MATCH)
+#undef PYSDR_MFMA_MATCH
+  return -1;
+}
 bool mixdec_mfma_plan(int shape, unsigned long long s0, unsigned long long m0, unsigned long long n, MfmaPlan* p);
 int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t st);
 

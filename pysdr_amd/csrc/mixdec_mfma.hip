@@ -641,15 +641,6 @@ int launch_g(const MixMfmaArgs& a, int grid, hipStream_t st) {
 
 }  // namespace
 
-// Which (UP, DOWN, taps per branch) have an instantiation: PYSDR_MFMA_SHAPES in common.h
-int mixdec_mfma_shape(int up, int down, int kdec) {
-#define PYSDR_MFMA_MATCH(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
-  if (up == UP && down == DOWN && kdec == KT) return ID;
-  PYSDR_MFMA_SHAPES(PYSDR_MFMA_MATCH)
-#undef PYSDR_MFMA_MATCH
-  return -1;
-}
-
 bool mixdec_mfma_plan(int shape, unsigned long long s0, unsigned long long m0, unsigned long long n, MfmaPlan* p) {
 #define PYSDR_MFMA_PLAN(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
   if (shape == ID) return mfma_plan<MfmaGeo<UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY>>(s0, m0, n, p);

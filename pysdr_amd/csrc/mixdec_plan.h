@@ -159,6 +159,28 @@ inline bool plan_mixdec(MixDecArgs& a, int tile_bytes, int threads_req, int wgs_
   return true;
 }
 
+// The front end's whole decision for one decimator: which of its three forms runs, and for the vector form the plan above.
+// A function of the decimator's shape, its call site (raw peak wanted or not) and the context's tuning only -- never of the
+// call.  decim_run (api.hip) launches what this says and pysdr_front_end_plan reports it: one helper, so the two cannot drift.
+struct FrontEndPlan {
+  int form;      // PYSDR_FORM_VECTOR / _MFMA / _SMALL
+  int mshape;    // _MFMA: the id in PYSDR_MFMA_SHAPES; -1 otherwise
+  MdKey key;     // _VECTOR: the instantiation of PYSDR_MIXDEC_SHAPES
+  bool fits;     // false: the vector plan does not fit the LDS (decim_run refuses the call; the small resampler needs it too)
+};
+// `a` holds the shape (nrx, up, down, kpad, n_out) and receives the vector plan unless the matrix-core form takes the shape.
+inline FrontEndPlan plan_front_end(MixDecArgs& a, int kdec, bool want_peak, int tile_bytes, int threads_req, int wgs_per_cu,
+                                   int yflush_cap, int mfma_enable) {
+  FrontEndPlan f{PYSDR_FORM_VECTOR, -1, MdKey{a.nrx, 0, 1024, 0}, true};
+  // one RX with a long prototype at a rate that has an instantiation: the matrix-core form (mixdec_mfma.hip)
+  f.mshape = (a.nrx == 1 && mfma_enable) ? mixdec_mfma_shape(a.up, a.down, kdec) : -1;
+  if (f.mshape >= 0) { f.form = PYSDR_FORM_MFMA; return f; }
+  // one RX, no raw peak wanted, short prototype and a small DOWN/UP (the fs1 -> FS_OUT stage of broadcast FM): resamp_small.hip
+  if (a.nrx == 1 && !want_peak && resamp_small_span(a.up, a.down, a.kpad) > 0) f.form = PYSDR_FORM_SMALL;
+  f.fits = plan_mixdec(a, tile_bytes, threads_req, wgs_per_cu, yflush_cap, f.key);
+  return f;
+}
+
 // launch the plan's instantiation (PYSDR_ERR_ARG for a key that is not in PYSDR_MIXDEC_SHAPES)
 int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStream_t st);
 

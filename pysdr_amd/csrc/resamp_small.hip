@@ -19,8 +19,7 @@ namespace pysdr {
 
 namespace {
 
-constexpr int kRsThreads = 256;
-
+// (kRsThreads = 256 and resamp_small_span: common.h)
 __global__ __launch_bounds__(kRsThreads) void resamp_small_kernel(const MixDecArgs a, int span_cap, int ngroups) {
   extern __shared__ __attribute__((aligned(16))) float2 rs_lds[];
   float2* const xs = rs_lds;                       // [span_cap] input span of one group of 256 outputs
@@ -277,14 +276,6 @@ static size_t resamp_branch_lds(int up, int down, int kpad, int* span_out) {
   if (bytes > 64 * 1024 || span > (long)kRbPre * up * kRbL) return 0;
   *span_out = (int)span;
   return bytes;
-}
-
-// span of input samples 256 consecutive outputs need (+ the filter): what the launch reserves in LDS; 0 = not eligible
-int resamp_small_span(int up, int down, int kpad) {
-  const long span = ((long)kRsThreads * down + up - 1) / up + kpad + 4;
-  const long bytes = (span + (long)up * (kpad + 1)) * (long)sizeof(float2);
-  if (span > 4096 || bytes > 60 * 1024) return 0;
-  return (int)span;
 }
 
 int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st) {

@@ -165,12 +165,6 @@ int launch_mixdec(const MixDecArgs& a, MdKey key, int threads, int grid, hipStre
 }
 
 // ---- the short-prototype resampler (resamp_small.hip): every workgroup's input span fits what the launch reserves
-int resamp_small_span(int up, int down, int kpad) {
-  const long span = (256L * down + up - 1) / up + kpad + 4;
-  const long bytes = (span + (long)up * (kpad + 1)) * (long)sizeof(float2);
-  if (span > 4096 || bytes > 60 * 1024) return 0;
-  return (int)span;
-}
 int g_small_launches = 0;
 int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st) {
   if (fake_hip::tracing()) {
@@ -283,13 +277,6 @@ static void roll_on_host(const float2* x, const float2* hist_old, float2* hist_n
   }
 }
 
-int mixdec_mfma_shape(int up, int down, int kdec) {
-#define PYSDR_MFMA_MATCH(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
-  if (up == UP && down == DOWN && kdec == KT) return ID;
-  PYSDR_MFMA_SHAPES(PYSDR_MFMA_MATCH)
-#undef PYSDR_MFMA_MATCH
-  return -1;
-}
 bool mixdec_mfma_plan(int shape, unsigned long long s0, unsigned long long m0, unsigned long long n, MfmaPlan* p) {
 #define PYSDR_MFMA_PLAN(ID, UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY) \
   if (shape == ID) return mfma_plan<MfmaGeo<UP, DOWN, S, KT, NB, WK, NP, NBUF, CARRY>>(s0, m0, n, p);

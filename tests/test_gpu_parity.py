@@ -516,16 +516,13 @@ def test_device_resident_batch_and_untouched_input():
     _lib.check(lib.pysdr_dev_free(0, d), "free")
 
 
-@pytest.mark.parametrize("name", ["C1", "C2"])
-def test_device_batch_at_an_odd_sample_offset(name):
-    """A device-resident batch that starts at an ODD sample of its buffer is only 8-byte aligned.  The LDS-DMA of both
-    mix + decimate kernels takes such a source (scripts/diag/glds_align_test.hip: any 4-byte aligned address; the
-    matrix-core form relies on it, the vector form falls back to its generic staging): same bits as the same samples from
-    a 16-byte aligned buffer, and the oracle's values."""
+def check_device_batch_at_an_odd_sample_offset(cfg, x, B, want_iq=None):
+    """``x``: B chunks + 1 samples; the batch is x[1:].  Every sub-receiver: the device-resident batch that starts at sample 1 of
+    the uploaded buffer == the same samples staged from an aligned host array, bit for bit (audio, baseband IQ, chunk counts, raw
+    peaks), and the baseband IQ is the oracle's (``want_iq[i]``: a reference of the caller's for x[1:], else the float32 oracle)."""
     from pysdr_amd import _lib
-    cfg = so.CONFIGS[name]
-    L, B = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3], 6
-    x = so.synth_iq(cfg, B * L + 1, 21)
+    L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
+    assert len(x) == B * L + 1
     lib = _lib.lib()
     d = C.c_void_p()
     _lib.check(lib.pysdr_dev_alloc(0, x.nbytes, C.byref(d)), "alloc")
@@ -533,17 +530,34 @@ def test_device_batch_at_an_odd_sample_offset(name):
         _lib.check(lib.pysdr_dev_upload(0, d, C.c_void_p(x.ctypes.data), x.nbytes), "upload")
         P1, g1 = make_gpu_receivers(cfg, max_batch_chunks=B)
         P1._pysdr_stream.process_batch(d.value + 8, B, L, on_device=True)          # samples 1 .. B*L of the buffer
-        odd = P1._pysdr_stream.fetch(0, B)
+        odd = [P1._pysdr_stream.fetch(i, B) for i in range(len(g1))]
         P2, g2 = make_gpu_receivers(cfg, max_batch_chunks=B)
         P2._pysdr_stream.process_batch(np.ascontiguousarray(x[1:]), B, L, on_device=False)   # staged: 16-byte aligned
-        even = P2._pysdr_stream.fetch(0, B)
+        even = [P2._pysdr_stream.fetch(i, B) for i in range(len(g2))]
     finally:
         lib.pysdr_dev_free(0, d)
-    for u, v in zip(odd, even):
-        assert np.array_equal(u, v)
-    o = so.make_receivers(cfg, np.float32)[0]
-    want = np.concatenate([(o.demod_data(x[1 + k * L:1 + (k + 1) * L]), o.iq.copy())[1] for k in range(B)])
-    assert relerr(odd[1], want) <= TOL          # the baseband IQ (the stage under test; the NFM audio's start-up has its own allowance)
+    worst = 0.0
+    for i, (o_i, e_i) in enumerate(zip(odd, even)):
+        for u, v in zip(o_i, e_i):
+            assert np.array_equal(u, v), i
+    for i, o in enumerate(so.make_receivers(cfg, np.float32) if want_iq is None else want_iq):
+        want = o if want_iq is not None else \
+            np.concatenate([(o.demod_data(x[1 + k * L:1 + (k + 1) * L]), o.iq.copy())[1] for k in range(B)])
+        e = relerr(odd[i][1], want)
+        worst = max(worst, e)
+        assert e <= TOL, (i, e)     # the baseband IQ (the stage under test; the NFM audio's start-up has its own allowance)
+    return P1, worst
+
+
+@pytest.mark.parametrize("name", ["C1", "C2"])
+def test_device_batch_at_an_odd_sample_offset(name):
+    """A device-resident batch that starts at an ODD sample of its buffer is only 8-byte aligned.  The LDS-DMA of both
+    mix + decimate kernels takes such a source (scripts/diag/glds_align_test.hip: any 4-byte aligned address; the
+    matrix-core form relies on it, the vector form falls back to its generic staging): same bits as the same samples from
+    a 16-byte aligned buffer, and the oracle's values.  (Every instantiation: tests/test_gpu_front_end_sweep.py.)"""
+    cfg = so.CONFIGS[name]
+    L, B = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3], 6
+    check_device_batch_at_an_odd_sample_offset(cfg, so.synth_iq(cfg, B * L + 1, 21), B)
 
 
 @pytest.mark.parametrize("name", ["FT8TRI", "TEST2RX"])
@@ -566,27 +580,13 @@ def test_multi_rx_1001_taps_with_tiles_too_small_to_hold_the_taps(name):
     run_both(cfg, [L, L, 1000, 7, L - 13, 2 * L + 5, 333], seed=43, tile=(12288, 1024))
 
 
-@pytest.mark.parametrize("grid", [0, 3])
-@pytest.mark.parametrize("name,nrx", [("FT8TRI", 3), ("TEST2RX", 2), ("FT8TRI", 2), ("C3", 4), ("C3", 6), ("C3", 5), ("RTL", 2)])
-def test_multi_rx_long_prototype_does_not_depend_on_the_cut(name, nrx, grid, monkeypatch):
-    """The tap-holding shapes of the vector mix + decimate kernel (mixdec.hip, 768 threads: 2 - 6 sub-receivers, 1001 taps at
-    UP = 3; 4, 5 and 6 RX on C3's stream re-run with the long prototype; 3/500, 3/250 and 3/128): chunk by chunk == one batch == cut at random
-    places, bit for bit, for every sub-receiver -- at the default grid and held to three workgroups (many tiles per
-    workgroup: the output stage's flush cadence, peaks carried across chunks) -- and the baseband IQ equals the oracle."""
-    if grid:
-        monkeypatch.setenv("PYSDR_TUNING", "1")
-        monkeypatch.setenv("PYSDR_MIXDEC_GRID", str(grid))
-    cfg = dict(so.CONFIGS["TEST2RX" if name == "RTL" else name], ntaps_dec=1001)
-    if name == "RTL":
-        cfg['fs'] = 2.048e6                   # the reference's RTL rate (3/128 to 48 kHz): TEST's two NFM sub-receivers on it
-    if name == "C3":
-        import bench
-        cfg['rx'] = bench.RX6[:nrx]
-    else:
-        cfg['rx'] = cfg['rx'][:nrx]
+def check_does_not_depend_on_the_cut(cfg, B=10, x=None, want_iq=None):
+    """Chunk by chunk == one batch == cut at random places, bit for bit, for every sub-receiver (baseband IQ, audio, chunk
+    counts; the raw chunk peaks are NumPy's), and the baseband IQ equals the oracle (``want_iq[i]``: a reference of the caller's
+    for the B chunks of ``x``, else the float32 oracle).  -> (the chunked run's parameters, the worst IQ error)."""
     L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
-    B = 10
-    x = so.synth_iq(cfg, B * L, 33)
+    x = so.synth_iq(cfg, B * L, 33) if x is None else x
+    assert len(x) == B * L
     P1, g1 = make_gpu_receivers(cfg)
     am1, iq1 = [[] for _ in g1], [[] for _ in g1]
     for k in range(B):
@@ -615,9 +615,35 @@ def test_multi_rx_long_prototype_does_not_depend_on_the_cut(name, nrx, grid, mon
                 rx.demod_data(x[c:min(c + 4 * L, b)]); iq3[i].append(rx.iq.copy())
     for i in range(len(g3)):
         assert np.array_equal(np.concatenate(iq1[i]), np.concatenate(iq3[i])), i
-    for i, o in enumerate(so.make_receivers(cfg, np.float32)):
-        want = np.concatenate([(o.demod_data(x[k * L:(k + 1) * L]), o.iq.copy())[1] for k in range(B)])
-        assert relerr(np.concatenate(iq1[i]), want) <= TOL, (i, o.mode)
+    worst = 0.0
+    for i, o in enumerate(so.make_receivers(cfg, np.float32) if want_iq is None else want_iq):
+        want = o if want_iq is not None else \
+            np.concatenate([(o.demod_data(x[k * L:(k + 1) * L]), o.iq.copy())[1] for k in range(B)])
+        e = relerr(np.concatenate(iq1[i]), want)
+        worst = max(worst, e)
+        assert e <= TOL, (i, e)
+    return P1, worst
+
+
+@pytest.mark.parametrize("grid", [0, 3])
+@pytest.mark.parametrize("name,nrx", [("FT8TRI", 3), ("TEST2RX", 2), ("FT8TRI", 2), ("C3", 4), ("C3", 6), ("C3", 5), ("RTL", 2)])
+def test_multi_rx_long_prototype_does_not_depend_on_the_cut(name, nrx, grid, monkeypatch):
+    """The tap-holding shapes of the vector mix + decimate kernel (mixdec.hip, 768 threads: 2 - 6 sub-receivers, 1001 taps at
+    UP = 3; 4, 5 and 6 RX on C3's stream re-run with the long prototype; 3/500, 3/250 and 3/128): chunk by chunk == one batch == cut at random
+    places, bit for bit, for every sub-receiver -- at the default grid and held to three workgroups (many tiles per
+    workgroup: the output stage's flush cadence, peaks carried across chunks) -- and the baseband IQ equals the oracle."""
+    if grid:
+        monkeypatch.setenv("PYSDR_TUNING", "1")
+        monkeypatch.setenv("PYSDR_MIXDEC_GRID", str(grid))
+    cfg = dict(so.CONFIGS["TEST2RX" if name == "RTL" else name], ntaps_dec=1001)
+    if name == "RTL":
+        cfg['fs'] = 2.048e6                   # the reference's RTL rate (3/128 to 48 kHz): TEST's two NFM sub-receivers on it
+    if name == "C3":
+        import bench
+        cfg['rx'] = bench.RX6[:nrx]
+    else:
+        cfg['rx'] = cfg['rx'][:nrx]
+    check_does_not_depend_on_the_cut(cfg)
 
 
 @pytest.mark.parametrize("name", ["FT8TRI", "TEST2RX"])
