@@ -305,6 +305,36 @@ int  pysdr_rtty_reset(pysdr_rtty* rt);
 int  pysdr_rtty_decode(pysdr_rtty* rt, const float* lines, int nlines, int on_device, int flipped, int* codes,
                        long long* t, double* snr2, int* n_dec, int* ndet, int* isym, float* best);
 
+/* ---- polyphase channelizer: every channel of an M-channel raster in one pass (a build feature,
+ * no reference call site: the reference tunes one sub-receiver per channel, receiver.py:826-835) ----------------------
+ * M = 2^a 5^b in [16, 4096] channels centred on k fs / M (k >= M/2: the negative frequency (k - M) fs / M), decimation D
+ * with M / D in {1, 2, 4} (output rate fs / D), real prototype h of 1 <= ntaps <= 16 M taps:
+ *   y_k[m] = sum_i h[i] x[mD - i] exp(-j 2 pi ((k (mD - i)) mod M) / M),  x[n] = 0 for n < 0, n and m absolute since create
+ * or reset -- channel k is NCO(-k fs / M) + the rational resampler with UP = 1 of a sub-receiver's rx.iq.  A call that brings
+ * the samples [s0, s1) produces the outputs with s0 <= mD < s1 (any n, 0 and n < D included); any cut of a stream into
+ * calls gives the same bits.  Output is channel-major: out[a * out_pitch + i] (complex samples), row a = channel
+ * (k_first + a) mod M, a < nk, i < *n_out.
+ * pysdr_chan_plan needs no device: PYSDR_ERR_ARG for a shape outside these rules, else out = {passes, radix of pass
+ * 0 .. 7 (0 beyond the last), frames per workgroup, frames per FIR work item, threads, LDS bytes, history length
+ * ceil(ntaps / M) M - 1, taps per branch, 0}.
+ * create: max_taps bounds later set_taps, max_in the samples of one call; no output before the first set_taps
+ * (PYSDR_ERR_STATE).  set_taps takes effect at the next call, for the whole window of that call's outputs (rx.dec.h).
+ * process: iq / out are device pointers where on_device / out_on_device != 0; with both the call only queues work on the
+ * channelizer's stream (pysdr_chan_sync waits for it), otherwise it returns with the host buffers filled.
+ * The device staging of a host input (max_in samples) and of a host output (nk rows) is allocated by the first call that
+ * passes a host pointer on that side; a handle fed device pointers only never holds it.
+ * PYSDR_ERR_STATE: n > max_in, or out_pitch smaller than the call's output count.
+ * set_taps / reset / sync / process of one handle exclude each other (a lock in the handle); destroy must not race them. */
+typedef struct pysdr_chan pysdr_chan;
+int  pysdr_chan_plan(int M, int D, int ntaps, int k_first, int nk, int32_t out[16]);
+int  pysdr_chan_create(int device, int M, int D, int k_first, int nk, int max_taps, int max_in, pysdr_chan** out);
+void pysdr_chan_destroy(pysdr_chan* ch);
+int  pysdr_chan_set_taps(pysdr_chan* ch, const double* h, int ntaps);
+int  pysdr_chan_reset(pysdr_chan* ch);
+int  pysdr_chan_sync(pysdr_chan* ch);
+int  pysdr_chan_process(pysdr_chan* ch, const void* iq, int n, int on_device, void* out, long long out_pitch,
+                        int out_on_device, int* n_out);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -111,6 +111,13 @@ PROTOTYPES = {
     "pysdr_rtty_destroy": (None, [_vp]),
     "pysdr_rtty_reset": (_i, [_vp]),
     "pysdr_rtty_decode": (_i, [_vp, _vp, _i, _i, _i, _pi, C.POINTER(C.c_longlong), _pd, _pi, _pi, _pi, _pf]),
+    "pysdr_chan_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_chan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "pysdr_chan_destroy": (None, [_vp]),
+    "pysdr_chan_set_taps": (_i, [_vp, _pd, _i]),
+    "pysdr_chan_reset": (_i, [_vp]),
+    "pysdr_chan_sync": (_i, [_vp]),
+    "pysdr_chan_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -120,3 +120,10 @@ def squelch_ratio_taps(fs_out, ntaps=63):
     lp = firwin(ntaps, 3000.0, window='hamming', fs=fs_out)
     hp = firwin(ntaps, 4000.0, window='hamming', pass_zero=False, fs=fs_out)
     return np.ascontiguousarray(lp, np.float32), np.ascontiguousarray(hp, np.float32)
+
+
+def channelizer_taps(M, taps_per_branch=8):
+    """Default prototype of the polyphase channelizer: Kaiser(8.0) low-pass, cut-off half a channel
+    spacing, ``taps_per_branch`` taps on each of the M branches.  Sum 1, -6.02 dB at half a spacing, <= -83 dB from one
+    spacing on: alias-free to 80 dB for D <= M/2."""
+    return firwin(int(taps_per_branch) * int(M), 0.5 / M, window=('kaiser', 8.0), fs=1.0)
