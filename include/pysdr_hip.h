@@ -335,6 +335,51 @@ int  pysdr_chan_sync(pysdr_chan* ch);
 int  pysdr_chan_process(pysdr_chan* ch, const void* iq, int n, int on_device, void* out, long long out_pitch,
                         int out_on_device, int* n_out);
 
+/* ---- channel bank: AM / NFM audio, AGC and squelch on every row of a channelizer (a build feature:
+ * the reference demodulates one sub-receiver per channel, receiver.py:826-835) -----------------------------------------
+ * Every row a < nk of the channelizer `ch` gets a sub-receiver's stage 2 in mode PYSDR_AM or PYSDR_NFM: with y[m] the
+ * row (bit for bit what pysdr_chan_process delivers, 0 for m < 0) and c[0 .. ntaps_af) real AF taps, 3 <= ntaps_af <= 255,
+ *   d[m] = |y[m]|  (AM)   or   f32(fs_out / (2 pi 5000)) fm(y[m-2], y[m-1], y[m])  (NFM, sigs/nfm.m:124-127),
+ *   a[m] = sum_i c[i] d[m - i],   am[m] = a[m] gain.
+ * One mode, one AF filter, one AGC setting and one squelch threshold hold for the whole bank.  A call that completes
+ * n_out >= 1 outputs is one AGC block per channel: peak = max |a| over its outputs goes through the block AGC (active
+ * in AM while enabled; NFM has gain 1), and in NFM with a threshold > 0 the mean of |d[m] - 2 d[m-1] + d[m-2]| over
+ * its outputs goes through level += 0.64 (noise - level); a channel whose level exceeds the threshold is closed and gets
+ * gain 0.  A call that completes no output changes no AGC and no squelch state.  The un-gained a does not depend on how
+ * a stream is cut into calls, bit for bit; am, AGC and squelch do, by definition.
+ * pysdr_bank_plan needs no device: PYSDR_ERR_ARG for nk outside [1, 4096], ntaps_af outside [3, 255] or max_out < 1, else
+ * out = {outputs per workgroup, threads, LDS bytes, workgroups per row for max_out outputs, history samples kept per
+ * row, taps rounded up to steps of 8, 0, 0}.
+ * create borrows ch, which must outlive the bank, and resets it (pysdr_chan_reset: the bank's stream starts at sample 0
+ * of an empty channelizer); while a bank exists, feed ch only through it.  fs_out = the channelizer's
+ * output rate fs / D (the NFM scale).  No output before the first set_mode (PYSDR_ERR_STATE); set_mode takes a mode and
+ * ntaps == ntaps_af real taps and holds from the next call on, for the whole AF window of that call's outputs; any other
+ * mode or tap count: PYSDR_ERR_ARG.  set_agc: enable and the target block peak ref > 0 (0.5 at create); set_squelch: the
+ * threshold, 0 = off.  reset also resets the channelizer.
+ * process: iq as in pysdr_chan_process (device pointer where on_device != 0).  am[a * am_pitch + i], i < *n_out, is a host
+ * or (am_on_device != 0) device buffer, or NULL: the results stay on the device for pysdr_bank_fetch.  With a device or
+ * no am buffer and device input the call only queues work on the channelizer's stream (pysdr_bank_sync waits for it).
+ * PYSDR_ERR_STATE: n > max_in of the channelizer, or am_pitch smaller than the call's output count.
+ * state: agc (smoothed peak), gain (before the gate), maxbuf (last block peak), squelch level and gate of every channel,
+ * [nk] each, NULL skips.  fetch: the last call's outputs of the named rows only -- am[i * pitch + j] and the channel
+ * samples iq[2 (i * pitch + j)] of row rows[i]; either may be NULL.  After a call that completed no output (and after
+ * create and reset) there is nothing to fetch: the buffers are left as they are.
+ * The calls on one handle exclude each other (a lock in the handle); destroy must not race them.  An error leaves the
+ * handle usable. */
+typedef struct pysdr_bank pysdr_bank;
+int  pysdr_bank_plan(int nk, int ntaps_af, int max_out, int32_t out[8]);
+int  pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pysdr_bank** out);
+void pysdr_bank_destroy(pysdr_bank* b);
+int  pysdr_bank_set_mode(pysdr_bank* b, int mode, const double* af, int ntaps);
+int  pysdr_bank_set_agc(pysdr_bank* b, int enable, float ref);
+int  pysdr_bank_set_squelch(pysdr_bank* b, float thresh);
+int  pysdr_bank_reset(pysdr_bank* b);
+int  pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, float* am, long long am_pitch,
+                        int am_on_device, int* n_out);
+int  pysdr_bank_state(pysdr_bank* b, float* agc, float* gain, float* maxbuf, float* level, uint8_t* open);
+int  pysdr_bank_fetch(pysdr_bank* b, const int* rows, int nrows, float* am, float* iq, long long pitch);
+int  pysdr_bank_sync(pysdr_bank* b);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -118,6 +118,17 @@ PROTOTYPES = {
     "pysdr_chan_reset": (_i, [_vp]),
     "pysdr_chan_sync": (_i, [_vp]),
     "pysdr_chan_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
+    "pysdr_bank_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_bank_create": (_i, [_vp, _d, _i, _i, C.POINTER(_vp)]),
+    "pysdr_bank_destroy": (None, [_vp]),
+    "pysdr_bank_set_mode": (_i, [_vp, _i, _pd, _i]),
+    "pysdr_bank_set_agc": (_i, [_vp, _i, _f]),
+    "pysdr_bank_set_squelch": (_i, [_vp, _f]),
+    "pysdr_bank_reset": (_i, [_vp]),
+    "pysdr_bank_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
+    "pysdr_bank_state": (_i, [_vp, _pf, _pf, _pf, _pf, C.POINTER(C.c_uint8)]),
+    "pysdr_bank_fetch": (_i, [_vp, _pi, _i, _pf, _pf, C.c_longlong]),
+    "pysdr_bank_sync": (_i, [_vp]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpysdr_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpysdr_hip_diag.so")   # loaded only when PYSDR_USE_DIAG_LIB=1
-SOURCES = ["api.hip", "mixdec.hip", "mixdec_mfma.hip", "resamp_small.hip", "stage2.hip", "pllseed.hip", "misc.hip", "psdfft.hip", "waterfall.hip", "rtty.hip", "chan.hip"]
+SOURCES = ["api.hip", "mixdec.hip", "mixdec_mfma.hip", "resamp_small.hip", "stage2.hip", "pllseed.hip", "misc.hip", "psdfft.hip", "waterfall.hip", "rtty.hip", "chan.hip", "bank.hip"]
 # Flags every build uses (measured choices, part of the shipped configuration):
 #   stage2.hip   -fno-slp-vectorize: packed-f32 pairs built by the SLP vectoriser run at half rate on gfx950 and are fed
 #                by v_mov shuffles; the AF FIR is written for plain FMAs with its own v_pk_fma_f32
@@ -23,8 +23,10 @@ SOURCES = ["api.hip", "mixdec.hip", "mixdec_mfma.hip", "resamp_small.hip", "stag
 #                pays for the pairing with v_mov shuffles and 17 more registers; -fno-signed-zeros lets the zero-padded
 #                half of the first DFT16 fold away (C3, PSD ms per 10666 frames: default 2.752 / 2.774, -fno-slp-vectorize
 #                2.731, + -fno-signed-zeros 2.721: the pair is fabric-bound, 17 % fewer issue cycles buy 1.5 %)
+#   bank.hip     the AF FIR of the channel bank is the same chain of plain FMAs over a register window as stage2.hip's
 BASE_FLAGS = {"stage2.hip": ["-fno-slp-vectorize"],
-              "psdfft.hip": ["-fno-slp-vectorize", "-fno-signed-zeros"]}
+              "psdfft.hip": ["-fno-slp-vectorize", "-fno-signed-zeros"],
+              "bank.hip": ["-fno-slp-vectorize"]}
 # Extra flags for A/B runs (-DMM_C1_NBUF=3, -DFIRX_THREADS=128, ...), one variable per source file.  They are read ONLY
 # under PYSDR_TUNING=1 (the same master switch the library's run-time tuning variables obey) or for the diagnostic build:
 # an ambient variable cannot change the shipped library.  PYSDR_PSD_FLAGS REPLACES psdfft.hip's base flags (its A/B is about them).
@@ -33,7 +35,7 @@ BASE_FLAGS = {"stage2.hip": ["-fno-slp-vectorize"],
 FLAG_VARS = {"mixdec.hip": "PYSDR_MIXDEC_FLAGS", "mixdec_mfma.hip": "PYSDR_MFMA_FLAGS", "resamp_small.hip": "PYSDR_RESAMP_FLAGS",
              "api.hip": "PYSDR_API_FLAGS",        # a shape's S / NB enter the host's plan: pass the same -D to both
              "stage2.hip": "PYSDR_STAGE2_FLAGS", "pllseed.hip": "PYSDR_SEED_FLAGS", "psdfft.hip": "PYSDR_PSD_FLAGS",
-             "chan.hip": "PYSDR_CHAN_FLAGS"}
+             "chan.hip": "PYSDR_CHAN_FLAGS", "bank.hip": "PYSDR_BANK_FLAGS"}
 
 
 def extra_flags(diag=False):

@@ -14,7 +14,7 @@
 //   3. Store: row a = channel (k_first + a) mod M of the channel-major output takes its fw frames from LDS position
 //      perm[a] (the digit reversal, a host table); consecutive lanes write consecutive frames of a row.
 // No intermediate goes through memory; the only other launch of a call is the roll of the input history.
-#include "common.h"
+#include "chan_internal.h"
 
 #include <cmath>
 #include <mutex>
@@ -254,6 +254,13 @@ struct pysdr_chan {
   std::vector<float> h_taps;
   std::mutex mu;            // one call at a time on a handle: set_taps / reset / sync / process
 };
+
+namespace pysdr {
+ChanInfo chan_info(pysdr_chan* c) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  return ChanInfo{c->device, c->M, c->D, c->nk, c->max_in, c->out_cap, c->n_abs, c->stream};
+}
+}  // namespace pysdr
 
 using namespace pysdr;
 
