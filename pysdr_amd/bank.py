@@ -1,4 +1,5 @@
-"""Channel bank: AM / NFM audio, AGC and squelch on every channel of a raster (``bank.hip``).  A
+"""Channel bank: AM / NFM audio, AGC and squelch on every channel of a raster (kernels ``bank.hip``,
+host half ``api_objects.hip``).  A
 ``Channelizer`` delivers the rows; every row then gets what a sub-receiver tuned there would do behind its ``rx.iq`` --
 detector, real AF low-pass, block AGC (AM), noise squelch (NFM) -- with one call as the AGC block.  One mode, one AF
 filter, one squelch threshold and one AGC setting hold for the whole bank."""

@@ -1,5 +1,5 @@
-"""Polyphase channelizer: every channel of an M-channel raster in one pass over the wideband input (DESIGN.md 3 item 15,
-``chan.hip``).  Channel k is centred on k fs / M and comes out at fs / D, exactly as a sub-receiver tuned there with
+"""Polyphase channelizer: every channel of an M-channel raster in one pass over the wideband input (DESIGN.md 3 item 15;
+kernels ``chan.hip``, host half ``api_objects.hip``).  Channel k is centred on k fs / M and comes out at fs / D, exactly as a sub-receiver tuned there with
 UP = 1 and the prototype ``h`` would deliver its ``rx.iq`` -- but the input is read once for all of them."""
 from __future__ import annotations
 

@@ -1,6 +1,6 @@
 // C ABI of libpysdr_hip.so (include/pysdr_hip.h): context management, the per-call
 // launch sequence of the receiver hot path, spectrum (rocFFT), device-memory helpers
-// and the RCCL broadcast.  Host-side only; kernels live in mixdec/stage2/misc.hip.
+// and the RCCL broadcast (the four stream objects: api_objects.hip).  Host-side only; kernels live in mixdec/stage2/misc.hip.
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 #include <rocfft/rocfft.h>
@@ -15,6 +15,7 @@
 #include "host_res.h"
 #include "mixdec_mfma_geom.h"
 #include "mixdec_plan.h"
+#include "objects_plan.h"
 
 namespace pysdr {
 
@@ -25,6 +26,24 @@ void set_last_error(const char* fmt, ...) {
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
+}
+
+// (these two are shared with api_objects.hip: objects_plan.h)
+int use_device(int dev) {
+  hipError_t e = hipSetDevice(dev);
+  if (e != hipSuccess) {
+    set_last_error("hipSetDevice(%d): %s", dev, hipGetErrorString(e));
+    return PYSDR_ERR_NO_DEVICE;
+  }
+  return PYSDR_OK;
+}
+
+// A create function that failed half-way: the message gains the entry point's name in front of the failing call and
+// its HIP error string; the caller then destroys the half-built object (its owners free what exists).
+int failed_in(const char* entry, int rc) {
+  const std::string what = pysdr_last_error();
+  set_last_error("%s: %s", entry, what.c_str());
+  return rc;
 }
 
 }  // namespace pysdr
@@ -269,15 +288,6 @@ namespace {
 
 std::mutex g_rocfft_mu;
 int g_rocfft_users = 0;
-
-int use_device(int dev) {
-  hipError_t e = hipSetDevice(dev);
-  if (e != hipSuccess) {
-    set_last_error("hipSetDevice(%d): %s", dev, hipGetErrorString(e));
-    return PYSDR_ERR_NO_DEVICE;
-  }
-  return PYSDR_OK;
-}
 
 // g[p][k] = h[p + up*k] * exp(-j*w*k), w = 2*pi*fword/2^32
 void build_taps(const Decim& d, const double* h, int nt, uint32_t fword, float2* out) {
@@ -684,14 +694,6 @@ int run_tail(pysdr_ctx* c, TailJob& j) {
 int flush_tail(pysdr_ctx* c) {
   if (!c->tail.valid) return PYSDR_OK;
   return run_tail(c, c->tail);
-}
-
-// A create function that failed half-way: the message gains the entry point's name in front of the failing call and
-// its HIP error string; the caller then destroys the half-built object (its owners free what exists).
-int failed_in(const char* entry, int rc) {
-  const std::string what = pysdr_last_error();
-  set_last_error("%s: %s", entry, what.c_str());
-  return rc;
 }
 
 // The device allocations of a new context and their initial fills

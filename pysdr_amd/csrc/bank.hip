@@ -17,59 +17,13 @@
 //       squelch updates (one lane), scales the row in place where the gain is not 1, and moves the last Hpad samples of
 //       the row to its front (read, barrier, write: the ranges may overlap).
 // A call that completes no output launches neither and changes no state.
-#include "chan_internal.h"
-
-#include <cmath>
-#include <mutex>
+#include "objects_plan.h"
 
 namespace pysdr {
 namespace {
 
-constexpr int kBankThreads = 256;
-constexpr int kBankW = 8;                               // outputs per thread = taps per step
-constexpr int kBankTile = kBankThreads * kBankW;        // outputs per workgroup
-constexpr int kBankTapsMin = 3, kBankTapsMax = 255;     // 3: the squelch's second difference reaches d[m - 2]
-constexpr int kBankNkMax = 4096;
-constexpr float kAgcBeta = 0.1f, kAgcGainMax = 1.0e4f, kAgcRefDefault = 0.5f, kAgcFloor = 1e-12f;
+constexpr float kAgcBeta = 0.1f, kAgcGainMax = 1.0e4f, kAgcFloor = 1e-12f;
 constexpr float kBankSqAlpha = 0.64f;
-constexpr double kNfmFullScaleDev = 5000.0;
-
-struct BankPlan {
-  int tp = 0;          // taps rounded up to whole steps of 8
-  int hpad = 0;        // history samples kept in front of a row, >= T + 1, a multiple of 8
-  int lds_floats = 0;  // kBankTile + tp
-  int tiles = 0;       // per row, for max_out outputs
-};
-
-bool bank_plan(int nk, int ntaps, int max_out, BankPlan* p) {
-  if (nk < 1 || nk > kBankNkMax || ntaps < kBankTapsMin || ntaps > kBankTapsMax || max_out < 1) return false;
-  BankPlan q;
-  q.tp = (ntaps + kBankW - 1) / kBankW * kBankW;
-  q.hpad = (ntaps + 1 + 7) & ~7;
-  q.lds_floats = kBankTile + q.tp;
-  q.tiles = (max_out + kBankTile - 1) / kBankTile;
-  *p = q;
-  return true;
-}
-
-struct BankState {       // one per channel, in device memory
-  float agc, gain, maxbuf, err, level;
-  int open;
-};
-
-struct BankArgs {
-  const float2* y;        // Y + Hpad: y[a * ypitch + i] = output i of this call, i >= -Hpad (history)
-  long long ypitch;
-  float* a;               // a[a * apitch + i]
-  long long apitch;
-  int n_out, T, tp;
-  const float* taps;      // [tp], zero beyond T (never multiplied: 0 * NaN would widen a NaN's footprint)
-  float fm_scale;
-  int noise;              // 1: leave the squelch's partial sums
-  float* pmax;            // [nk][ptiles]
-  double* psum;           // [nk][ptiles]
-  int ptiles;
-};
 
 // max that keeps a NaN, as np.max does
 __device__ __forceinline__ float nanmax(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
@@ -176,20 +130,6 @@ __global__ __launch_bounds__(kBankThreads) void bank_kernel(const BankArgs a) {
   }
 }
 
-struct FinishArgs {
-  float2* ybase;          // Y: row a at ybase + a * ypitch, history in [0, hpad)
-  long long ypitch;
-  float* a;
-  long long apitch;
-  int n_out, hpad, ntiles, ptiles;
-  const float* pmax;
-  const double* psum;
-  BankState* state;
-  int agc_active;         // AGC enabled and mode AM
-  int squelch;            // mode NFM and threshold > 0
-  float ref, thresh;
-};
-
 __global__ __launch_bounds__(kBankThreads) void bank_finish(const FinishArgs f) {
   __shared__ double ssum[kBankThreads];
   __shared__ float smax[kBankThreads];
@@ -246,248 +186,19 @@ __global__ __launch_bounds__(kBankThreads) void bank_finish(const FinishArgs f) 
 }
 
 }  // namespace
+
+int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st) {
+  const size_t lds = (size_t)p.lds_floats * sizeof(float);
+  if (mode == PYSDR_AM) hipLaunchKernelGGL(bank_kernel<PYSDR_AM>, dim3(ntiles, nk), dim3(kBankThreads), lds, st, a);
+  else hipLaunchKernelGGL(bank_kernel<PYSDR_NFM>, dim3(ntiles, nk), dim3(kBankThreads), lds, st, a);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
+int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st) {
+  hipLaunchKernelGGL(bank_finish, dim3(nk), dim3(kBankThreads), 0, st, f);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
 }  // namespace pysdr
-
-struct pysdr_bank {
-  pysdr_chan* ch = nullptr;
-  pysdr::ChanInfo ci{};
-  pysdr::BankPlan plan;
-  int mode = PYSDR_NFM, T = 0;
-  bool have_taps = false;
-  int agc_enable = 1;
-  float ref = pysdr::kAgcRefDefault, thresh = 0.f, fm_scale = 0.f;
-  int last_n_out = 0;
-  long long ypitch = 0, apitch = 0;
-  float2* d_y = nullptr;            // [nk][hpad + out_cap]
-  float* d_a = nullptr;             // [nk][out_cap]
-  float* d_taps = nullptr;          // [tp]
-  float* d_pmax = nullptr;          // [nk][tiles]
-  double* d_psum = nullptr;         // [nk][tiles]
-  pysdr::BankState* d_state = nullptr;
-  std::vector<float> h_taps;
-  std::vector<pysdr::BankState> h_state;
-  std::mutex mu;                    // one call at a time on a handle
-};
-
-using namespace pysdr;
-
-static int bank_reset_locked(pysdr_bank* b) {
-  const int rc = pysdr_chan_reset(b->ch);
-  if (rc != PYSDR_OK) return rc;
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  hipStream_t st = b->ci.stream;
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // h_state may still feed an earlier copy
-  PYSDR_HIP_CHECK(hipMemsetAsync(b->d_y, 0, (size_t)b->ci.nk * b->ypitch * sizeof(float2), st));
-  b->h_state.assign((size_t)b->ci.nk, BankState{0.f, 1.f, 0.f, 0.f, 0.f, 1});
-  PYSDR_HIP_CHECK(hipMemcpyAsync(b->d_state, b->h_state.data(), b->h_state.size() * sizeof(BankState), hipMemcpyHostToDevice, st));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  b->last_n_out = 0;
-  return PYSDR_OK;
-}
-
-extern "C" {
-
-int pysdr_bank_plan(int nk, int ntaps_af, int max_out, int32_t out[8]) {
-  if (!out) { set_last_error("pysdr_bank_plan: out is NULL"); return PYSDR_ERR_ARG; }
-  BankPlan p;
-  if (!bank_plan(nk, ntaps_af, max_out, &p)) {
-    set_last_error("pysdr_bank_plan: nk %d outside [1, %d], ntaps_af %d outside [%d, %d] or max_out %d < 1", nk, kBankNkMax,
-                   ntaps_af, kBankTapsMin, kBankTapsMax, max_out);
-    return PYSDR_ERR_ARG;
-  }
-  out[0] = kBankTile; out[1] = kBankThreads; out[2] = p.lds_floats * (int)sizeof(float); out[3] = p.tiles; out[4] = p.hpad;
-  out[5] = p.tp; out[6] = 0; out[7] = 0;
-  return PYSDR_OK;
-}
-
-int pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pysdr_bank** out) {
-  if (!out) { set_last_error("pysdr_bank_create: out is NULL"); return PYSDR_ERR_ARG; }
-  *out = nullptr;
-  if (!ch) { set_last_error("pysdr_bank_create: NULL channelizer"); return PYSDR_ERR_ARG; }
-  if (mode != PYSDR_AM && mode != PYSDR_NFM) { set_last_error("pysdr_bank_create: mode %d is neither AM nor NFM", mode); return PYSDR_ERR_ARG; }
-  if (!(fs_out > 0.0)) { set_last_error("pysdr_bank_create: fs_out %g", fs_out); return PYSDR_ERR_ARG; }
-  const ChanInfo ci = chan_info(ch);
-  BankPlan p;
-  if (!bank_plan(ci.nk, ntaps_af, ci.out_cap, &p)) {
-    set_last_error("pysdr_bank_create: ntaps_af %d outside [%d, %d]", ntaps_af, kBankTapsMin, kBankTapsMax);
-    return PYSDR_ERR_ARG;
-  }
-  hipError_t e0 = hipSetDevice(ci.device);
-  if (e0 != hipSuccess) { set_last_error("hipSetDevice(%d): %s", ci.device, hipGetErrorString(e0)); return PYSDR_ERR_NO_DEVICE; }
-  pysdr_bank* b = new pysdr_bank();
-  b->ch = ch; b->ci = ci; b->plan = p; b->mode = mode; b->T = ntaps_af;
-  b->fm_scale = (float)(fs_out / (2.0 * M_PI * kNfmFullScaleDev));
-  b->ypitch = (long long)p.hpad + ci.out_cap;
-  b->apitch = ci.out_cap;
-#define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { set_last_error("pysdr_bank_create: %s -> %s", #e, hipGetErrorString(_e)); pysdr_bank_destroy(b); return PYSDR_ERR_HIP; } } while (0)
-  CK(hipMalloc(&b->d_y, (size_t)ci.nk * b->ypitch * sizeof(float2)));
-  CK(hipMalloc(&b->d_a, (size_t)ci.nk * b->apitch * sizeof(float)));
-  CK(hipMalloc(&b->d_taps, (size_t)p.tp * sizeof(float)));
-  CK(hipMalloc(&b->d_pmax, (size_t)ci.nk * p.tiles * sizeof(float)));
-  CK(hipMalloc(&b->d_psum, (size_t)ci.nk * p.tiles * sizeof(double)));
-  CK(hipMalloc(&b->d_state, (size_t)ci.nk * sizeof(BankState)));
-#undef CK
-  const int rc = bank_reset_locked(b);
-  if (rc != PYSDR_OK) { pysdr_bank_destroy(b); return rc; }
-  *out = b;
-  return PYSDR_OK;
-}
-
-void pysdr_bank_destroy(pysdr_bank* b) {
-  if (!b) return;
-  (void)hipSetDevice(b->ci.device);
-  if (b->ci.stream) (void)hipStreamSynchronize(b->ci.stream);
-  for (void* p : {(void*)b->d_y, (void*)b->d_a, (void*)b->d_taps, (void*)b->d_pmax, (void*)b->d_psum, (void*)b->d_state})
-    if (p) (void)hipFree(p);
-  delete b;
-}
-
-int pysdr_bank_set_mode(pysdr_bank* b, int mode, const double* af, int ntaps) {
-  if (!b || !af) { set_last_error("pysdr_bank_set_mode: NULL bank or taps"); return PYSDR_ERR_ARG; }
-  if (mode != PYSDR_AM && mode != PYSDR_NFM) { set_last_error("pysdr_bank_set_mode: mode %d is neither AM nor NFM", mode); return PYSDR_ERR_ARG; }
-  if (ntaps != b->T) { set_last_error("pysdr_bank_set_mode: ntaps %d != ntaps_af %d", ntaps, b->T); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  hipStream_t st = b->ci.stream;
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // the staging vector may still feed an earlier copy
-  b->h_taps.assign((size_t)b->plan.tp, 0.f);
-  for (int i = 0; i < ntaps; ++i) b->h_taps[i] = (float)af[i];
-  PYSDR_HIP_CHECK(hipMemcpyAsync(b->d_taps, b->h_taps.data(), b->h_taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  b->mode = mode;
-  b->have_taps = true;
-  return PYSDR_OK;
-}
-
-int pysdr_bank_set_agc(pysdr_bank* b, int enable, float ref) {
-  if (!b) { set_last_error("pysdr_bank_set_agc: NULL bank"); return PYSDR_ERR_ARG; }
-  if (!(ref > 0.f)) { set_last_error("pysdr_bank_set_agc: ref %g", (double)ref); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->agc_enable = enable ? 1 : 0;
-  b->ref = ref;
-  return PYSDR_OK;
-}
-
-int pysdr_bank_set_squelch(pysdr_bank* b, float thresh) {
-  if (!b) { set_last_error("pysdr_bank_set_squelch: NULL bank"); return PYSDR_ERR_ARG; }
-  if (!(thresh >= 0.f)) { set_last_error("pysdr_bank_set_squelch: threshold %g", (double)thresh); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  b->thresh = thresh;
-  return PYSDR_OK;
-}
-
-int pysdr_bank_reset(pysdr_bank* b) {
-  if (!b) { set_last_error("pysdr_bank_reset: NULL bank"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  return bank_reset_locked(b);
-}
-
-int pysdr_bank_sync(pysdr_bank* b) {
-  if (!b) { set_last_error("pysdr_bank_sync: NULL bank"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(b->ci.stream));
-  return PYSDR_OK;
-}
-
-int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, float* am, long long am_pitch, int am_on_device,
-                       int* n_out) {
-  if (!b || !n_out) { set_last_error("pysdr_bank_process: NULL bank or n_out"); return PYSDR_ERR_ARG; }
-  *n_out = 0;
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_bank_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
-  if (n > b->ci.max_in) { set_last_error("pysdr_bank_process: n %d > max_in %d", n, b->ci.max_in); return PYSDR_ERR_STATE; }
-  if (!b->have_taps) { set_last_error("pysdr_bank_process: no mode set"); return PYSDR_ERR_STATE; }
-  // what the channelizer is about to complete: checked before it advances its stream
-  const unsigned long long D = (unsigned long long)b->ci.D, s0 = chan_info(b->ch).n_abs, s1 = s0 + (unsigned long long)n;
-  const int nf_want = (int)((s1 + D - 1) / D - (s0 + D - 1) / D);
-  if (am && am_pitch < nf_want) {
-    set_last_error("pysdr_bank_process: pitch %lld < the call's %d outputs", am_pitch, nf_want);
-    return PYSDR_ERR_STATE;
-  }
-  int nf = 0;
-  const int rc = pysdr_chan_process(b->ch, iq, n, on_device, b->d_y + b->plan.hpad, b->ypitch, 1, &nf);
-  if (rc != PYSDR_OK) return rc;
-  if (nf != nf_want) { set_last_error("pysdr_bank_process: the channelizer was fed beside its bank (%d outputs, %d expected)", nf, nf_want); return PYSDR_ERR_STATE; }
-  if (nf == 0) { b->last_n_out = 0; return PYSDR_OK; }                // no output: no AGC block, no state change, nothing to fetch
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  hipStream_t st = b->ci.stream;
-  const int ntiles = (nf + kBankTile - 1) / kBankTile;
-  const int squelch = (b->mode == PYSDR_NFM && b->thresh > 0.f) ? 1 : 0;
-  BankArgs a{};
-  a.y = b->d_y + b->plan.hpad; a.ypitch = b->ypitch; a.a = b->d_a; a.apitch = b->apitch;
-  a.n_out = nf; a.T = b->T; a.tp = b->plan.tp; a.taps = b->d_taps; a.fm_scale = b->fm_scale; a.noise = squelch;
-  a.pmax = b->d_pmax; a.psum = b->d_psum; a.ptiles = b->plan.tiles;
-  const size_t lds = (size_t)b->plan.lds_floats * sizeof(float);
-  if (b->mode == PYSDR_AM) hipLaunchKernelGGL(bank_kernel<PYSDR_AM>, dim3(ntiles, b->ci.nk), dim3(kBankThreads), lds, st, a);
-  else hipLaunchKernelGGL(bank_kernel<PYSDR_NFM>, dim3(ntiles, b->ci.nk), dim3(kBankThreads), lds, st, a);
-  PYSDR_HIP_CHECK(hipGetLastError());
-  FinishArgs f{};
-  f.ybase = b->d_y; f.ypitch = b->ypitch; f.a = b->d_a; f.apitch = b->apitch;
-  f.n_out = nf; f.hpad = b->plan.hpad; f.ntiles = ntiles; f.ptiles = b->plan.tiles;
-  f.pmax = b->d_pmax; f.psum = b->d_psum; f.state = b->d_state;
-  f.agc_active = (b->agc_enable && b->mode == PYSDR_AM) ? 1 : 0;
-  f.squelch = squelch; f.ref = b->ref; f.thresh = b->thresh;
-  hipLaunchKernelGGL(bank_finish, dim3(b->ci.nk), dim3(kBankThreads), 0, st, f);
-  PYSDR_HIP_CHECK(hipGetLastError());
-  b->last_n_out = nf;
-  *n_out = nf;
-  if (am) {
-    PYSDR_HIP_CHECK(hipMemcpy2DAsync(am, (size_t)am_pitch * sizeof(float), b->d_a, (size_t)b->apitch * sizeof(float),
-                                     (size_t)nf * sizeof(float), (size_t)b->ci.nk,
-                                     am_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
-    if (!am_on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));     // the host buffer is the caller's again
-  }
-  return PYSDR_OK;
-}
-
-int pysdr_bank_state(pysdr_bank* b, float* agc, float* gain, float* maxbuf, float* level, uint8_t* open) {
-  if (!b) { set_last_error("pysdr_bank_state: NULL bank"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  hipStream_t st = b->ci.stream;
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  PYSDR_HIP_CHECK(hipMemcpyAsync(b->h_state.data(), b->d_state, b->h_state.size() * sizeof(BankState), hipMemcpyDeviceToHost, st));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  for (int i = 0; i < b->ci.nk; ++i) {
-    const BankState& s = b->h_state[i];
-    if (agc) agc[i] = s.agc;
-    if (gain) gain[i] = s.gain;
-    if (maxbuf) maxbuf[i] = s.maxbuf;
-    if (level) level[i] = s.level;
-    if (open) open[i] = s.open ? 1 : 0;
-  }
-  return PYSDR_OK;
-}
-
-int pysdr_bank_fetch(pysdr_bank* b, const int* rows, int nrows, float* am, float* iq, long long pitch) {
-  if (!b) { set_last_error("pysdr_bank_fetch: NULL bank"); return PYSDR_ERR_ARG; }
-  if (nrows < 0 || (nrows > 0 && !rows)) { set_last_error("pysdr_bank_fetch: nrows %d / NULL rows", nrows); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 0 || rows[i] >= b->ci.nk) { set_last_error("pysdr_bank_fetch: row %d outside [0, %d)", rows[i], b->ci.nk); return PYSDR_ERR_ARG; }
-  const int nf = b->last_n_out;
-  if (pitch < nf) { set_last_error("pysdr_bank_fetch: pitch %lld < the last call's %d outputs", pitch, nf); return PYSDR_ERR_STATE; }
-  if (nf == 0 || nrows == 0 || (!am && !iq)) return PYSDR_OK;
-  PYSDR_HIP_CHECK(hipSetDevice(b->ci.device));
-  hipStream_t st = b->ci.stream;
-  for (int i = 0; i < nrows; ++i) {
-    // runs of consecutive rows go as one strided copy
-    int run = 1;
-    while (i + run < nrows && rows[i + run] == rows[i] + run) ++run;
-    const size_t r = (size_t)rows[i];
-    if (am)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(am + (size_t)i * pitch, (size_t)pitch * sizeof(float), b->d_a + r * b->apitch,
-                                       (size_t)b->apitch * sizeof(float), (size_t)nf * sizeof(float), (size_t)run,
-                                       hipMemcpyDeviceToHost, st));
-    if (iq)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(iq + 2 * (size_t)i * pitch, (size_t)pitch * sizeof(float2),
-                                       b->d_y + r * b->ypitch + b->plan.hpad, (size_t)b->ypitch * sizeof(float2),
-                                       (size_t)nf * sizeof(float2), (size_t)run, hipMemcpyDeviceToHost, st));
-    i += run - 1;
-  }
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  return PYSDR_OK;
-}
-
-}  // extern "C"

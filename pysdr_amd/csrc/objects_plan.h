@@ -1,0 +1,179 @@
+// What the four stream objects -- waterfall, RTTY decoder bank, channelizer, channel bank -- share between their kernels
+// (waterfall.hip, rtty.hip, chan.hip, bank.hip), their host half (api_objects.hip) and the checking launch layer of
+// tests/host_san: constants, pure plans, kernel argument structs, and DECLARATIONS ONLY of the launch functions (defined in
+// the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  Nothing in this header calls the
+// HIP runtime; plain C++.  Not part of the public ABI.
+#pragma once
+
+#include "common.h"
+
+namespace pysdr {
+
+// api.hip: what every create function of the host layer shares
+int use_device(int dev);                        // hipSetDevice, PYSDR_ERR_NO_DEVICE with a message
+int failed_in(const char* entry, int rc);       // the message gains the entry point's name; returns rc
+
+// ---- waterfall (waterfall.hip) ---------------------------------------------------------
+constexpr float kFill = -1.0e38f;    // Plotting.py:385
+
+struct WfArgs {
+  const float* wf;        // [ncols][nfft]
+  int nfft, ncols, head, cnt, shift;
+  float* mean;            // [nfft]
+  float* stat;            // [0] bkgnd, [1] max(wf) as an ordered key
+  float* image;           // [ncols][nfft]
+};
+int launch_wf_fill(float* p, size_t n, float v, hipStream_t st);
+int launch_wf_push(const float* line, int n, int nfft, int shift, float* slot, hipStream_t st);
+int launch_wf_mean_median(const WfArgs& a, hipStream_t st);                         // mean, then stat[0]
+int launch_wf_max_image(const WfArgs& a, int npsd, float pan_dr, hipStream_t st);   // stat[1] (zeroed by the caller), then image
+int launch_wf_peaks(const float* x, int n, double height, int dist, int* pos, int* state, int* kept, int* count, hipStream_t st);
+
+// ---- RTTY decoder bank (rtty.hip) ------------------------------------------------------
+constexpr int kM = 30;                // lines per character (rtty.py:386)
+constexpr int kHist = 128;            // ring rows beyond max_lines
+constexpr int kMaxLines = 32768;
+
+struct RttyArgs {         // one decode call: lines n0 .. n0 + nlines - 1, decisions at n_first + 30 j, j < nd
+  const float* lines;     // [nlines][nfft]
+  int nfft, flipped, nlines;
+  int band_lo, nband, moff, nsh, nb, flo, fhi;    // moff, flo, fhi: counted from band_lo
+  long long n0, n_first;
+  int nd, max_dec, R;
+  float *band, *s4, *best, *sc2;                  // rings [R][nband] / [R][nb]
+  int* isym;                                      // ring [R][nb]
+  int* shift;                                     // [nb]
+  long long* t; double* snr; int* held; int* code;   // [max_dec][nb]
+  int* ndet;                                      // [max_lines]
+};
+int launch_rtty_decode(const RttyArgs& a, hipStream_t st);   // rt_gather .. rt_sc2, (rt_decide, rt_emit,) rt_find
+
+// ---- polyphase channelizer (chan.hip) --------------------------------------------------
+constexpr int kChanMaxPass = 8;
+constexpr int kChanLdsElems = 16384;      // complex LDS elements a workgroup may hold (128 KB of the 160 KB)
+constexpr int kChanMaxIn = 1 << 28;
+
+struct ChanPlan {
+  int npass = 0, radix[kChanMaxPass] = {};
+  int C = 0;          // M / D
+  int fw = 0;         // frames per workgroup
+  int fi = 0;         // frames per FIR work item
+  int threads = 0;
+  int mp = 0;         // LDS pitch of a frame, odd: the store reads one element of every frame side by side
+  int lds_bytes = 0;
+};
+
+// Pure arithmetic: which launch a channelizer of this shape runs with; false: outside the rules of DESIGN §3 item 15.
+inline bool chan_plan(int M, int D, ChanPlan* p) {
+  if (M < 16 || M > 4096 || D < 1 || M % D != 0) return false;
+  const int C = M / D;
+  if (C != 1 && C != 2 && C != 4) return false;
+  int twos = 0, fives = 0, m = M;
+  while (m % 2 == 0) { m /= 2; ++twos; }
+  while (m % 5 == 0) { m /= 5; ++fives; }
+  if (m != 1) return false;
+  ChanPlan q;
+  q.C = C;
+  for (int i = 0; i < fives; ++i) q.radix[q.npass++] = 5;
+  for (int i = 0; i < twos / 2; ++i) q.radix[q.npass++] = 4;
+  if (twos & 1) q.radix[q.npass++] = 2;
+  // 16 frames = 128-byte row segments while they fit the LDS; small M: as many groups of 16 as fill 256 branches
+  if (M <= 256) q.fw = 16 * (256 / M);
+  else if (M * 16 <= kChanLdsElems) q.fw = 16;
+  else if (M * 8 <= kChanLdsElems) q.fw = 8;
+  else q.fw = 4;
+  q.fi = q.fw < 8 ? 4 : 8;
+  q.mp = M | 1;
+  q.threads = q.fw * M > 4096 ? 1024 : 256;
+  q.lds_bytes = q.fw * q.mp * (int)sizeof(float2);
+  *p = q;
+  return true;
+}
+
+inline uint32_t magic_of(int d) { return (uint32_t)(0x100000000ull / (unsigned)d) + 1u; }   // d >= 2; exact n / d while n d < 2^32
+
+struct ChanArgs {
+  const float2* x;        // this call's samples, x[0] = absolute sample s0
+  const float2* hist;     // hist[H]: samples s0 - H .. s0 - 1 (zeros before the stream's start)
+  int H, n;
+  int off0;               // mf D - s0, 0 <= off0 < D: where the call's first frame mf ends
+  int mf_lo;              // mf mod 4
+  int nframes;
+  int M, D, P, mp, fw;
+  const float* taps;      // [P][M]
+  const float2* tw;       // [M] e^{+j 2 pi j / M}
+  const int* perm;        // [nk] LDS position of row a's channel
+  int nk;
+  float2* y;              // y[a * pitch + (m - mf)]
+  long long pitch;
+  int npass, radix[kChanMaxPass];
+  uint32_t magic_M, magic_fw, magic_per[kChanMaxPass], magic_nq[kChanMaxPass];
+  int xq, xr;             // grid / 8, grid % 8: the workgroups that share an L2 take consecutive runs of frames
+};
+int chan_prepare(const ChanPlan& p);            // more than 64 KB of LDS is an opt-in per kernel
+int launch_chan(const ChanPlan& p, const ChanArgs& a, int grid, hipStream_t st);
+// new history = last H samples of [old history | x[0 .. n)]
+int launch_chan_roll(const float2* x, int n, const float2* old, float2* neu, int H, hipStream_t st);
+
+// ---- channel bank (bank.hip) -----------------------------------------------------------
+constexpr int kBankThreads = 256;
+constexpr int kBankW = 8;                               // outputs per thread = taps per step
+constexpr int kBankTile = kBankThreads * kBankW;        // outputs per workgroup
+constexpr int kBankTapsMin = 3, kBankTapsMax = 255;     // 3: the squelch's second difference reaches d[m - 2]
+constexpr int kBankNkMax = 4096;
+constexpr float kAgcRefDefault = 0.5f;
+
+struct BankPlan {
+  int tp = 0;          // taps rounded up to whole steps of 8
+  int hpad = 0;        // history samples kept in front of a row, >= T + 1, a multiple of 8
+  int lds_floats = 0;  // kBankTile + tp
+  int tiles = 0;       // per row, for max_out outputs
+};
+
+inline bool bank_plan(int nk, int ntaps, int max_out, BankPlan* p) {
+  if (nk < 1 || nk > kBankNkMax || ntaps < kBankTapsMin || ntaps > kBankTapsMax || max_out < 1) return false;
+  BankPlan q;
+  q.tp = (ntaps + kBankW - 1) / kBankW * kBankW;
+  q.hpad = (ntaps + 1 + 7) & ~7;
+  q.lds_floats = kBankTile + q.tp;
+  q.tiles = (max_out + kBankTile - 1) / kBankTile;
+  *p = q;
+  return true;
+}
+
+struct BankState {       // one per channel, in device memory
+  float agc, gain, maxbuf, err, level;
+  int open;
+};
+
+struct BankArgs {
+  const float2* y;        // Y + Hpad: y[a * ypitch + i] = output i of this call, i >= -Hpad (history)
+  long long ypitch;
+  float* a;               // a[a * apitch + i]
+  long long apitch;
+  int n_out, T, tp;
+  const float* taps;      // [tp], zero beyond T (never multiplied: 0 * NaN would widen a NaN's footprint)
+  float fm_scale;
+  int noise;              // 1: leave the squelch's partial sums
+  float* pmax;            // [nk][ptiles]
+  double* psum;           // [nk][ptiles]
+  int ptiles;
+};
+
+struct FinishArgs {
+  float2* ybase;          // Y: row a at ybase + a * ypitch, history in [0, hpad)
+  long long ypitch;
+  float* a;
+  long long apitch;
+  int n_out, hpad, ntiles, ptiles;
+  const float* pmax;
+  const double* psum;
+  BankState* state;
+  int agc_active;         // AGC enabled and mode AM
+  int squelch;            // mode NFM and threshold > 0
+  float ref, thresh;
+};
+int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st);   // mode: PYSDR_AM | PYSDR_NFM
+int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st);
+
+}  // namespace pysdr

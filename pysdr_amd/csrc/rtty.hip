@@ -21,36 +21,10 @@
 //   rt_find     (line)               the finder's 21-line sums and their count
 // Sums are taken in the order NumPy takes them in the reference (sc2 sequential from best_n; snr2 and the finder
 // pairwise), so a difference from it comes only from the 32 x 32 float32 matmul, whose order BLAS decides.
-#include "common.h"
-
-struct pysdr_rtty {
-  int device = 0, nfft = 0, nsh = 0, bin_lo = 0, bin_hi = 0, find_lo = 0, find_hi = 0, max_lines = 0;
-  int nb = 0;              // decoders = bin_hi - bin_lo
-  int band_lo = 0, nband = 0;
-  int R = 0;               // ring rows; line n >= 1 lives in row n % R
-  int max_dec = 0;         // decisions one call can complete
-  long long n = 0;         // lines decoded so far
-  float* d_lines = nullptr;     // staging for host lines [max_lines][nfft]
-  float* d_band = nullptr;      // ring [R][nband]
-  float* d_s4 = nullptr;        // ring [R][nb]
-  float* d_best = nullptr;      // ring [R][nb]
-  float* d_sc2 = nullptr;       // ring [R][nb]
-  int* d_isym = nullptr;        // ring [R][nb]
-  int* d_shift = nullptr;       // [nb]
-  long long* d_t = nullptr;     // [max_dec][nb]
-  double* d_snr = nullptr;      // [max_dec][nb]
-  int* d_held = nullptr;        // [max_dec][nb]
-  int* d_code = nullptr;        // [max_dec][nb]
-  int* d_ndet = nullptr;        // [max_lines]
-  hipStream_t stream = nullptr;
-};
+#include "objects_plan.h"
 
 namespace pysdr {
 namespace {
-
-constexpr int kM = 30;                // lines per character (rtty.py:386)
-constexpr int kHist = 128;            // ring rows beyond max_lines
-constexpr int kMaxLines = 32768;
 
 __device__ __forceinline__ size_t rrow(long long n, int R) { return (size_t)(n % R); }
 
@@ -233,155 +207,22 @@ __global__ __launch_bounds__(256) void rt_find(const float* __restrict__ band, i
 }
 
 }  // namespace
-}  // namespace pysdr
 
-using namespace pysdr;
-
-extern "C" {
-
-int pysdr_rtty_create(int device, int nfft, int nbins_shift, int bin_lo, int bin_hi, int find_lo, int find_hi,
-                      int max_lines, pysdr_rtty** out) {
-  if (!out) { set_last_error("pysdr_rtty_create: out is NULL"); return PYSDR_ERR_ARG; }
-  *out = nullptr;
-  if (nfft < 2 || nbins_shift < 1 || nbins_shift >= nfft) {
-    set_last_error("pysdr_rtty_create: nfft %d / nbins_shift %d", nfft, nbins_shift);
-    return PYSDR_ERR_ARG;
+int launch_rtty_decode(const RttyArgs& a, hipStream_t st) {
+  const int gb = (a.nb + 255) / 256;
+  hipLaunchKernelGGL(rt_gather, dim3((a.nband + 255) / 256, a.nlines), dim3(256), 0, st, a.lines, a.nfft, a.flipped, a.band_lo,
+                     a.nband, a.n0, a.R, a.band);
+  hipLaunchKernelGGL(rt_s4, dim3(gb, a.nlines), dim3(256), 0, st, a.band, a.nband, a.moff, a.nsh, a.nb, a.n0, a.R, a.s4);
+  hipLaunchKernelGGL(rt_best, dim3(gb, a.nlines), dim3(256), 0, st, a.s4, a.nb, a.n0, a.R, a.best, a.isym);
+  hipLaunchKernelGGL(rt_sc2, dim3(gb, a.nlines), dim3(256), 0, st, a.best, a.nb, a.n0, a.R, a.sc2);
+  if (a.nd > 0) {
+    hipLaunchKernelGGL(rt_decide, dim3(gb, a.nd), dim3(256), 0, st, a.band, a.sc2, a.isym, a.nband, a.moff, a.nsh, a.nb,
+                       a.n_first, a.R, a.t, a.snr, a.held);
+    hipLaunchKernelGGL(rt_emit, dim3(gb), dim3(256), 0, st, a.snr, a.held, a.nb, a.nd, a.shift, a.code);
   }
-  const int top = nfft - nbins_shift;
-  if (bin_lo < 0 || bin_hi > top || bin_lo >= bin_hi) {
-    set_last_error("pysdr_rtty_create: decoder bins [%d, %d) not a non-empty range inside [0, %d)", bin_lo, bin_hi, top);
-    return PYSDR_ERR_ARG;
-  }
-  if (find_lo < 0 || find_hi > top || find_lo > find_hi) {
-    set_last_error("pysdr_rtty_create: finder bins [%d, %d) not a range inside [0, %d)", find_lo, find_hi, top);
-    return PYSDR_ERR_ARG;
-  }
-  if (max_lines < 1 || max_lines > kMaxLines) {
-    set_last_error("pysdr_rtty_create: max_lines %d outside [1, %d]", max_lines, kMaxLines);
-    return PYSDR_ERR_ARG;
-  }
-  hipError_t e0 = hipSetDevice(device);
-  if (e0 != hipSuccess) { set_last_error("hipSetDevice(%d): %s", device, hipGetErrorString(e0)); return PYSDR_ERR_NO_DEVICE; }
-  pysdr_rtty* r = new pysdr_rtty();
-  r->device = device; r->nfft = nfft; r->nsh = nbins_shift; r->bin_lo = bin_lo; r->bin_hi = bin_hi;
-  r->find_lo = find_lo; r->find_hi = find_hi; r->max_lines = max_lines;
-  r->nb = bin_hi - bin_lo;
-  r->band_lo = find_lo < find_hi ? (bin_lo < find_lo ? bin_lo : find_lo) : bin_lo;
-  const int hi = find_lo < find_hi ? (bin_hi > find_hi ? bin_hi : find_hi) : bin_hi;
-  r->nband = hi + nbins_shift - r->band_lo;                       // <= nfft - band_lo
-  r->R = max_lines + kHist;
-  r->max_dec = max_lines / kM + 1;
-  const size_t ring = (size_t)r->R * r->nb, dec = (size_t)r->max_dec * r->nb;
-#define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { set_last_error("pysdr_rtty_create: %s -> %s", #e, hipGetErrorString(_e)); pysdr_rtty_destroy(r); return PYSDR_ERR_HIP; } } while (0)
-  CK(hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking));
-  CK(hipMalloc(&r->d_lines, (size_t)max_lines * nfft * sizeof(float)));
-  CK(hipMalloc(&r->d_band, (size_t)r->R * r->nband * sizeof(float)));
-  CK(hipMalloc(&r->d_s4, ring * sizeof(float)));
-  CK(hipMalloc(&r->d_best, ring * sizeof(float)));
-  CK(hipMalloc(&r->d_sc2, ring * sizeof(float)));
-  CK(hipMalloc(&r->d_isym, ring * sizeof(int)));
-  CK(hipMalloc(&r->d_shift, (size_t)r->nb * sizeof(int)));
-  CK(hipMalloc(&r->d_t, dec * sizeof(long long)));
-  CK(hipMalloc(&r->d_snr, dec * sizeof(double)));
-  CK(hipMalloc(&r->d_held, dec * sizeof(int)));
-  CK(hipMalloc(&r->d_code, dec * sizeof(int)));
-  CK(hipMalloc(&r->d_ndet, (size_t)max_lines * sizeof(int)));
-#undef CK
-  const int rc = pysdr_rtty_reset(r);
-  if (rc != PYSDR_OK) { pysdr_rtty_destroy(r); return rc; }
-  *out = r;
-  return PYSDR_OK;
-}
-
-void pysdr_rtty_destroy(pysdr_rtty* r) {
-  if (!r) return;
-  (void)hipSetDevice(r->device);
-  if (r->stream) (void)hipStreamSynchronize(r->stream);
-  for (void* p : {(void*)r->d_lines, (void*)r->d_band, (void*)r->d_s4, (void*)r->d_best, (void*)r->d_sc2, (void*)r->d_isym,
-                  (void*)r->d_shift, (void*)r->d_t, (void*)r->d_snr, (void*)r->d_held, (void*)r->d_code, (void*)r->d_ndet})
-    if (p) (void)hipFree(p);
-  if (r->stream) (void)hipStreamDestroy(r->stream);
-  delete r;
-}
-
-int pysdr_rtty_reset(pysdr_rtty* r) {
-  if (!r) { set_last_error("pysdr_rtty_reset: NULL decoder"); return PYSDR_ERR_ARG; }
-  PYSDR_HIP_CHECK(hipSetDevice(r->device));
-  const size_t ring = (size_t)r->R * r->nb;
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_band, 0, (size_t)r->R * r->nband * sizeof(float), r->stream));
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_s4, 0, ring * sizeof(float), r->stream));
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_best, 0, ring * sizeof(float), r->stream));
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_sc2, 0, ring * sizeof(float), r->stream));
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_isym, 0, ring * sizeof(int), r->stream));
-  PYSDR_HIP_CHECK(hipMemsetAsync(r->d_shift, 0, (size_t)r->nb * sizeof(int), r->stream));   // shift off
-  PYSDR_HIP_CHECK(hipStreamSynchronize(r->stream));
-  r->n = 0;
-  return PYSDR_OK;
-}
-
-int pysdr_rtty_decode(pysdr_rtty* r, const float* lines, int nlines, int on_device, int flipped, int* codes,
-                      long long* t, double* snr2, int* n_dec, int* ndet, int* isym, float* best) {
-  if (!r) { set_last_error("pysdr_rtty_decode: NULL decoder"); return PYSDR_ERR_ARG; }
-  if (nlines < 0 || nlines > r->max_lines) {
-    set_last_error("pysdr_rtty_decode: nlines %d outside [0, max_lines = %d]", nlines, r->max_lines);
-    return PYSDR_ERR_ARG;
-  }
-  if ((nlines > 0 && !lines) || !codes || !t || !snr2 || !n_dec || !ndet) {
-    set_last_error("pysdr_rtty_decode: NULL lines, codes, t, snr2, n_dec or ndet");
-    return PYSDR_ERR_ARG;
-  }
-  *n_dec = 0;
-  if (nlines == 0) return PYSDR_OK;
-  PYSDR_HIP_CHECK(hipSetDevice(r->device));
-  hipStream_t st = r->stream;
-  const long long n0 = r->n + 1, n1 = r->n + nlines;                 // lines n0..n1
-  const long long j_first = r->n / kM + 1, j_last = n1 / kM;         // decisions at n = 30 j
-  const int nd = (int)(j_last - j_first + 1);                        // <= nlines / 30 + 1 = max_dec
-  const float* src = lines;
-  if (!on_device) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(r->d_lines, lines, (size_t)nlines * r->nfft * sizeof(float), hipMemcpyHostToDevice, st));
-    src = r->d_lines;
-  }
-  const int gb = (r->nb + 255) / 256;
-  const int moff = r->bin_lo - r->band_lo;
-  hipLaunchKernelGGL(rt_gather, dim3((r->nband + 255) / 256, nlines), dim3(256), 0, st, src, r->nfft, flipped ? 1 : 0,
-                     r->band_lo, r->nband, n0, r->R, r->d_band);
-  hipLaunchKernelGGL(rt_s4, dim3(gb, nlines), dim3(256), 0, st, r->d_band, r->nband, moff, r->nsh, r->nb, n0, r->R, r->d_s4);
-  hipLaunchKernelGGL(rt_best, dim3(gb, nlines), dim3(256), 0, st, r->d_s4, r->nb, n0, r->R, r->d_best, r->d_isym);
-  hipLaunchKernelGGL(rt_sc2, dim3(gb, nlines), dim3(256), 0, st, r->d_best, r->nb, n0, r->R, r->d_sc2);
-  if (nd > 0) {
-    hipLaunchKernelGGL(rt_decide, dim3(gb, nd), dim3(256), 0, st, r->d_band, r->d_sc2, r->d_isym, r->nband, moff, r->nsh,
-                       r->nb, j_first * kM, r->R, r->d_t, r->d_snr, r->d_held);
-    hipLaunchKernelGGL(rt_emit, dim3(gb), dim3(256), 0, st, r->d_snr, r->d_held, r->nb, nd, r->d_shift, r->d_code);
-  }
-  hipLaunchKernelGGL(rt_find, dim3(nlines), dim3(256), 0, st, r->d_band, r->nband, r->find_lo - r->band_lo,
-                     r->find_hi - r->band_lo, r->nsh, n0, r->R, r->d_ndet);
+  hipLaunchKernelGGL(rt_find, dim3(a.nlines), dim3(256), 0, st, a.band, a.nband, a.flo, a.fhi, a.nsh, a.n0, a.R, a.ndet);
   PYSDR_HIP_CHECK(hipGetLastError());
-  const size_t dn = (size_t)nd * r->nb;
-  if (nd > 0) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(codes, r->d_code, dn * sizeof(int), hipMemcpyDeviceToHost, st));
-    PYSDR_HIP_CHECK(hipMemcpyAsync(t, r->d_t, dn * sizeof(long long), hipMemcpyDeviceToHost, st));
-    PYSDR_HIP_CHECK(hipMemcpyAsync(snr2, r->d_snr, dn * sizeof(double), hipMemcpyDeviceToHost, st));
-  }
-  PYSDR_HIP_CHECK(hipMemcpyAsync(ndet, r->d_ndet, (size_t)nlines * sizeof(int), hipMemcpyDeviceToHost, st));
-  // the per-line rows of the call: ring rows n0 % R .., in at most two pieces
-  const int r0 = (int)(n0 % r->R);
-  const int first = nlines < r->R - r0 ? nlines : r->R - r0;
-  const size_t w = (size_t)r->nb;
-  if (isym) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(isym, r->d_isym + r0 * w, first * w * sizeof(int), hipMemcpyDeviceToHost, st));
-    if (first < nlines)
-      PYSDR_HIP_CHECK(hipMemcpyAsync(isym + first * w, r->d_isym, (nlines - first) * w * sizeof(int), hipMemcpyDeviceToHost, st));
-  }
-  if (best) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(best, r->d_best + r0 * w, first * w * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (first < nlines)
-      PYSDR_HIP_CHECK(hipMemcpyAsync(best + first * w, r->d_best, (nlines - first) * w * sizeof(float), hipMemcpyDeviceToHost, st));
-  }
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  r->n = n1;
-  *n_dec = nd;
   return PYSDR_OK;
 }
 
-}  // extern "C"
+}  // namespace pysdr

@@ -7,26 +7,10 @@
 //   roll   wf = np.roll(wf, -nbins, axis=0)
 //   image  bkgnd = median(mean(wf[:, -cnt:], 1));  zz = wf[0:npsd, :] - bkgnd  (npsd = length of the
 //          line just pushed);  img = max(zz, nanmax(zz) - PAN_DR)
-#include "common.h"
-
-struct pysdr_waterfall {
-  int device = 0, nfft = 0, ncols = 0;
-  int head = 0;        // slot that receives the next line (= oldest column)
-  int cnt = 0;         // valid columns (wf_cnt, Plotting.py:545-546)
-  int shift = 0;       // accumulated retune roll: logical bin i lives at (i + shift) mod nfft
-  float* d_wf = nullptr;     // [ncols][nfft]
-  float* d_line = nullptr;   // staging for host lines
-  float* d_mean = nullptr;   // [nfft]
-  float* d_stat = nullptr;   // [0] bkgnd, [1] max(wf)
-  float* d_image = nullptr;  // [ncols][nfft]
-  int* d_pk = nullptr;       // peak pick scratch: [3][nfft / 2 + 2] positions, states, kept indices; + [1] the count
-  hipStream_t stream = nullptr;
-};
+#include "objects_plan.h"
 
 namespace pysdr {
 namespace {
-
-constexpr float kFill = -1.0e38f;    // Plotting.py:385
 
 __global__ __launch_bounds__(256) void wf_fill_kernel(float* p, size_t n, float v) {
   for (size_t i = blockIdx.x * 256ull + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = v;
@@ -262,128 +246,40 @@ __global__ __launch_bounds__(1024) void wf_peaks_kernel(const float* __restrict_
 }
 
 }  // namespace
+
+int launch_wf_fill(float* p, size_t n, float v, hipStream_t st) {
+  hipLaunchKernelGGL(wf_fill_kernel, dim3(1024), dim3(256), 0, st, p, n, v);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
+int launch_wf_push(const float* line, int n, int nfft, int shift, float* slot, hipStream_t st) {
+  hipLaunchKernelGGL(wf_push_kernel, dim3((nfft + 255) / 256), dim3(256), 0, st, line, n, nfft, shift, slot);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
+int launch_wf_mean_median(const WfArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(wf_mean_kernel, dim3((a.nfft + 255) / 256), dim3(256), 0, st, a.wf, a.nfft, a.ncols, a.head, a.cnt, a.shift,
+                     a.mean);
+  hipLaunchKernelGGL(wf_median_kernel, dim3(1), dim3(1024), 0, st, a.mean, a.nfft, a.stat);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
+int launch_wf_max_image(const WfArgs& a, int npsd, float pan_dr, hipStream_t st) {
+  hipLaunchKernelGGL(wf_max_kernel, dim3(512), dim3(256), 0, st, a.wf, a.nfft, a.ncols, a.shift, npsd,
+                     reinterpret_cast<unsigned*>(a.stat + 1));
+  hipLaunchKernelGGL(wf_image_kernel, dim3((a.nfft + 255) / 256, a.ncols), dim3(256), 0, st, a.wf, a.nfft, a.ncols, a.head, a.shift,
+                     a.stat, pan_dr, a.image);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
+int launch_wf_peaks(const float* x, int n, double height, int dist, int* pos, int* state, int* kept, int* count, hipStream_t st) {
+  hipLaunchKernelGGL(wf_peaks_kernel, dim3(1), dim3(1024), 0, st, x, n, height, dist, pos, state, kept, count);
+  PYSDR_HIP_CHECK(hipGetLastError());
+  return PYSDR_OK;
+}
+
 }  // namespace pysdr
-
-using namespace pysdr;
-
-extern "C" {
-
-int pysdr_waterfall_create(int device, int nfft, int ncols, pysdr_waterfall** out) {
-  if (!out || nfft < 2 || ncols < 1) return PYSDR_ERR_ARG;
-  hipError_t e0 = hipSetDevice(device);
-  if (e0 != hipSuccess) { set_last_error("hipSetDevice(%d): %s", device, hipGetErrorString(e0)); return PYSDR_ERR_NO_DEVICE; }
-  pysdr_waterfall* w = new pysdr_waterfall();
-  w->device = device; w->nfft = nfft; w->ncols = ncols;
-  const size_t n = (size_t)nfft * ncols;
-#define CK(e) do { hipError_t _e = (e); if (_e != hipSuccess) { set_last_error("pysdr_waterfall_create: %s -> %s", #e, hipGetErrorString(_e)); pysdr_waterfall_destroy(w); return PYSDR_ERR_HIP; } } while (0)
-  CK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-  CK(hipMalloc(&w->d_wf, n * sizeof(float)));
-  CK(hipMalloc(&w->d_image, n * sizeof(float)));
-  CK(hipMalloc(&w->d_line, (size_t)nfft * sizeof(float)));
-  CK(hipMalloc(&w->d_mean, (size_t)nfft * sizeof(float)));
-  CK(hipMalloc(&w->d_stat, 4 * sizeof(float)));
-  CK(hipMalloc(&w->d_pk, (3 * ((size_t)nfft / 2 + 2) + 1) * sizeof(int)));
-#undef CK
-  hipLaunchKernelGGL(wf_fill_kernel, dim3(1024), dim3(256), 0, w->stream, w->d_wf, n, kFill);
-  if (hipStreamSynchronize(w->stream) != hipSuccess) { pysdr_waterfall_destroy(w); return PYSDR_ERR_HIP; }
-  *out = w;
-  return PYSDR_OK;
-}
-
-void pysdr_waterfall_destroy(pysdr_waterfall* w) {
-  if (!w) return;
-  (void)hipSetDevice(w->device);
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
-  if (w->d_wf) (void)hipFree(w->d_wf);
-  if (w->d_image) (void)hipFree(w->d_image);
-  if (w->d_line) (void)hipFree(w->d_line);
-  if (w->d_mean) (void)hipFree(w->d_mean);
-  if (w->d_stat) (void)hipFree(w->d_stat);
-  if (w->d_pk) (void)hipFree(w->d_pk);
-  if (w->stream) (void)hipStreamDestroy(w->stream);
-  delete w;
-}
-
-int pysdr_waterfall_push(pysdr_waterfall* w, const float* line, int n, int on_device) {
-  if (!w || !line || n < 0 || n > w->nfft) return PYSDR_ERR_ARG;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  const float* src = line;
-  if (!on_device) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_line, line, (size_t)n * sizeof(float), hipMemcpyHostToDevice, w->stream));
-    src = w->d_line;
-  }
-  hipLaunchKernelGGL(wf_push_kernel, dim3((w->nfft + 255) / 256), dim3(256), 0, w->stream, src, n, w->nfft,
-                     w->shift, w->d_wf + (size_t)w->head * w->nfft);
-  PYSDR_HIP_CHECK(hipGetLastError());
-  if (!on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));   // the caller may reuse `line`
-  w->head = (w->head + 1) % w->ncols;
-  if (w->cnt < w->ncols) w->cnt++;
-  return PYSDR_OK;
-}
-
-int pysdr_waterfall_roll(pysdr_waterfall* w, int nbins) {
-  if (!w) return PYSDR_ERR_ARG;
-  long s = ((long)w->shift + nbins) % w->nfft;
-  if (s < 0) s += w->nfft;
-  w->shift = (int)s;
-  return PYSDR_OK;
-}
-
-int pysdr_waterfall_image_rows(pysdr_waterfall* w, float pan_dr, int npsd, float* image_out, float* mean_out,
-                               float* bkgnd_out) {
-  if (!w || npsd < 1 || npsd > w->nfft) return PYSDR_ERR_ARG;
-  if (w->cnt < 1) { set_last_error("pysdr_waterfall_image: no line pushed yet"); return PYSDR_ERR_STATE; }
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  const int gx = (w->nfft + 255) / 256;
-  const size_t n = (size_t)w->nfft * w->ncols;
-  hipLaunchKernelGGL(wf_mean_kernel, dim3(gx), dim3(256), 0, w->stream, w->d_wf, w->nfft, w->ncols, w->head,
-                     w->cnt, w->shift, w->d_mean);
-  hipLaunchKernelGGL(wf_median_kernel, dim3(1), dim3(1024), 0, w->stream, w->d_mean, w->nfft, w->d_stat);
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_stat + 1, 0, sizeof(float), w->stream));
-  hipLaunchKernelGGL(wf_max_kernel, dim3(512), dim3(256), 0, w->stream, w->d_wf, w->nfft, w->ncols, w->shift, npsd,
-                     reinterpret_cast<unsigned*>(w->d_stat + 1));
-  hipLaunchKernelGGL(wf_image_kernel, dim3(gx, w->ncols), dim3(256), 0, w->stream, w->d_wf, w->nfft, w->ncols,
-                     w->head, w->shift, w->d_stat, pan_dr, w->d_image);
-  PYSDR_HIP_CHECK(hipGetLastError());
-  if (image_out) PYSDR_HIP_CHECK(hipMemcpyAsync(image_out, w->d_image, n * sizeof(float), hipMemcpyDeviceToHost, w->stream));
-  if (mean_out) PYSDR_HIP_CHECK(hipMemcpyAsync(mean_out, w->d_mean, (size_t)w->nfft * sizeof(float), hipMemcpyDeviceToHost, w->stream));
-  if (bkgnd_out) PYSDR_HIP_CHECK(hipMemcpyAsync(bkgnd_out, w->d_stat, sizeof(float), hipMemcpyDeviceToHost, w->stream));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
-  return PYSDR_OK;
-}
-
-int pysdr_waterfall_peaks(pysdr_waterfall* w, const float* line, int n, double height, int distance, int* idx_out, int cap,
-                          int* n_out) {
-  if (!w || !n_out || n < 0 || n > w->nfft || distance < 1 || cap < 0 || (cap > 0 && !idx_out)) return PYSDR_ERR_ARG;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  const float* x = w->d_mean;
-  if (line) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_line, line, (size_t)n * sizeof(float), hipMemcpyHostToDevice, w->stream));
-    x = w->d_line;
-  } else if (w->cnt < 1) {
-    set_last_error("pysdr_waterfall_peaks: no averaged line yet (pysdr_waterfall_image first, or pass a line)");
-    return PYSDR_ERR_STATE;
-  }
-  const size_t half = (size_t)w->nfft / 2 + 2;
-  int* pos = w->d_pk, *state = w->d_pk + half, *kept = w->d_pk + 2 * half, *count = w->d_pk + 3 * half;
-  hipLaunchKernelGGL(wf_peaks_kernel, dim3(1), dim3(1024), 0, w->stream, x, n, height, distance, pos, state, kept, count);
-  PYSDR_HIP_CHECK(hipGetLastError());
-  int np_ = 0;
-  PYSDR_HIP_CHECK(hipMemcpyAsync(&np_, count, sizeof(int), hipMemcpyDeviceToHost, w->stream));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
-  *n_out = np_;
-  const int m = np_ < cap ? np_ : cap;
-  if (m > 0) {
-    PYSDR_HIP_CHECK(hipMemcpyAsync(idx_out, kept, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, w->stream));
-    PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
-  }
-  return PYSDR_OK;
-}
-
-int pysdr_waterfall_image(pysdr_waterfall* w, float pan_dr, float* image_out, float* mean_out,
-                          float* bkgnd_out) {
-  if (!w) return PYSDR_ERR_ARG;
-  return pysdr_waterfall_image_rows(w, pan_dr, w->nfft, image_out, mean_out, bkgnd_out);
-}
-
-}  // extern "C"

@@ -8,7 +8,7 @@ decoder compares (``rtty.py:485-492``).
 
 ``RTTY_Decoders`` is the reference's bank of Baudot decoders (``RTTY_Decoder``, ``rtty.py:431-701``)
 and its signal finder (``find_sigs``, ``:744-764``) on the GPU, one decoder on every bin of a range
-(``rtty.hip``); ``RTTY_Skimmer`` hands the filterbank's device lines to it without a download."""
+(kernels ``rtty.hip``, host half ``api_objects.hip``); ``RTTY_Skimmer`` hands the filterbank's device lines to it without a download."""
 from __future__ import annotations
 
 import ctypes as C

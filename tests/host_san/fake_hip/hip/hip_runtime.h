@@ -1,7 +1,7 @@
 // A HIP runtime made of the host heap, for the sanitizer build of the HOST half of libpysdr_hip.so
 // (tests/host_san): "device" memory is malloc'ed (so AddressSanitizer sees every size the host code
 // passes to a copy or to a kernel), copies are memcpy, streams and events complete at once.  Only the
-// calls pysdr_amd/csrc/api.hip makes exist.  Nothing here is part of the product.
+// calls pysdr_amd/csrc/api.hip and api_objects.hip make exist.  Nothing here is part of the product.
 //   HOST_SAN_TRACE=<file>    one line per stream-ordered operation (copies, fills, event records, waits, synchronises; the
 //                            launch layer adds its launches).  Streams, events and allocations are named by the order in
 //                            which the TRACE first meets them (+ byte offset), never by address or creation order: allocating
@@ -146,6 +146,15 @@ inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind k) {
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) {
   if (fake_hip::tracing()) fake_hip::Line("memcpy_async").st(st).i(fake_kind(k), (long long)n).p("dst", d).p("src", s);
   std::memmove(d, s, n);
+  return hipSuccess;
+}
+// row by row: AddressSanitizer sees both pitches
+inline hipError_t hipMemcpy2DAsync(void* d, size_t dpitch, const void* s, size_t spitch, size_t width, size_t height, hipMemcpyKind k,
+                                   hipStream_t st = nullptr) {
+  if (fake_hip::tracing())
+    fake_hip::Line("memcpy2d_async").st(st).i(fake_kind(k), (long long)width).i("height", (long long)height).i("dpitch", (long long)dpitch)
+        .i("spitch", (long long)spitch).p("dst", d).p("src", s);
+  for (size_t r = 0; r < height; ++r) std::memmove(static_cast<char*>(d) + r * dpitch, static_cast<const char*>(s) + r * spitch, width);
   return hipSuccess;
 }
 inline hipError_t hipMemset(void* d, int v, size_t n) {

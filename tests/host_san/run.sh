@@ -8,7 +8,7 @@ HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(cd "$HERE/../.." && pwd)
 OUT=${HOST_SAN_OUT:-/tmp/pysdr_host_san}
 mkdir -p "$OUT"
-SRC="$ROOT/pysdr_amd/csrc/api.hip $HERE/stub_kernels.cpp $HERE/san_main.cpp"
+SRC="$ROOT/pysdr_amd/csrc/api.hip $ROOT/pysdr_amd/csrc/api_objects.hip $HERE/stub_kernels.cpp $HERE/san_main.cpp"
 INC="-I$HERE/fake_hip -I$ROOT/pysdr_amd/csrc"
 build() { # name, flags...
   local name=$1; shift

@@ -7,6 +7,8 @@
 // planner (pysdr_amd/csrc/mixdec_plan.h) is also swept directly over every shape, tile override and thread count, and the
 // plans of the two serial loops (pysdr_amd/csrc/host_plan.h) over rates, call lengths and tunings.  `san_main allocfail`
 // runs a short scenario over every object kind with the n-th allocation / event / stream creation failing, n = 1, 2, ...
+// The four stream objects of api_objects.hip (waterfall, RTTY decoder bank, channelizer, channel bank) have a scenario each,
+// part of the default run; `san_main objects` runs those four alone (their queue trace on its own).
 //   build + run: tests/host_san/run.sh   (tests/test_host_sanitizers.py does that)
 #include <atomic>
 #include <cmath>
@@ -380,6 +382,305 @@ static void pll_plan_sweep() {
   std::printf("pll plan sweep: %d plans\n", nplans);
 }
 
+// ---- the four stream objects (pysdr_amd/csrc/api_objects.hip): `san_main objects` runs these alone
+static int g_obj_calls = 0;
+struct DevMem {              // device memory of the harness's own, freed at scope end
+  void* p = nullptr;
+  explicit DevMem(size_t bytes) { OK(pysdr_dev_alloc(0, bytes ? bytes : 1, &p)); std::memset(p, 0, bytes); }
+  ~DevMem() { OK(pysdr_dev_free(0, p)); }
+};
+
+static void channelizer_scenario(int M, int D, int k_first, int nk, int max_taps, int max_in) {
+  pysdr_chan* c = nullptr;
+  OK(pysdr_chan_create(0, M, D, k_first, nk, max_taps, max_in, &c));
+  const long long pitch = max_in / D + 2;
+  std::vector<float> x(2 * (size_t)max_in, 0.25f), y(2 * (size_t)nk * pitch);
+  DevMem dx(8 * (size_t)max_in), dy(8 * (size_t)nk * (pitch + 3));
+  int nf = 0;
+  FAILS(pysdr_chan_process(c, x.data(), 1, 0, y.data(), pitch, 0, &nf));                 // no taps yet
+  auto h = taps(max_taps);
+  FAILS(pysdr_chan_set_taps(c, h.data(), 0));
+  FAILS(pysdr_chan_set_taps(c, h.data(), max_taps + 1));
+  FAILS(pysdr_chan_set_taps(c, nullptr, 1));
+  FAILS(pysdr_chan_set_taps(nullptr, h.data(), 1));
+  OK(pysdr_chan_set_taps(c, h.data(), max_taps));
+  unsigned long long s = 0;
+  auto run = [&](int n, int in_dev, int out_dev) {
+    const int want = (int)((s + n + D - 1) / D - (s + D - 1) / D);
+    OK(pysdr_chan_process(c, in_dev ? dx.p : (void*)x.data(), n, in_dev, out_dev ? dy.p : (void*)y.data(), out_dev ? pitch + 3 : pitch, out_dev, &nf));
+    if (nf != want) { std::fprintf(stderr, "channelizer: %d outputs, %d expected\n", nf, want); std::exit(1); }
+    s += n; ++g_obj_calls;
+  };
+  for (int combo = 0; combo < 4; ++combo)                 // host / device input x host / device output: both lazy staging buffers
+    for (int n : {0, 1, D - 1, D, D + 1, max_in, 7, max_in - 1}) run(n, combo & 1, combo >> 1);
+  OK(pysdr_chan_set_taps(c, h.data(), M - 3));            // a shorter prototype: one tap row
+  run(max_in, 0, 0); run(3, 1, 1);
+  OK(pysdr_chan_reset(c)); s = 0;
+  run(D + 1, 0, 1); run(max_in, 1, 0);
+  OK(pysdr_chan_sync(c));
+  FAILS(pysdr_chan_process(c, x.data(), max_in + 1, 0, y.data(), pitch, 0, &nf));        // over capacity
+  FAILS(pysdr_chan_process(c, x.data(), -1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, nullptr, 1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, x.data(), 1, 0, y.data(), pitch, 0, nullptr));
+  FAILS(pysdr_chan_process(nullptr, x.data(), 1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, x.data(), 2 * D, 0, nullptr, pitch, 0, &nf));              // outputs and nowhere to put them
+  FAILS(pysdr_chan_process(c, x.data(), 2 * D, 0, y.data(), 1, 0, &nf));                 // pitch too small
+  run(2 * D, 0, 0);                                                                      // ... and none of them moved the stream
+  FAILS(pysdr_chan_reset(nullptr));
+  FAILS(pysdr_chan_sync(nullptr));
+  pysdr_chan_destroy(c);
+  pysdr_chan_destroy(nullptr);
+}
+
+static void channelizer_errors() {
+  int32_t pl[16];
+  pysdr_chan* c = nullptr;
+  OK(pysdr_chan_plan(16, 4, 64, 0, 16, pl));
+  FAILS(pysdr_chan_plan(16, 4, 64, 0, 16, nullptr));
+  FAILS(pysdr_chan_plan(15, 5, 64, 0, 1, pl));            // M < 16
+  FAILS(pysdr_chan_plan(8192, 8192, 64, 0, 1, pl));
+  FAILS(pysdr_chan_plan(48, 48, 64, 0, 1, pl));           // a factor 3
+  FAILS(pysdr_chan_plan(16, 3, 64, 0, 1, pl));            // D does not divide M
+  FAILS(pysdr_chan_plan(16, 0, 64, 0, 1, pl));
+  FAILS(pysdr_chan_plan(16, 2, 64, 0, 1, pl));            // M / D = 8
+  FAILS(pysdr_chan_plan(16, 4, 0, 0, 1, pl));
+  FAILS(pysdr_chan_plan(16, 4, 16 * 16 + 1, 0, 1, pl));
+  FAILS(pysdr_chan_plan(16, 4, 64, -1, 1, pl));
+  FAILS(pysdr_chan_plan(16, 4, 64, 16, 1, pl));
+  FAILS(pysdr_chan_plan(16, 4, 64, 0, 0, pl));
+  FAILS(pysdr_chan_plan(16, 4, 64, 0, 17, pl));
+  FAILS(pysdr_chan_create(0, 16, 4, 0, 16, 64, 100, nullptr));
+  FAILS(pysdr_chan_create(0, 16, 2, 0, 16, 64, 100, &c));
+  FAILS(pysdr_chan_create(0, 16, 4, 0, 16, 64, 0, &c));
+  FAILS(pysdr_chan_create(0, 16, 4, 0, 16, 64, (1 << 28) + 1, &c));
+  FAILS(pysdr_chan_create(1, 16, 4, 0, 16, 64, 100, &c));  // no such device
+  if (c) { std::fprintf(stderr, "a failed pysdr_chan_create left a handle\n"); std::exit(1); }
+}
+
+static void bank_scenario(int mode, int ntaps_af) {
+  const int M = 16, D = 4, nk = 5, max_in = 2049 * D + 3;
+  pysdr_chan* ch = nullptr;
+  OK(pysdr_chan_create(0, M, D, 13, nk, 2 * M, max_in, &ch));      // rows 13, 14, 15, 0, 1
+  auto h = taps(2 * M);
+  OK(pysdr_chan_set_taps(ch, h.data(), 2 * M));
+  pysdr_bank* b = nullptr;
+  OK(pysdr_bank_create(ch, 12000.0, mode, ntaps_af, &b));
+  const long long cap = 2049 + 8;
+  std::vector<float> x(2 * (size_t)max_in, 0.25f), am((size_t)nk * cap), iq(2 * (size_t)nk * cap);
+  DevMem dx(8 * (size_t)max_in), dam(4 * (size_t)nk * cap);
+  int nf = 0;
+  FAILS(pysdr_bank_process(b, x.data(), D, 0, am.data(), cap, 0, &nf));                  // no mode set
+  auto af = taps(ntaps_af);
+  FAILS(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af + 1));
+  FAILS(pysdr_bank_set_mode(b, PYSDR_USB, af.data(), ntaps_af));
+  FAILS(pysdr_bank_set_mode(b, mode, nullptr, ntaps_af));
+  FAILS(pysdr_bank_set_mode(nullptr, mode, af.data(), ntaps_af));
+  OK(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af));
+  unsigned long long s = 0;
+  // am: 0 none, 1 host at pitch n_out, 2 device at pitch n_out, 3 device at a wider pitch
+  auto run = [&](int n, int in_dev, int how) {
+    const int want = (int)((s + n + D - 1) / D - (s + D - 1) / D);
+    float* out = how == 0 ? nullptr : how == 1 ? am.data() : (float*)dam.p;
+    OK(pysdr_bank_process(b, in_dev ? dx.p : (void*)x.data(), n, in_dev, out, how == 3 ? want + 5 : want, how >= 2, &nf));
+    if (nf != want) { std::fprintf(stderr, "bank: %d outputs, %d expected\n", nf, want); std::exit(1); }
+    s += n; ++g_obj_calls;
+  };
+  const int rows_run[] = {0, 1, 2}, rows_far[] = {4, 0, 2}, rows_rep[] = {1, 1, 3, 4, 4};
+  auto fetches = [&] {
+    OK(pysdr_bank_fetch(b, rows_run, 3, am.data(), iq.data(), nf + 1));
+    OK(pysdr_bank_fetch(b, rows_far, 3, am.data(), nullptr, nf));
+    OK(pysdr_bank_fetch(b, rows_rep, 5, nullptr, iq.data(), cap));
+    OK(pysdr_bank_fetch(b, rows_rep, 5, nullptr, nullptr, cap));
+    OK(pysdr_bank_fetch(b, nullptr, 0, am.data(), iq.data(), cap));
+    if (nf > 0) FAILS(pysdr_bank_fetch(b, rows_run, 3, am.data(), iq.data(), nf - 1));   // pitch too small
+  };
+  for (int pass = 0; pass < 4; ++pass) {
+    // from s = 0 (mod D): 1 output, 0 outputs, exactly one tile, one more than a tile, nothing at all
+    int k = pass;
+    for (int n : {1, 1, 2048 * D, 2049 * D, 0, D - 2}) { run(n, k & 1, k & 3); fetches(); ++k; }
+    if (pass == 1) { OK(pysdr_bank_set_squelch(b, 0.5f)); OK(pysdr_bank_set_agc(b, 0, 0.3f)); }
+    if (pass == 2) {                                      // the other mode and back, then from the start
+      OK(pysdr_bank_set_mode(b, mode == PYSDR_AM ? PYSDR_NFM : PYSDR_AM, af.data(), ntaps_af));
+      run(2049 * D, 0, 1); fetches();
+      OK(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af));
+      OK(pysdr_bank_reset(b)); s = 0;
+      OK(pysdr_bank_set_agc(b, 1, 0.5f));
+    }
+  }
+  std::vector<float> agc(nk), gain(nk), mx(nk), lvl(nk);
+  std::vector<uint8_t> open(nk);
+  OK(pysdr_bank_state(b, agc.data(), gain.data(), mx.data(), lvl.data(), open.data()));
+  OK(pysdr_bank_state(b, nullptr, gain.data(), nullptr, nullptr, nullptr));
+  OK(pysdr_bank_sync(b));
+  // errors that must leave the stream where it was
+  FAILS(pysdr_bank_process(b, x.data(), 8 * D, 0, am.data(), 7, 0, &nf));                // pitch too small
+  FAILS(pysdr_bank_process(b, x.data(), max_in + 1, 0, am.data(), cap, 0, &nf));
+  FAILS(pysdr_bank_process(b, x.data(), -1, 0, am.data(), cap, 0, &nf));
+  FAILS(pysdr_bank_process(b, nullptr, 1, 0, am.data(), cap, 0, &nf));
+  FAILS(pysdr_bank_process(b, x.data(), 1, 0, am.data(), cap, 0, nullptr));
+  run(8 * D, 0, 1);
+  // The channelizer fed beside its bank, between two bank calls: the bank reads the channelizer's sample count before
+  // each call, so its next call is sized right (its rows' history has a gap: the caller's business).  The error itself
+  // needs the direct call to land between that read and the bank's own channelizer call -- another thread.
+  {
+    std::vector<float> y(2 * (size_t)nk * 16);
+    int n2 = 0;
+    OK(pysdr_chan_process(ch, x.data(), 3 * D + 1, 0, y.data(), 16, 0, &n2));
+    s += 3 * D + 1;
+    run(5 * D, 0, 1); fetches();
+  }
+  const int bad_rows[] = {0, nk};
+  FAILS(pysdr_bank_fetch(b, bad_rows, 2, am.data(), nullptr, cap));
+  FAILS(pysdr_bank_fetch(b, rows_run, -1, am.data(), nullptr, cap));
+  FAILS(pysdr_bank_fetch(b, nullptr, 1, am.data(), nullptr, cap));
+  FAILS(pysdr_bank_fetch(nullptr, rows_run, 1, am.data(), nullptr, cap));
+  FAILS(pysdr_bank_set_agc(b, 1, 0.f));
+  FAILS(pysdr_bank_set_agc(nullptr, 1, 0.5f));
+  FAILS(pysdr_bank_set_squelch(b, -1.f));
+  FAILS(pysdr_bank_set_squelch(nullptr, 0.f));
+  FAILS(pysdr_bank_state(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  FAILS(pysdr_bank_reset(nullptr));
+  FAILS(pysdr_bank_sync(nullptr));
+  pysdr_bank_destroy(b);
+  pysdr_bank_destroy(nullptr);
+  // create and plan errors
+  int32_t pl[8];
+  b = nullptr;
+  OK(pysdr_bank_plan(nk, ntaps_af, 2049, pl));
+  FAILS(pysdr_bank_plan(nk, ntaps_af, 2049, nullptr));
+  FAILS(pysdr_bank_plan(0, ntaps_af, 2049, pl));
+  FAILS(pysdr_bank_plan(4097, ntaps_af, 2049, pl));
+  FAILS(pysdr_bank_plan(nk, 2, 2049, pl));
+  FAILS(pysdr_bank_plan(nk, 256, 2049, pl));
+  FAILS(pysdr_bank_plan(nk, ntaps_af, 0, pl));
+  FAILS(pysdr_bank_create(ch, 12000.0, mode, ntaps_af, nullptr));
+  FAILS(pysdr_bank_create(nullptr, 12000.0, mode, ntaps_af, &b));
+  FAILS(pysdr_bank_create(ch, 12000.0, PYSDR_CW, ntaps_af, &b));
+  FAILS(pysdr_bank_create(ch, 0.0, mode, ntaps_af, &b));
+  FAILS(pysdr_bank_create(ch, 12000.0, mode, 2, &b));
+  FAILS(pysdr_bank_create(ch, 12000.0, mode, 256, &b));
+  if (b) { std::fprintf(stderr, "a failed pysdr_bank_create left a handle\n"); std::exit(1); }
+  pysdr_chan_destroy(ch);
+}
+
+static void rtty_scenario(int find_lo, int find_hi) {
+  const int nfft = 64, nsh = 5, bin_lo = 10, bin_hi = 30, max_lines = 33, nb = bin_hi - bin_lo;
+  pysdr_rtty* r = nullptr;
+  OK(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, find_lo, find_hi, max_lines, &r));
+  const int R = max_lines + 128, max_dec = max_lines / 30 + 1;
+  std::vector<float> lines((size_t)max_lines * nfft, -80.f), best((size_t)max_lines * nb);
+  DevMem dl(4 * (size_t)max_lines * nfft);
+  std::vector<int> codes((size_t)max_dec * nb), ndet(max_lines), isym((size_t)max_lines * nb);
+  std::vector<long long> t((size_t)max_dec * nb);
+  std::vector<double> snr((size_t)max_dec * nb);
+  long long n = 0, ndec_all = 0;
+  int k = 0, wrapped_with_rows = 0;
+  for (int cycle = 0; cycle < 5; ++cycle) {
+    for (int nl : {0, 1, 29, 30, 31, max_lines}) {
+      const bool want_isym = (k & 4) == 0 || (k % 3) == 0, want_best = (k & 8) == 0, rows = want_isym || want_best, dev = k & 1;   // both, either alone, neither
+      int nd = -1;
+      OK(pysdr_rtty_decode(r, dev ? (const float*)dl.p : lines.data(), nl, dev, (k >> 1) & 1, codes.data(), t.data(), snr.data(), &nd, ndet.data(),
+                           want_isym ? isym.data() : nullptr, want_best ? best.data() : nullptr));
+      const int want = (int)((n + nl) / 30 - n / 30);
+      if (nd != want) { std::fprintf(stderr, "rtty: %d decisions, %d expected\n", nd, want); std::exit(1); }
+      if (rows && nl > 0 && (n + 1) % R + nl > R) ++wrapped_with_rows;                   // the two-piece copies took both pieces
+      n += nl; ndec_all += nd; ++k; ++g_obj_calls;
+    }
+    if (cycle == 2) { OK(pysdr_rtty_reset(r)); n = 0; }
+  }
+  if (wrapped_with_rows < 1) { std::fprintf(stderr, "rtty: the ring never wrapped inside a call that fetched its rows\n"); std::exit(1); }
+  int nd = 0;
+  FAILS(pysdr_rtty_decode(nullptr, lines.data(), 1, 0, 1, codes.data(), t.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_decode(r, lines.data(), -1, 0, 1, codes.data(), t.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_decode(r, lines.data(), max_lines + 1, 0, 1, codes.data(), t.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_decode(r, nullptr, 1, 0, 1, codes.data(), t.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_decode(r, lines.data(), 1, 0, 1, nullptr, t.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_decode(r, lines.data(), 1, 0, 1, codes.data(), t.data(), snr.data(), nullptr, ndet.data(), nullptr, nullptr));
+  FAILS(pysdr_rtty_reset(nullptr));
+  pysdr_rtty_destroy(r);
+  pysdr_rtty_destroy(nullptr);
+  r = nullptr;
+  const int top = nfft - nsh;
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, 0, 0, max_lines, nullptr));
+  FAILS(pysdr_rtty_create(0, 1, 1, 0, 1, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, 0, bin_lo, bin_hi, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nfft, bin_lo, bin_hi, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, -1, bin_hi, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, top + 1, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_hi, bin_hi, 0, 0, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, -1, 5, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, 0, top + 1, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, 9, 8, max_lines, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, 0, 0, 0, &r));
+  FAILS(pysdr_rtty_create(0, nfft, nsh, bin_lo, bin_hi, 0, 0, 32769, &r));
+  FAILS(pysdr_rtty_create(1, nfft, nsh, bin_lo, bin_hi, 0, 0, max_lines, &r));
+  if (r) { std::fprintf(stderr, "a failed pysdr_rtty_create left a handle\n"); std::exit(1); }
+}
+
+static void waterfall_scenario() {
+  const int nfft = 64, ncols = 5;
+  pysdr_waterfall* w = nullptr;
+  OK(pysdr_waterfall_create(0, nfft, ncols, &w));
+  std::vector<float> line(nfft, -70.f), img((size_t)nfft * ncols), mean(nfft);
+  for (int i = 0; i < nfft; ++i) line[i] += (float)((i * 7) % 11);
+  DevMem dl(4 * (size_t)nfft);
+  float bk = 0;
+  int np = 0;
+  std::vector<int> idx(40);
+  FAILS(pysdr_waterfall_image(w, 60.f, img.data(), mean.data(), &bk));                   // before the first push
+  FAILS(pysdr_waterfall_peaks(w, nullptr, nfft, -60.0, 3, idx.data(), 40, &np));
+  OK(pysdr_waterfall_peaks(w, line.data(), nfft, -60.0, 3, idx.data(), 40, &np));       // a passed line needs no push
+  int k = 0;
+  for (int n : {0, 10, nfft, 1, nfft - 1, nfft, 33, nfft}) {                             // more lines than columns
+    OK(pysdr_waterfall_push(w, (k & 1) ? (const float*)dl.p : line.data(), n, k & 1));
+    OK(pysdr_waterfall_roll(w, k == 2 ? 3 : k == 3 ? -7 : k == 4 ? 3 * nfft + 8 : k == 5 ? -2 * nfft - 9 : 0));
+    OK(pysdr_waterfall_image(w, 60.f, img.data(), mean.data(), &bk));
+    OK(pysdr_waterfall_image(w, 60.f, nullptr, mean.data(), &bk));
+    OK(pysdr_waterfall_image(w, 60.f, img.data(), nullptr, &bk));
+    OK(pysdr_waterfall_image(w, 60.f, img.data(), mean.data(), nullptr));
+    OK(pysdr_waterfall_image_rows(w, 60.f, 20, img.data(), mean.data(), &bk));
+    OK(pysdr_waterfall_peaks(w, nullptr, nfft, -60.0, 3, nullptr, 0, &np));              // from the mean, count only
+    OK(pysdr_waterfall_peaks(w, nullptr, nfft, -60.0, 1, idx.data(), 40, &np));
+    OK(pysdr_waterfall_peaks(w, line.data(), 17, -60.0, 2, idx.data(), 3, &np));         // fewer slots than peaks
+    OK(pysdr_waterfall_peaks(w, line.data(), 0, -60.0, 2, idx.data(), 3, &np));
+    ++k; ++g_obj_calls;
+  }
+  FAILS(pysdr_waterfall_push(w, nullptr, 1, 0));
+  FAILS(pysdr_waterfall_push(w, line.data(), -1, 0));
+  FAILS(pysdr_waterfall_push(w, line.data(), nfft + 1, 0));
+  FAILS(pysdr_waterfall_push(nullptr, line.data(), 1, 0));
+  FAILS(pysdr_waterfall_roll(nullptr, 1));
+  FAILS(pysdr_waterfall_image(nullptr, 60.f, img.data(), mean.data(), &bk));
+  FAILS(pysdr_waterfall_image_rows(w, 60.f, 0, img.data(), mean.data(), &bk));
+  FAILS(pysdr_waterfall_image_rows(w, 60.f, nfft + 1, img.data(), mean.data(), &bk));
+  FAILS(pysdr_waterfall_peaks(w, line.data(), nfft + 1, -60.0, 3, idx.data(), 40, &np));
+  FAILS(pysdr_waterfall_peaks(w, line.data(), nfft, -60.0, 0, idx.data(), 40, &np));
+  FAILS(pysdr_waterfall_peaks(w, line.data(), nfft, -60.0, 3, idx.data(), -1, &np));
+  FAILS(pysdr_waterfall_peaks(w, line.data(), nfft, -60.0, 3, nullptr, 4, &np));
+  FAILS(pysdr_waterfall_peaks(w, line.data(), nfft, -60.0, 3, idx.data(), 40, nullptr));
+  pysdr_waterfall_destroy(w);
+  pysdr_waterfall_destroy(nullptr);
+  w = nullptr;
+  FAILS(pysdr_waterfall_create(0, nfft, ncols, nullptr));
+  FAILS(pysdr_waterfall_create(0, 1, ncols, &w));
+  FAILS(pysdr_waterfall_create(0, nfft, 0, &w));
+  FAILS(pysdr_waterfall_create(1, nfft, ncols, &w));
+  if (w) { std::fprintf(stderr, "a failed pysdr_waterfall_create left a handle\n"); std::exit(1); }
+}
+
+static void stream_objects() {
+  g_obj_calls = 0;
+  channelizer_errors();
+  for (int D : {16, 8, 4}) channelizer_scenario(16, D, 11, 9, 3 * 16 + 5, 300 * D + 5);  // rows 11 .. 15, 0 .. 3; more than one workgroup
+  channelizer_scenario(80, 20, 77, 80, 2 * 80, 1000);                                    // 2^4 5: a radix-5 pass, every channel
+  for (int mode : {PYSDR_AM, PYSDR_NFM})
+    for (int ntaps_af : {3, 8, 9, 255}) bank_scenario(mode, ntaps_af);
+  rtty_scenario(0, 0);                                    // finder range empty
+  rtty_scenario(5, 50);                                   // ... and wider than the decoders' on both sides
+  waterfall_scenario();
+  std::printf("stream objects: %d calls\n", g_obj_calls);
+}
+
 // ---- `san_main allocfail`: the n-th hipMalloc / hipHostMalloc / event / stream creation of a run fails (fake_hip).  Every
 // step of the scenario that fails must leave a message, and must succeed when it is simply called again -- a half-built
 // object was destroyed by its create function, a half-added receiver slot is taken over by the next pysdr_rx_add, a
@@ -457,6 +758,31 @@ static void allocfail_scenario() {
   STEP(pysdr_spectrum_create(0, 4096, 8192, 2, win.data(), &sp));
   STEP(pysdr_spectrum_frame(sp, xin.data(), 1, 1, out.data(), &n_out));
   pysdr_spectrum_destroy(sp);
+  // the four stream objects: create + one call + destroy of each
+  pysdr_waterfall* w = nullptr;
+  STEP(pysdr_waterfall_create(0, 64, 5, &w));
+  STEP(pysdr_waterfall_push(w, xin.data(), 64, 0));
+  STEP(pysdr_waterfall_image(w, 60.f, out.data(), nullptr, nullptr));
+  pysdr_waterfall_destroy(w);
+  pysdr_rtty* rt = nullptr;
+  STEP(pysdr_rtty_create(0, 64, 5, 10, 30, 5, 50, 33, &rt));
+  std::vector<int> codes(2 * 20), ndet(33);
+  std::vector<long long> tt(2 * 20);
+  std::vector<double> snr(2 * 20);
+  int nd = 0;
+  STEP(pysdr_rtty_decode(rt, xin.data(), 31, 0, 1, codes.data(), tt.data(), snr.data(), &nd, ndet.data(), nullptr, nullptr));
+  pysdr_rtty_destroy(rt);
+  pysdr_chan* ch = nullptr;
+  STEP(pysdr_chan_create(0, 16, 4, 13, 5, 32, 400, &ch));
+  OK(pysdr_chan_set_taps(ch, h.data(), 32));
+  STEP(pysdr_chan_process(ch, xin.data(), 400, 0, out.data(), 128, 0, &nd));             // both lazy staging buffers
+  if (nd != 100) { std::fprintf(stderr, "channelizer: %d outputs after the injected failure\n", nd); std::exit(1); }
+  pysdr_bank* bk = nullptr;
+  STEP(pysdr_bank_create(ch, 12000.0, PYSDR_NFM, 9, &bk));
+  OK(pysdr_bank_set_mode(bk, PYSDR_NFM, h.data(), 9));
+  STEP(pysdr_bank_process(bk, xin.data(), 400, 0, out.data(), 128, 0, &nd));
+  pysdr_bank_destroy(bk);
+  pysdr_chan_destroy(ch);
 }
 
 static void allocfail() {
@@ -510,6 +836,34 @@ static void race() {
   stop.store(true);
   knobs.join();
   pysdr_destroy(c);
+  // the two stream objects that lock: one thread feeds the bank, another turns its knobs and waits on the borrowed channelizer
+  pysdr_chan* ch = nullptr;
+  OK(pysdr_chan_create(0, 16, 4, 13, 5, 32, 1024, &ch));
+  OK(pysdr_chan_set_taps(ch, h.data(), 32));
+  pysdr_bank* b = nullptr;
+  OK(pysdr_bank_create(ch, 12000.0, PYSDR_NFM, 9, &b));
+  OK(pysdr_bank_set_mode(b, PYSDR_NFM, h.data(), 9));
+  stop.store(false);
+  std::thread bank_knobs([&] {
+    float g[5];
+    uint8_t open[5];
+    for (int k = 0; !stop.load(); ++k) {
+      OK(pysdr_bank_set_agc(b, k & 1, 0.5f));
+      OK(pysdr_bank_set_squelch(b, (k & 2) ? 0.1f : 0.0f));
+      OK(pysdr_bank_state(b, nullptr, g, nullptr, nullptr, open));
+      OK(pysdr_bank_sync(b));
+      OK(pysdr_chan_sync(ch));
+    }
+  });
+  std::vector<float> am(5 * 256);
+  for (int it = 0; it < 300; ++it) {
+    int nf = 0;
+    OK(pysdr_bank_process(b, x.data(), 1024 - (it % 5), 0, am.data(), 256, 0, &nf));
+  }
+  stop.store(true);
+  bank_knobs.join();
+  pysdr_bank_destroy(b);
+  pysdr_chan_destroy(ch);
 }
 
 int main(int argc, char** argv) {
@@ -522,12 +876,17 @@ int main(int argc, char** argv) {
     allocfail();
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "objects") == 0) {
+    stream_objects();
+    return 0;
+  }
   int ndev = 0;
   OK(pysdr_device_count(&ndev));
   FAILS(pysdr_create(nullptr, nullptr));
   FAILS(pysdr_set_overlap(nullptr, 1));
   planner_sweep();
   pll_plan_sweep();
+  stream_objects();
   for (int pass = 0; pass < 3; ++pass) {
   g_overlap = pass == 0 ? 0 : (pass == 1 ? 2 : 1);
   for (const Rate& r : kRates) {

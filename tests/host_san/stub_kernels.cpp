@@ -1,5 +1,5 @@
 // The launch layer of libpysdr_hip.so for the sanitizer build of its HOST half (tests/host_san):
-// every launch_* that api.hip calls, as a host function that
+// every launch_* that api.hip and api_objects.hip call, as a host function that
 //   * reads every input element and writes every output element the real kernel is entitled to touch
 //     (the "device" memory is malloc'ed by the fake HIP runtime, so AddressSanitizer checks the sizes and
 //     offsets the host code computed: capacities, history prefixes, strides of the per-block arrays);
@@ -20,6 +20,7 @@
 #include "mixdec_geom.h"
 #include "mixdec_mfma_geom.h"
 #include "mixdec_plan.h"
+#include "objects_plan.h"
 
 namespace pysdr {
 
@@ -498,6 +499,223 @@ int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, fl
   for (int f = 0; f < nframes; ++f) read_all(x + (size_t)f * hop, 32768);
   write_all(work, (size_t)nframes * 65536);
   write_all(out, (size_t)nframes * 65536);
+  return PYSDR_OK;
+}
+
+// ==== the four stream objects (api_objects.hip; footprints read off waterfall.hip / rtty.hip / chan.hip / bank.hip) ====
+
+// ---- waterfall
+// wf_fill_kernel: writes p[0, n)
+int launch_wf_fill(float* p, size_t n, float v, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_wf_fill").st(st).i("n", (long long)n).f("v", v).p("p", p);
+  write_all(p, n);
+  return PYSDR_OK;
+}
+// wf_push_kernel: reads line[0, n), writes slot[0, nfft) (every bin: the fill beyond n)
+int launch_wf_push(const float* line, int n, int nfft, int shift, float* slot, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_wf_push").st(st).i("n", n).i("nfft", nfft).i("shift", shift).p("line", line).p("slot", slot);
+  SAN_CHECK(n >= 0 && n <= nfft && shift >= 0 && shift < nfft, "n %d shift %d nfft %d", n, shift, nfft);
+  read_all(line, (size_t)n);
+  write_all(slot, (size_t)nfft);
+  return PYSDR_OK;
+}
+static void check_wf(const WfArgs& a) {
+  SAN_CHECK(a.cnt >= 1 && a.cnt <= a.ncols && a.head >= 0 && a.head < a.ncols && a.shift >= 0 && a.shift < a.nfft, "cnt %d head %d shift %d", a.cnt, a.head, a.shift);
+}
+// wf_mean_kernel: reads the newest cnt columns wf[((head - k) mod ncols) nfft + [0, nfft)], k = 1 .. cnt; writes mean[0, nfft).
+// wf_median_kernel: reads mean[0, nfft), writes stat[0]
+int launch_wf_mean_median(const WfArgs& a, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_wf_mean_median").st(st).i("nfft", a.nfft).i("ncols", a.ncols).i("head", a.head).i("cnt", a.cnt).i("shift", a.shift).p("wf", a.wf)
+        .p("mean", a.mean).p("stat", a.stat);
+  check_wf(a);
+  for (int k = 1; k <= a.cnt; ++k) read_all(a.wf + (size_t)((a.head - k + a.ncols) % a.ncols) * a.nfft, (size_t)a.nfft);
+  write_all(a.mean, (size_t)a.nfft);
+  read_all(a.mean, (size_t)a.nfft);
+  write_all(a.stat, 1);
+  return PYSDR_OK;
+}
+// wf_max_kernel: reads wf[0, nfft ncols), atomicMax on stat[1].  wf_image_kernel: reads wf (every column), stat[0], stat[1];
+// writes image[0, ncols nfft)
+int launch_wf_max_image(const WfArgs& a, int npsd, float pan_dr, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_wf_max_image").st(st).i("nfft", a.nfft).i("ncols", a.ncols).i("head", a.head).i("shift", a.shift).i("npsd", npsd).f("pan_dr", pan_dr)
+        .p("wf", a.wf).p("stat", a.stat).p("image", a.image);
+  check_wf(a);
+  SAN_CHECK(npsd >= 1 && npsd <= a.nfft, "npsd %d", npsd);
+  read_all(a.wf, (size_t)a.nfft * a.ncols);
+  read_all(a.stat, 2);
+  write_all(a.stat + 1, 1);
+  write_all(a.image, (size_t)a.nfft * a.ncols);
+  return PYSDR_OK;
+}
+// wf_peaks_kernel: reads x[0, n); a peak needs a rise in front and a fall behind it, so at most (n - 1) / 2 of them: writes
+// pos / state / kept [0, that many) and count[0].  The stub reports the most, so that the host's copy of `kept` is as long as it gets.
+int launch_wf_peaks(const float* x, int n, double height, int dist, int* pos, int* state, int* kept, int* count, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_wf_peaks").st(st).i("n", n).f("height", height).i("dist", dist).p("x", x).p("pos", pos).p("state", state).p("kept", kept).p("count", count);
+  const size_t most = n >= 3 ? (size_t)(n - 1) / 2 : 0;
+  SAN_CHECK(dist >= 1 && pos + most <= state && state + most <= kept && kept + most <= count, "the four parts of the peak scratch overlap (n %d)", n);
+  read_all(x, (size_t)n);
+  write_all(pos, most); write_all(state, most); write_all(kept, most);
+  *count = (int)most;
+  return PYSDR_OK;
+}
+
+// ---- RTTY decoder bank: line x >= 1 lives in ring row x % R; nothing before line 1 is read
+namespace {
+template <class T> void ring_rd(const T* ring, long long x, int R, int w, int col, int n) { if (x >= 1) read_all(ring + (size_t)(x % R) * w + col, (size_t)n); }
+template <class T> void ring_wr(T* ring, long long x, int R, int w) { write_all(ring + (size_t)(x % R) * w, (size_t)w); }
+}  // namespace
+int launch_rtty_decode(const RttyArgs& a, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_rtty_decode").st(st).i("nfft", a.nfft).i("flipped", a.flipped).i("nlines", a.nlines).i("band_lo", a.band_lo).i("nband", a.nband)
+        .i("moff", a.moff).i("nsh", a.nsh).i("nb", a.nb).i("flo", a.flo).i("fhi", a.fhi).i("n0", a.n0).i("n_first", a.n_first).i("nd", a.nd).i("R", a.R)
+        .p("lines", a.lines).p("band", a.band).p("s4", a.s4).p("best", a.best).p("sc2", a.sc2).p("isym", a.isym).p("shift", a.shift).p("t", a.t)
+        .p("snr", a.snr).p("held", a.held).p("code", a.code).p("ndet", a.ndet);
+  const int R = a.R, nb = a.nb, nband = a.nband;
+  SAN_CHECK(a.nlines >= 1 && a.n0 >= 1 && a.nd >= 0 && a.nd <= a.max_dec, "nlines %d n0 %lld nd %d max_dec %d", a.nlines, a.n0, a.nd, a.max_dec);
+  // the deepest reach is rt_sc2's best_{n-120}: its row must not be one this call writes
+  SAN_CHECK(a.nlines + 4 * kM <= R, "%d lines + 120 of reach > %d ring rows", a.nlines, R);
+  SAN_CHECK(a.band_lo >= 0 && a.band_lo + nband <= a.nfft, "band [%d, +%d) of %d", a.band_lo, nband, a.nfft);
+  SAN_CHECK(a.moff >= 0 && a.moff + nb + a.nsh <= nband, "decoder columns [%d, +%d) + %d of %d", a.moff, nb, a.nsh, nband);
+  SAN_CHECK(a.flo == a.fhi || (a.flo >= 0 && a.flo < a.fhi && a.fhi + a.nsh <= nband), "finder columns [%d, %d) + %d of %d", a.flo, a.fhi, a.nsh, nband);
+  SAN_CHECK(a.nd == 0 || (a.n_first % kM == 0 && a.n_first >= a.n0 && a.n_first + (long long)kM * (a.nd - 1) < a.n0 + a.nlines), "decisions");
+  for (int l = 0; l < a.nlines; ++l) {
+    const long long n = a.n0 + l;
+    // rt_gather: lines[l nfft + col], col = bin (flipped) or nfft - 1 - bin, bin in [band_lo, band_lo + nband); writes band row n
+    read_all(a.lines + (size_t)l * a.nfft + (a.flipped ? a.band_lo : a.nfft - a.band_lo - nband), (size_t)nband);
+    ring_wr(a.band, n, R, nband);
+  }
+  for (int l = 0; l < a.nlines; ++l) {
+    const long long n = a.n0 + l;
+    // rt_s4: band rows n-3 .. n, columns moff + k and moff + k + nsh, k < nb; writes s4 row n
+    for (int q = 0; q < 4; ++q) { ring_rd(a.band, n - q, R, nband, a.moff, nb); ring_rd(a.band, n - q, R, nband, a.moff + a.nsh, nb); }
+    ring_wr(a.s4, n, R, nb);
+  }
+  for (int l = 0; l < a.nlines; ++l) {
+    const long long n = a.n0 + l;
+    // rt_best: s4 rows n-28, n-24, ..., n; writes best and isym row n
+    for (int g = 0; g < 8; ++g) ring_rd(a.s4, n - 28 + 4 * g, R, nb, 0, nb);
+    ring_wr(a.best, n, R, nb); ring_wr(a.isym, n, R, nb);
+  }
+  for (int l = 0; l < a.nlines; ++l) {
+    const long long n = a.n0 + l;
+    // rt_sc2: best rows n, n-30, ..., n-120; writes sc2 row n
+    for (int i = 0; i < 5; ++i) ring_rd(a.best, n - i * kM, R, nb, 0, nb);
+    ring_wr(a.sc2, n, R, nb);
+  }
+  for (int j = 0; j < a.nd; ++j) {
+    const long long n = a.n_first + (long long)kM * j;
+    // rt_decide: sc2 rows n-29 .. n and (n > 30) n-59 .. n-30; isym row tlast + 1, band rows tlast - 28 + 4 q with tlast anywhere
+    // in [n-60, n-31]: isym rows n-59 .. n-30, band rows n-88 .. n-31, columns moff + k and + nsh; writes t / snr / held [j][nb]
+    for (long long x = n - (n > kM ? 59 : 29); x <= n; ++x) ring_rd(a.sc2, x, R, nb, 0, nb);
+    if (n > kM) {
+      for (long long x = n - 59; x <= n - 30; ++x) ring_rd(a.isym, x, R, nb, 0, nb);
+      for (long long x = n - 88; x <= n - 31; ++x) { ring_rd(a.band, x, R, nband, a.moff, nb); ring_rd(a.band, x, R, nband, a.moff + a.nsh, nb); }
+    }
+    write_all(a.t + (size_t)j * nb, (size_t)nb); write_all(a.snr + (size_t)j * nb, (size_t)nb); write_all(a.held + (size_t)j * nb, (size_t)nb);
+  }
+  if (a.nd > 0) {
+    // rt_emit: snr, held [nd][nb]; shift[nb] read and written; writes code [nd][nb]
+    read_all(a.snr, (size_t)a.nd * nb); read_all(a.held, (size_t)a.nd * nb); read_all(a.shift, (size_t)nb);
+    write_all(a.shift, (size_t)nb); write_all(a.code, (size_t)a.nd * nb);
+  }
+  for (int l = 0; l < a.nlines; ++l) {
+    const long long n = a.n0 + l;
+    // rt_find: band rows n-20 .. n, columns [flo, fhi) and + nsh; writes ndet[l]
+    for (int q = 0; q <= 20 && a.fhi > a.flo; ++q) { ring_rd(a.band, n - q, R, nband, a.flo, a.fhi - a.flo); ring_rd(a.band, n - q, R, nband, a.flo + a.nsh, a.fhi - a.flo); }
+    write_all(a.ndet + l, 1);
+  }
+  return PYSDR_OK;
+}
+
+// ---- polyphase channelizer
+int chan_prepare(const ChanPlan& p) {
+  SAN_CHECK(p.lds_bytes == p.fw * p.mp * (int)sizeof(float2) && p.lds_bytes <= 160 * 1024, "LDS %d", p.lds_bytes);
+  return PYSDR_OK;
+}
+// chan_kernel: frame t of the call and tap row p read x[(t - C p) D + off0 - r], r < M -- from x where that is in [0, n), from
+// hist[H + .] where in [-H, 0), nothing outside: all of x[0, n) and hist[0, H); taps[p M + r], p < P; tw[0, M); perm[0, nk).
+// Writes y[a pitch + i], a < nk, i < nframes.
+int launch_chan(const ChanPlan& p, const ChanArgs& a, int grid, hipStream_t st) {
+  if (fake_hip::tracing()) {
+    Line l("launch_chan");
+    l.st(st).i("grid", grid).i("threads", p.threads).i("lds", p.lds_bytes).i("C", p.C).i("fi", p.fi).i("H", a.H).i("n", a.n).i("off0", a.off0)
+        .i("mf_lo", a.mf_lo).i("nframes", a.nframes).i("M", a.M).i("D", a.D).i("P", a.P).i("mp", a.mp).i("fw", a.fw).i("nk", a.nk).i("pitch", a.pitch)
+        .i("npass", a.npass).i("magic_M", a.magic_M).i("magic_fw", a.magic_fw).i("xq", a.xq).i("xr", a.xr)
+        .p("x", a.x).p("hist", a.hist).p("taps", a.taps).p("tw", a.tw).p("perm", a.perm).p("y", a.y);
+    for (int s = 0; s < a.npass; ++s) l.i(rk("radix", s).c_str(), a.radix[s]).i(rk("mper", s).c_str(), a.magic_per[s]).i(rk("mnq", s).c_str(), a.magic_nq[s]);
+  }
+  SAN_CHECK(grid == a.xq * 8 + a.xr && a.xr >= 0 && a.xr < 8, "grid %d != xq %d * 8 + xr %d", grid, a.xq, a.xr);
+  SAN_CHECK(a.nframes >= 1 && (long long)grid * a.fw >= a.nframes && (long long)(grid - 1) * a.fw < a.nframes, "grid %d of %d frames covers %d", grid, a.fw, a.nframes);
+  SAN_CHECK(a.fw == p.fw && a.mp == p.mp && a.mp == (a.M | 1) && p.fw % p.fi == 0 && p.C * a.D == a.M && (p.threads == 256 || p.threads == 1024), "plan");
+  SAN_CHECK(a.off0 >= 0 && a.off0 < a.D && (long long)(a.nframes - 1) * a.D + a.off0 < a.n, "last frame ends at %lld of %d", (long long)(a.nframes - 1) * a.D + a.off0, a.n);
+  SAN_CHECK(a.P >= 1 && a.P * a.M - 1 <= a.H, "P %d M %d reach behind the history of %d", a.P, a.M, a.H);
+  SAN_CHECK(a.pitch >= a.nframes, "pitch %lld < %d frames", a.pitch, a.nframes);
+  int nb = a.M;
+  for (int s = 0; s < a.npass; ++s) { SAN_CHECK(a.radix[s] >= 2 && nb % a.radix[s] == 0, "radix"); nb /= a.radix[s]; }
+  SAN_CHECK(nb == 1, "passes do not make M");
+  read_all(a.x, (size_t)a.n);
+  read_all(a.hist, (size_t)a.H);
+  read_all(a.taps, (size_t)a.P * a.M);
+  read_all(a.tw, (size_t)a.M);
+  for (int r = 0; r < a.nk; ++r) SAN_CHECK(a.perm[r] >= 0 && a.perm[r] < a.M, "perm[%d] = %d", r, a.perm[r]);
+  for (int r = 0; r < a.nk; ++r) write_all(a.y + (size_t)r * (size_t)a.pitch, (size_t)a.nframes);
+  return PYSDR_OK;
+}
+// chan_roll: neu[i] = old[i + n] while i + n < H, else x[i + n - H], i < H
+int launch_chan_roll(const float2* x, int n, const float2* old, float2* neu, int H, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_chan_roll").st(st).i("n", n).i("H", H).p("x", x).p("old", old).p("new", neu);
+  SAN_CHECK(neu != old && n >= 1, "history roll in place / empty call");
+  for (int i = 0; i < H; ++i) {
+    const long long j = (long long)i + n;
+    neu[i] = j < H ? old[j] : x[j - H];
+  }
+  return PYSDR_OK;
+}
+
+// ---- channel bank
+// bank_kernel, per row: the detector at d[i], i in [-(T - 1), n_out), reads y[i] (AM) or y[i - 2 .. i] (NFM); taps[0, tp);
+// writes a[row apitch + i], i < n_out (whole float4 pairs where 8 outputs fit) and pmax / psum[row ptiles + t], t < ntiles
+int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_bank").st(st).i("mode", mode).i("ntiles", ntiles).i("nk", nk).i("lds_floats", p.lds_floats).i("ypitch", a.ypitch).i("apitch", a.apitch)
+        .i("n_out", a.n_out).i("T", a.T).i("tp", a.tp).f("fm_scale", a.fm_scale).i("noise", a.noise).i("ptiles", a.ptiles)
+        .p("y", a.y).p("a", a.a).p("taps", a.taps).p("pmax", a.pmax).p("psum", a.psum);
+  SAN_CHECK(mode == PYSDR_AM || mode == PYSDR_NFM, "mode %d", mode);
+  SAN_CHECK(a.tp % 8 == 0 && a.tp == p.tp && a.T >= kBankTapsMin && a.T <= a.tp && a.tp - a.T < 8, "T %d tp %d", a.T, a.tp);
+  SAN_CHECK(p.hpad >= a.T + 1 && p.hpad % 8 == 0 && p.hpad <= 256, "hpad %d for %d taps", p.hpad, a.T);
+  SAN_CHECK(ntiles <= a.ptiles && ntiles == (a.n_out + kBankTile - 1) / kBankTile && a.n_out >= 1, "%d tiles for %d outputs, room for %d", ntiles, a.n_out, a.ptiles);
+  SAN_CHECK(p.lds_floats == kBankTile + a.tp, "lds_floats %d", p.lds_floats);
+  SAN_CHECK(a.apitch % 4 == 0 && a.apitch >= a.n_out && (reinterpret_cast<uintptr_t>(a.a) & 15u) == 0, "a: pitch %lld, float4 stores", a.apitch);
+  const int back = mode == PYSDR_AM ? a.T - 1 : a.T + 1;
+  read_all(a.taps, (size_t)a.tp);
+  for (int r = 0; r < nk; ++r) {
+    read_all(a.y + (size_t)r * (size_t)a.ypitch - back, (size_t)back + a.n_out);
+    write_all(a.a + (size_t)r * (size_t)a.apitch, (size_t)a.n_out);
+    write_all(a.pmax + (size_t)r * a.ptiles, (size_t)ntiles);
+    write_all(a.psum + (size_t)r * a.ptiles, (size_t)ntiles);
+  }
+  return PYSDR_OK;
+}
+// bank_finish, per row: reads pmax / psum[row ptiles + t], t < ntiles; state[row] read and written; a[row apitch + i], i < n_out
+// scaled in place; y[n_out + t] -> y[t], t < hpad (y from the row's start: the last hpad samples of [history | outputs])
+int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_bank_finish").st(st).i("nk", nk).i("ypitch", f.ypitch).i("apitch", f.apitch).i("n_out", f.n_out).i("hpad", f.hpad).i("ntiles", f.ntiles)
+        .i("ptiles", f.ptiles).i("agc", f.agc_active).i("squelch", f.squelch).f("ref", f.ref).f("thresh", f.thresh)
+        .p("ybase", f.ybase).p("a", f.a).p("pmax", f.pmax).p("psum", f.psum).p("state", f.state);
+  SAN_CHECK(f.hpad >= 1 && f.hpad <= kBankThreads && f.ntiles >= 1 && f.ntiles <= f.ptiles && f.n_out >= 1, "hpad %d ntiles %d / %d", f.hpad, f.ntiles, f.ptiles);
+  SAN_CHECK(f.ypitch >= (long long)f.hpad + f.n_out, "row of %lld holds %d + %d", f.ypitch, f.hpad, f.n_out);
+  for (int r = 0; r < nk; ++r) {
+    read_all(f.pmax + (size_t)r * f.ptiles, (size_t)f.ntiles);
+    read_all(f.psum + (size_t)r * f.ptiles, (size_t)f.ntiles);
+    read_all(f.state + r, 1); write_all(f.state + r, 1);
+    read_all(f.a + (size_t)r * (size_t)f.apitch, (size_t)f.n_out); write_all(f.a + (size_t)r * (size_t)f.apitch, (size_t)f.n_out);
+    float2* y = f.ybase + (size_t)r * (size_t)f.ypitch;
+    std::memmove(y, y + f.n_out, (size_t)f.hpad * sizeof(float2));
+  }
   return PYSDR_OK;
 }
 

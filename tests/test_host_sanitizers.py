@@ -1,6 +1,7 @@
 """SURVEY.md 5 "sanitizers on the CPU build": the HOST half of libpysdr_hip.so -- pysdr_amd/csrc/api.hip
 (context / receiver bookkeeping, tile geometry handed to the mix + decimate kernel, PLL plans, the setter
-snapshot, the ingest ring's slot state machine, the spectrum object) compiled as plain C++ over a fake
+snapshot, the ingest ring's slot state machine, the spectrum object) and api_objects.hip (waterfall, RTTY decoder
+bank, channelizer, channel bank: ring wraparound, row pitches, strided copies, lazy staging) compiled as plain C++ over a fake
 HIP runtime whose "device" memory is the host heap, with a launch layer that touches exactly what each
 kernel may touch and re-walks every mixdec tile with the kernel's own geometry code
 (pysdr_amd/csrc/mixdec_geom.h) -- built and run under AddressSanitizer + UBSan, and the RX-thread-vs-Qt-
@@ -36,6 +37,7 @@ def test_host_half_and_mixdec_plans_under_address_and_ub_sanitizers(tmp_path):
     assert "HOST_SAN_OK" in out and "HOST_SAN_RACE_OK" in out
     assert "planner sweep: 1920 plans" in out
     assert "pll plan sweep:" in out
+    assert "stream objects: 432 calls" in out
     assert "HOST_SAN_ALLOCFAIL_OK" in out
 
 
