@@ -241,6 +241,7 @@ struct pysdr_ctx {
 
 struct pysdr_spectrum {
   int device = 0, chunk = 0, nfft = 0, max_frames = 0;
+  int num_cus = 256;          // read once at create: the grid of the columns loop (host_plan.h plan_psd_cols)
   Stream stream;
   DevBuf<float> d_win;
   DevBuf<float2> d_work;      // [frames][nfft], grown on demand
@@ -1511,6 +1512,10 @@ int pysdr_spectrum_create(int device, int chunk_size, int nfft, int max_frames, 
   pysdr_spectrum* sp = new pysdr_spectrum();
   sp->device = device; sp->chunk = chunk_size; sp->nfft = nfft; sp->max_frames = max_frames;
   sp->tune = SpectrumTuning::from_env();
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) sp->num_cus = prop.multiProcessorCount;
+  }
   rc = spectrum_alloc(sp, window);
   if (rc) { failed_in("pysdr_spectrum_create", rc); pysdr_spectrum_destroy(sp); return rc; }
   if (rocfft_execution_info_create(&sp->info) != rocfft_status_success ||
@@ -1561,6 +1566,10 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
     //  nontemporal: 320 / 384 / 448 / 512 / 576 / 640 frames = C3 step 3.04 / 2.97 / 2.96-2.97 / 2.93 / 2.94 / 3.26 ms,
     //  scripts/diag/psd_group_sweep.sh; on a second box 448 / 512 / 576 = 2.99-3.01 / 2.95-2.99 / 3.05: the cliff moves from box
     //  to box, so the default sits between the old 448 and the best 512)
+    // The columns pass of a launch is a loop over its frames on 16 x G resident workgroups (psd_form / plan_psd_cols in
+    // host_plan.h from the CU count read at create: 240 frames on 256 CUs = 60 rows of 4 frames each; a single frame = 16
+    // workgroups of one iteration); PYSDR_PSD_PATH=unit / loop:<G> for A/B.  Same bits either way.  Measured (LABNOTES 15):
+    // the columns kernel alone 134.3 -> 129.5 ns per frame, the C3 step 2.945 -> 2.893 ms (medians of 15 + 15 runs: 1.8 %).
     const int group = sp->tune.frames_per_group();
     if (sp->tune.nstreams > 1 && nframes > group) {
       // The groups are dealt out over `nstreams` streams, each with its own intermediate of group / nstreams
@@ -1590,7 +1599,8 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
         const int nf = (nframes - f0 < part) ? nframes - f0 : part;
         const int w = k % ns;
         rc = launch_psd64k(d_x + (size_t)f0 * hop, hop, nf, sp->d_win.get(), w ? sp->xwork[w].get() : sp->d_work.get(),
-                           d_out + (size_t)f0 * sp->nfft, db, w ? sp->xstream[w].get() : sp->stream.get(), sp->tune.packed);
+                           d_out + (size_t)f0 * sp->nfft, db, w ? sp->xstream[w].get() : sp->stream.get(),
+                           psd_form(sp->tune, nf, sp->num_cus));
         if (rc) break;             // a failed launch still joins the side streams below: what was forked keeps writing
       }                            // d_out / xwork until it is done, and the caller reacts to the error right away
       for (int i = 1; i < ns; ++i) {
@@ -1606,7 +1616,7 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
     for (int f0 = 0; f0 < nframes; f0 += group) {
       const int nf = (nframes - f0 < group) ? nframes - f0 : group;
       rc = launch_psd64k(d_x + (size_t)f0 * hop, hop, nf, sp->d_win.get(), sp->d_work.get(),
-                         d_out + (size_t)f0 * sp->nfft, db, sp->stream, sp->tune.packed);
+                         d_out + (size_t)f0 * sp->nfft, db, sp->stream, psd_form(sp->tune, nf, sp->num_cus));
       if (rc) return rc;
     }
     PYSDR_HIP_CHECK(hipEventRecord(sp->ev[1], sp->stream));

@@ -347,8 +347,9 @@ int launch_psd_post(const float2* work, int nframes, int nfft, int half, int db,
                     hipStream_t st);
 
 // fused 32768 -> 65536 PSD path (psdfft.hip): two kernels, `work` = nframes x 65536 complex
-// packed: the intermediate as block-scaled 24-bit fixed point (6 bytes per complex) instead of float2
+// form (host_plan.h psd_form): 0 = float2 intermediate; >= 1 = the intermediate as block-scaled 24-bit fixed point (6 bytes
+// per complex), 1 with one columns unit per workgroup, 1 + G with the columns as a loop over frames on 16 x G workgroups
 int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work,
-                  float* out, int db, hipStream_t st, int packed);
+                  float* out, int db, hipStream_t st, int form);
 
 }  // namespace pysdr

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "common.h"
 
@@ -122,6 +123,7 @@ struct Tuning {
 };
 
 // Tuning values of a spectrum object (pysdr_spectrum_create)
+constexpr int kPsdColsMaxG = 4096;   // most grid rows PYSDR_PSD_PATH=loop:<G> can ask for (far above any residency)
 struct SpectrumTuning {
   bool force_rocfft = false;  // PYSDR_PSD_ROCFFT: rocFFT even for the 32768 -> 65536 size
   int group = 0;              // frames per launch pair of the four-step path (PYSDR_PSD_GROUP); 0 = 480 with the 24-bit intermediate, 448 with float2
@@ -131,6 +133,10 @@ struct SpectrumTuning {
   // the rows of the other and the kernel boundaries of one stream hide behind the other's kernels
   static constexpr int kMaxStreams = 4;
   int nstreams = 2;
+  // PYSDR_PSD_PATH: the columns pass of the 24-bit path.  "unit": one unit (16 columns of one frame) per workgroup, grid
+  // 16 x frames; "loop:<G>": psd_cols_pk_kernel's loop over frames on 16 x G workgroups; unset: the loop with the G of
+  // plan_psd_cols.  (cols_g: -1 = default, 0 = unit, > 0 = forced G)
+  int cols_g = -1;
   int frames_per_group() const { return group > 0 ? group : (packed ? 480 : 448); }
 
   static SpectrumTuning from_env() {
@@ -139,9 +145,34 @@ struct SpectrumTuning {
     { const char* e = tuning_env("PYSDR_PSD_GROUP"); if (e && atoi(e) > 0) t.group = atoi(e); }
     { const char* e = tuning_env("PYSDR_PSD_PACKED"); if (e && *e) t.packed = atoi(e) ? 1 : 0; }
     { const char* e = tuning_env("PYSDR_PSD_STREAMS"); if (e && atoi(e) >= 1 && atoi(e) <= kMaxStreams) t.nstreams = atoi(e); }
+    { const char* e = tuning_env("PYSDR_PSD_PATH");
+      if (e && !strcmp(e, "unit")) t.cols_g = 0;
+      else if (e && !strncmp(e, "loop:", 5) && atoi(e + 5) > 0) t.cols_g = std::min(atoi(e + 5), kPsdColsMaxG); }
     return t;
   }
 };
+
+// The grid of the columns pass as a loop over frames (psdfft.hip psd_cols_pk_kernel): 16 column blocks x G workgroups, of
+// which workgroup (cb, g) walks over the frames g, g + G, g + 2 G, ... < nframes of the launch, the next one's samples
+// already in flight while one is transformed.  All 16 G workgroups must be resident at once: the 37 KB of LDS of a
+// workgroup allow kPsdColsWgPerCu of them on a CU.  Among the G that need the fewest rounds, the smallest is taken, so that
+// the frames deal as evenly as they can (240 frames on 256 CUs: 4 rounds, G = 60 with 4 frames each, not 64 of which
+// sixteen get 3); no workgroup ever gets more than one frame more than another, and G <= nframes: a single frame is 16
+// workgroups of one iteration.  `forced` (PYSDR_PSD_PATH=loop:<G>) is taken as it is, residency included (A/B runs).
+constexpr int kPsdColBlocks = 16, kPsdColsWgPerCu = 4;
+inline int psd_cols_max_g(int num_cus) { return std::max(1, std::min(kPsdColsMaxG, num_cus * kPsdColsWgPerCu / kPsdColBlocks)); }
+inline int plan_psd_cols(int nframes, int num_cus, int forced) {
+  if (nframes < 1) return 1;
+  if (forced > 0) return std::min(forced, nframes);
+  const int gmax = psd_cols_max_g(num_cus);
+  const int rounds = (nframes + gmax - 1) / gmax;
+  return (nframes + rounds - 1) / rounds;
+}
+// launch_psd64k's `form`: 0 = float2 intermediate, 1 = 24-bit with one columns unit per workgroup, 1 + G = 24-bit, loop on 16 x G
+inline int psd_form(const SpectrumTuning& t, int nframes, int num_cus) {
+  if (!t.packed) return 0;
+  return t.cols_g == 0 ? 1 : 1 + plan_psd_cols(nframes, num_cus, t.cols_g);
+}
 
 inline int round_up64(int v) { return (v + 63) & ~63; }
 // time constant 1/(zeta*wn) of a second-order loop of bandwidth bw_hz, in samples at fs

@@ -17,7 +17,14 @@
 // [p][b] order makes 128-byte pieces 2 KB apart: 257 -> 251 ns per frame).  Each
 // 256-point transform is radix 16 x 16 (one 16-point butterfly per thread per pass), data
 // exchanged through LDS with conflict-free strides.
+// The shipped pair keeps the intermediate as block-scaled 24-bit fixed point (psd_cols_pk / psd_rows_pk below), and its
+// columns pass is a LOOP OVER FRAMES: 16 x G resident workgroups, each keeping its column block -- table, window and
+// four-step twiddles set up once -- and loading its next frame while it transforms one (psd_cols_pk_kernel; the grid is
+// host_plan.h plan_psd_cols; LABNOTES 15).  One unit per workgroup (psd_cols_pk_unit_kernel, PYSDR_PSD_PATH=unit) is the A/B form.
+#include <algorithm>
+
 #include "common.h"
+#include "psd_cols_geom.h"
 
 namespace pysdr {
 
@@ -354,14 +361,132 @@ __device__ __forceinline__ void cols_unit_pk(const float2* __restrict__ xf, cons
   }
 }
 
-__global__ __launch_bounds__(256) void psd_cols_pk_kernel(const float2* __restrict__ x, size_t hop,
-                                                          const float* __restrict__ win, char* __restrict__ work) {
+__global__ __launch_bounds__(256) void psd_cols_pk_unit_kernel(const float2* __restrict__ x, size_t hop,
+                                                               const float* __restrict__ win, char* __restrict__ work) {
   __shared__ __attribute__((aligned(16))) float2 lds[kColLds];
   __shared__ __attribute__((aligned(16))) float2 tw[16 * kTwRow];
   __shared__ float red[4];
   const int f = blockIdx.y;
   tw256_build(tw, threadIdx.x);
   cols_unit_pk(x + (size_t)f * hop, win, work + (size_t)f * kN * sizeof(float2), blockIdx.x, threadIdx.x, lds, tw, red);
+}
+
+
+// ---- the same columns pass as a LOOP OVER FRAMES: grid = 16 x G, workgroup (cb, g) keeps column block cb and walks over
+// the frames g, g + G, g + 2 G, ... of the launch (G = gridDim.y <= nframes: host_plan.h plan_psd_cols; all 16 G workgroups
+// are resident at once, and no workgroup gets more than one frame more than another).  Nothing happens across workgroups.
+// What a unit recomputed for every frame from inputs that never change is set up ONCE in front of the loop: the W_256 table
+// (256 v_sin / v_cos pairs), the thread's 8 window values (8 L2 round trips in front of the first butterfly), and the 16
+// four-step twiddles of twiddle_pow0 (two v_sin / v_cos pairs and 12 complex products that depend on (bb, p1) only).  The
+// arithmetic of a frame is the unit's, operation by operation on the same values in the same order, so every bit of the
+// intermediate is what psd_cols_pk_unit_kernel writes (tests/test_gpu_psd_cols_loop.py).
+// A unit is a strict chain -- 16 loads, wait, DFT16, barrier, LDS, barrier, DFT16, reduce, barrier, 32 stores -- that only
+// the CU's other three workgroups hide.  Here the 8 samples of the workgroup's NEXT frame are loaded while this one is
+// transformed: issued in front of the first DFT16, taken at the top of the next iteration.  The loads come from inline asm
+// and are waited for by hand (LABNOTES 7.4: hipcc cannot count vmcnt across a back edge and would wait for a prefetch it
+// knows about in front of the first use of the CURRENT frame): "+v" ties the registers, so that nothing lies between the
+// load and the wait that reads them, and the wait sits in front of the frame's stores -- vmcnt counts those too, and the
+// loads have had the whole transform to land.
+//   (saddr form: one 32-bit lane offset, the frame's base + 32 KB a1 in scalar registers)
+__device__ __forceinline__ void cols_prefetch(v2f_t (&nx)[8], unsigned voff, const float2* xf) {
+  const PYSDR_AS1 char* base = (const PYSDR_AS1 char*)xf;
+#pragma unroll
+  for (int a1 = 0; a1 < 8; ++a1)
+    asm volatile("global_load_dwordx2 %0, %1, %2 nt" : "+v"(nx[a1]) : "v"(voff), "s"(base + 32768 * a1));
+}
+__device__ __forceinline__ void cols_prefetch_wait(v2f_t (&nx)[8]) {
+  asm volatile("s_waitcnt vmcnt(0)"
+               : "+v"(nx[0]), "+v"(nx[1]), "+v"(nx[2]), "+v"(nx[3]), "+v"(nx[4]), "+v"(nx[5]), "+v"(nx[6]), "+v"(nx[7]));
+}
+
+// (256 threads, four waves per SIMD: the 37 KB of LDS allow four workgroups per CU, so up to 128 registers cost nothing)
+__global__ __launch_bounds__(256, 4) void psd_cols_pk_kernel(const float2* __restrict__ x, size_t hop,
+                                                             const float* __restrict__ win, char* __restrict__ work,
+                                                             int nframes) {
+  __shared__ __attribute__((aligned(16))) float2 lds[kColLds];
+  __shared__ __attribute__((aligned(16))) float2 tw[16 * kTwRow];
+  __shared__ float red[4];
+  const int tid = threadIdx.x, cb = blockIdx.x;
+  const int b = tid & 15, hi = tid >> 4;
+  const int bb = cb * kColsPerWg + b;
+  PsdColsWalk fr((int)blockIdx.y, (int)gridDim.y, nframes);             // fr.f < nframes: the grid has at most nframes rows
+  const unsigned voff = (unsigned)(256 * hi + bb) * (unsigned)sizeof(float2);   // sample n = 256 (a0 + 16 a1) + bb, a0 = hi
+  v2f_t nx[8] = {};
+  cols_prefetch(nx, voff, x + (size_t)fr.f * hop);                     // the first frame, behind which the set-up hides
+  tw256_build(tw, tid);
+  float g[8];
+#pragma unroll
+  for (int a1 = 0; a1 < 8; ++a1) g[a1] = ldg1(win + 256 * (hi + 16 * a1) + bb);
+  // twiddle_pow0's factors W_65536^(bb (p1 + 16 p0)), p1 = hi: the same products in the same order, formed once
+  float2 t[16];
+  {
+    const float2 w = expmpi((float)(16 * bb) * (1.0f / 32768.0f)), w0 = expmpi((float)(bb * hi) * (1.0f / 32768.0f));
+    const float2 w2 = cmul(w, w), w4 = cmul(w2, w2), w8 = cmul(w4, w4);
+    const float2 b0 = w0, b4 = cmul(w0, w4), b8 = cmul(w0, w8), b12 = cmul(b4, w8);
+    const float2 w3 = cmul(w2, w);
+    t[0] = b0; t[1] = cmul(b0, w); t[2] = cmul(b0, w2); t[3] = cmul(b0, w3);
+    t[4] = b4; t[5] = cmul(b4, w); t[6] = cmul(b4, w2); t[7] = cmul(b4, w3);
+    t[8] = b8; t[9] = cmul(b8, w); t[10] = cmul(b8, w2); t[11] = cmul(b8, w3);
+    t[12] = b12; t[13] = cmul(b12, w); t[14] = cmul(b12, w2); t[15] = cmul(b12, w3);
+  }
+  float2* const p1w = lds + 16 * hi + b;                                // pass 1 writes slot(p1, a0 = hi, b)
+  const float2* const p2r = lds + 272 * hi + b;                         // pass 2 reads slot(p1 = hi, a0, b)
+  const size_t oidx = (size_t)cb * 4096 + hi * 16 + b;
+  cols_prefetch_wait(nx);
+  __syncthreads();                                                      // the table
+  for (;;) {
+    float2 u[16];
+#pragma unroll
+    for (int a1 = 0; a1 < 8; ++a1) {
+      u[a1] = make_float2(nx[a1].x * g[a1], nx[a1].y * g[a1]);
+      // the products are formed HERE, in front of the loads that overwrite nx: left alone, hipcc sinks them below the
+      // prefetch and keeps the old samples alive in a second register block, which it then refills by copying the new
+      // ones in front of their wait
+      asm volatile("" : "+v"(u[a1].x), "+v"(u[a1].y));
+    }
+#pragma unroll
+    for (int a1 = 8; a1 < 16; ++a1) u[a1] = make_float2(0.f, 0.f);
+    if (fr.has_next()) cols_prefetch(nx, voff, x + (size_t)fr.fn * hop);   // never a frame the launch does not have
+    dft16(u);
+    twiddle_tab(u, tw, hi);
+    // No barrier in front of these writes: every thread's pass-2 reads of the LAST frame lie in front of its reduction
+    // barrier (C) below, which every thread has passed before any thread gets here.  The unit's first barrier was for the
+    // table; in the loop, (C) of iteration i - 1 is what orders pass 2's LDS reads before iteration i's pass-1 writes.
+#pragma unroll
+    for (int p1 = 0; p1 < 16; ++p1) p1w[272 * p1] = u[p1];
+    __syncthreads();                                                    // (B) pass 1 -> pass 2
+    float2 v[16];
+#pragma unroll
+    for (int a0 = 0; a0 < 16; ++a0) v[a0] = p2r[16 * a0];
+    dft16(v);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = cmul(v[k], t[k]);
+    float m = 0.f;
+#pragma unroll
+    for (int p0 = 0; p0 < 16; ++p0) m = fmaxf(fmaxf(m, fabsf(v[p0].x)), fabsf(v[p0].y));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    red[tid >> 6] = m;                     // every lane of the wave holds the same m: no single-lane block in front of (C)
+    __syncthreads();                       // (C) the block maximum; red[] is rewritten only behind the next frame's (B)
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const bool live = m >= 1.0e-20f;
+    const float sc = live ? __fdiv_rn(8388600.0f, m) : 0.0f;
+    char* const wf = work + (size_t)fr.f * kN * sizeof(float2);
+    cols_prefetch_wait(nx);                // the next frame's samples: in flight since the top of this iteration
+    // the loop's one single-lane block (LABNOTES 7.1 (a)), behind the last barrier of the iteration
+    if ((tid & 63) == 0)
+      *(PYSDR_AS1 float*)(wf + kPkScaleOff + 4 * (4 * cb + (tid >> 6))) = live ? __fdiv_rn(m, 8388600.0f) * (1.0f / 256.0f) : 0.f;
+    PYSDR_AS1 unsigned* oh = (PYSDR_AS1 unsigned*)wf + oidx;
+    PYSDR_AS1 unsigned short* ol = (PYSDR_AS1 unsigned short*)(wf + kPkLoOff) + oidx;
+#pragma unroll
+    for (int p0 = 0; p0 < 16; ++p0) {
+      const unsigned a = (unsigned)__float2int_rn(v[p0].x * sc), c = (unsigned)__float2int_rn(v[p0].y * sc);
+      oh[p0 * 256] = pk_perm(c, a, 0x06050201u);
+      ol[p0 * 256] = (unsigned short)pk_perm(c, a, 0x0c0c0400u);
+    }
+    if (!fr.has_next()) break;
+    fr.advance();
+  }
 }
 
 __device__ __forceinline__ void rows_unit_pk(const char* __restrict__ wf, float* __restrict__ of, int rb, int db,
@@ -420,10 +545,17 @@ __global__ __launch_bounds__(512) void psd_rows_pk_kernel(const char* __restrict
 }  // namespace
 
 // nframes frames; `work` holds nframes x 65536 complex of intermediate.
+// form (host_plan.h psd_form): 0 = float2 intermediate; 1 = 24-bit intermediate, one columns unit per workgroup;
+// 1 + G = 24-bit intermediate, columns as a loop over frames on a grid of 16 x min(G, nframes) workgroups
 int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work,
-                  float* out, int db, hipStream_t st, int packed) {
-  if (packed) {
-    hipLaunchKernelGGL(psd_cols_pk_kernel, dim3(256 / kColsPerWg, nframes), dim3(256), 0, st, x, hop, win, (char*)work);
+                  float* out, int db, hipStream_t st, int form) {
+  if (form >= 1) {
+    if (form > 1) {
+      const int rows = std::min(form - 1, nframes);
+      hipLaunchKernelGGL(psd_cols_pk_kernel, dim3(256 / kColsPerWg, rows), dim3(256), 0, st, x, hop, win, (char*)work, nframes);
+    } else {
+      hipLaunchKernelGGL(psd_cols_pk_unit_kernel, dim3(256 / kColsPerWg, nframes), dim3(256), 0, st, x, hop, win, (char*)work);
+    }
     PYSDR_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(psd_rows_pk_kernel, dim3(256 / kRowsPerWg, nframes), dim3(512), 0, st, (const char*)work, out, db);
     PYSDR_HIP_CHECK(hipGetLastError());

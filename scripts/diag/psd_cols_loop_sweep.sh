@@ -1,0 +1,16 @@
+# The columns loop of the 64k PSD (psdfft.hip psd_cols_pk_kernel) on the C3 step: grid rows G (a quarter, a half and the whole
+# of the residency of a 256-CU device, and the plan's evened default) x streams x frames per group, beside the unit form.
+#   scripts/diag/psd_cols_loop_sweep.sh [repeats]
+for rep in $(seq ${1:-2}); do
+for streams in 1 2; do
+for grp in 384 480 512; do
+for path in unit loop:16 loop:32 loop:64 default; do
+  if [ $path = default ]; then unset PYSDR_PSD_PATH; else export PYSDR_PSD_PATH=$path; fi
+  PYSDR_TUNING=1 PYSDR_PSD_STREAMS=$streams PYSDR_PSD_GROUP=$grp timeout -k 10 120 python bench.py --steps 30 --warmup 5 2>/dev/null | python -c "
+import sys, json
+d = json.loads(sys.stdin.read().strip().splitlines()[-1])
+print('streams $streams group $grp path %-8s' % '$path', 'GS/s %.1f' % (d['value'] / 1e3), 'ms %.4f' % d['ms_per_step'])" || exit 1
+done
+done
+done
+done
