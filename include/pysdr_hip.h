@@ -365,12 +365,24 @@ int  pysdr_chan_process(pysdr_chan* ch, const void* iq, int n, int on_device, vo
  * samples iq[2 (i * pitch + j)] of row rows[i]; either may be NULL.  After a call that completed no output (and after
  * create and reset) there is nothing to fetch: the buffers are left as they are.
  * The calls on one handle exclude each other (a lock in the handle); destroy must not race them.  An error leaves the
- * handle usable. */
+ * handle usable.
+ * The complex-tap modes: pysdr_bank_set_mode_cplx takes mode PYSDR_USB, PYSDR_LSB or PYSDR_CW and
+ * ntaps == ntaps_af complex taps c = af_re + j af_im (create names only the start mode, and set_mode's real taps cannot
+ * express these modes: both go on refusing them); it holds from the next call on like set_mode, with the same locking
+ * and stream discipline.  NULL pointers, another tap count or any other mode (AM, NFM, SSB, IQ, ...): PYSDR_ERR_ARG, the
+ * handle unchanged.  With m the absolute output index since create / reset,
+ *   d[m] = y[m]  (USB, LSB)   or   y[m] exp(j 2 pi ph(m) / 2^32), ph(m) = fword m mod 2^32 as a signed 32-bit value,
+ *          fword = pysdr_freq_word(bfo_hz, fs_out)  (CW; bfo_hz is not used otherwise),
+ *   a[m] = Re sum_i c[i] d[m - i],   am[m] = a[m] gain,
+ * and the block AGC is active while enabled, as in AM.  There is no squelch in these modes: a threshold is ignored, level
+ * keeps its value and every gate stays open.  The un-gained a does not depend on how the stream is cut into calls, bit for
+ * bit, the BFO phase included.  The kernels of these modes use twice the LDS bytes pysdr_bank_plan reports. */
 typedef struct pysdr_bank pysdr_bank;
 int  pysdr_bank_plan(int nk, int ntaps_af, int max_out, int32_t out[8]);
 int  pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pysdr_bank** out);
 void pysdr_bank_destroy(pysdr_bank* b);
 int  pysdr_bank_set_mode(pysdr_bank* b, int mode, const double* af, int ntaps);
+int  pysdr_bank_set_mode_cplx(pysdr_bank* b, int mode, const double* af_re, const double* af_im, int ntaps, double bfo_hz);
 int  pysdr_bank_set_agc(pysdr_bank* b, int enable, float ref);
 int  pysdr_bank_set_squelch(pysdr_bank* b, float thresh);
 int  pysdr_bank_reset(pysdr_bank* b);

@@ -122,6 +122,7 @@ PROTOTYPES = {
     "pysdr_bank_create": (_i, [_vp, _d, _i, _i, C.POINTER(_vp)]),
     "pysdr_bank_destroy": (None, [_vp]),
     "pysdr_bank_set_mode": (_i, [_vp, _i, _pd, _i]),
+    "pysdr_bank_set_mode_cplx": (_i, [_vp, _i, _pd, _pd, _i, _d]),
     "pysdr_bank_set_agc": (_i, [_vp, _i, _f]),
     "pysdr_bank_set_squelch": (_i, [_vp, _f]),
     "pysdr_bank_reset": (_i, [_vp]),

@@ -2,7 +2,8 @@
 host half ``api_objects.hip``).  A
 ``Channelizer`` delivers the rows; every row then gets what a sub-receiver tuned there would do behind its ``rx.iq`` --
 detector, real AF low-pass, block AGC (AM), noise squelch (NFM) -- with one call as the AGC block.  One mode, one AF
-filter, one squelch threshold and one AGC setting hold for the whole bank."""
+filter, one squelch threshold and one AGC setting hold for the whole bank.  ``SidebandBank`` adds the complex-tap modes
+USB, LSB and CW."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,10 +14,12 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .channelizer import Channelizer
-from .design import af_bank_real
+from .design import af_bank_cmpx, af_bank_real, cw_taps
 from .tables import AF_BWs, MODE_INDEX, index_of_bw
 
 BANK_MODES = ("AM", "NFM")
+SIDEBAND_MODES = ("USB", "LSB", "CW")
+BFO_DEFAULT = 700.0        # Hz, the reference's CW pitch
 
 
 def plan(nk, ntaps_af, max_out):
@@ -35,8 +38,22 @@ def af_taps(fs_out, ntaps, af_bw):
     return af_bank_real(fs_out, ntaps, [AF_BWs[idx]])[0]
 
 
+def sideband_taps(fs_out, ntaps, mode, af_bw, bfo=BFO_DEFAULT):
+    """The complex AF taps (complex128) of a sub-receiver in USB / LSB -- the row of ``rx.demod.filter_bank_cmpx`` picked
+    as ``af_taps`` picks its row ('Max' for 0 or a width without a label), conjugated for LSB -- or in CW: a band-pass of
+    af_bw Hz (0: the widest) around the BFO pitch."""
+    if mode == "CW":
+        return cw_taps(fs_out, ntaps, af_bw, bfo)
+    if mode not in ("USB", "LSB"):
+        raise _lib.PysdrError(f"sideband_taps: mode {mode!r} is not one of {SIDEBAND_MODES}")
+    idx = index_of_bw(af_bw, AF_BWs, 0) if af_bw else 0
+    c = af_bank_cmpx(fs_out, ntaps, [AF_BWs[idx]])[0]
+    return np.conj(c) if mode == "LSB" else c
+
+
 class ChannelBank:
     """Row a of every output is channel ``(k_first + a) % M`` at ``freqs[a]`` Hz, as for ``Channelizer``."""
+    MODES = BANK_MODES
 
     def __init__(self, fs, M, D=None, h=None, channels=None, mode="NFM", af_bw=4e3, ntaps_af=255, squelch=0.0, agc=True,
                  device=0, max_in=1 << 22):
@@ -44,15 +61,16 @@ class ChannelBank:
         self._h = None
         self.chan = None
         self.ntaps_af = int(ntaps_af)
-        if mode not in BANK_MODES:
-            raise _lib.PysdrError(f"ChannelBank: mode {mode!r} is not one of {BANK_MODES}")
+        if mode not in self.MODES:
+            raise _lib.PysdrError(f"{type(self).__name__}: mode {mode!r} is not one of {self.MODES}")
         nk = int(M) if channels is None else int(channels[1])
         plan(nk, self.ntaps_af, 1)                                    # a bad shape fails here, with or without a device
         self.chan = Channelizer(fs, M, D, h, channels, device, max_in)
         self.fs, self.M, self.D, self.nk = self.chan.fs, self.chan.M, self.chan.D, self.chan.nk
         self.freqs, self.fs_out = self.chan.freqs, self.chan.fs_out
         hd = C.c_void_p()
-        check(self._L.pysdr_bank_create(self.chan._h, self.fs_out, MODE_INDEX[mode], self.ntaps_af, C.byref(hd)),
+        start = mode if mode in BANK_MODES else BANK_MODES[0]        # create names a real-tap mode; set_mode below sets the real one
+        check(self._L.pysdr_bank_create(self.chan._h, self.fs_out, MODE_INDEX[start], self.ntaps_af, C.byref(hd)),
               "pysdr_bank_create")
         self._h = hd
         self.mode, self.af_bw = mode, float(af_bw)
@@ -82,8 +100,8 @@ class ChannelBank:
 
     def set_mode(self, mode, af_bw=None):
         """Mode and AF filter from the next call on, for the whole AF window of that call's outputs."""
-        if mode not in BANK_MODES:
-            raise _lib.PysdrError(f"ChannelBank: mode {mode!r} is not one of {BANK_MODES}")
+        if mode not in self.MODES:
+            raise _lib.PysdrError(f"{type(self).__name__}: mode {mode!r} is not one of {self.MODES}")
         bw = self.af_bw if af_bw is None else float(af_bw)
         af = np.ascontiguousarray(af_taps(self.fs_out, self.ntaps_af, bw), np.float64)
         check(self._L.pysdr_bank_set_mode(self._h, MODE_INDEX[mode], _lib.as_pd(af), len(af)), "pysdr_bank_set_mode")
@@ -186,3 +204,30 @@ class ChannelBank:
 
     def sync(self):
         check(self._L.pysdr_bank_sync(self._h), "pysdr_bank_sync")
+
+
+class SidebandBank(ChannelBank):
+    """A ``ChannelBank`` that also runs USB, LSB and CW: complex AF taps, the real part of the filter output as audio, in
+    CW behind a BFO of ``bfo`` Hz whose phase follows the absolute output index.  The block AGC is active in these modes
+    as in AM; they have no squelch: a threshold is ignored, every gate stays open."""
+    MODES = BANK_MODES + SIDEBAND_MODES
+
+    def __init__(self, fs, M, D=None, h=None, channels=None, mode="USB", af_bw=3e3, ntaps_af=255, squelch=0.0, agc=True,
+                 device=0, max_in=1 << 22, bfo=BFO_DEFAULT):
+        self.bfo = float(bfo)
+        super().__init__(fs, M, D, h, channels, mode, af_bw, ntaps_af, squelch, agc, device, max_in)
+
+    def set_mode(self, mode, af_bw=None, bfo=None):
+        """Mode, AF filter and (CW) BFO pitch from the next call on, for the whole AF window of that call's outputs."""
+        if mode not in self.MODES:
+            raise _lib.PysdrError(f"SidebandBank: mode {mode!r} is not one of {self.MODES}")
+        if bfo is not None:
+            self.bfo = float(bfo)
+        if mode in BANK_MODES:
+            return super().set_mode(mode, af_bw)
+        bw = self.af_bw if af_bw is None else float(af_bw)
+        af = np.ascontiguousarray(sideband_taps(self.fs_out, self.ntaps_af, mode, bw, self.bfo), np.complex128)
+        re, im = np.ascontiguousarray(af.real), np.ascontiguousarray(af.imag)
+        check(self._L.pysdr_bank_set_mode_cplx(self._h, MODE_INDEX[mode], _lib.as_pd(re), _lib.as_pd(im), len(af), self.bfo),
+              "pysdr_bank_set_mode_cplx")
+        self.mode, self.af_bw, self.af = mode, bw, af

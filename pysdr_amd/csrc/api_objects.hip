@@ -71,11 +71,13 @@ struct pysdr_bank {
   bool have_taps = false;
   int agc_enable = 1;
   float ref = kAgcRefDefault, thresh = 0.f, fm_scale = 0.f;
+  double fs_out = 0.0;
+  uint32_t fword = 0;               // CW: the BFO's phase increment per output
   int last_n_out = 0;
   long long ypitch = 0, apitch = 0;
   DevBuf<float2> d_y;               // [nk][hpad + out_cap]
   DevBuf<float> d_a;                // [nk][out_cap]
-  DevBuf<float> d_taps;             // [tp]
+  DevBuf<float> d_taps;             // [2 tp]: real taps in the first half; USB / LSB / CW: re, then -im
   DevBuf<float> d_pmax;             // [nk][tiles]
   DevBuf<double> d_psum;            // [nk][tiles]
   DevBuf<BankState> d_state;
@@ -156,7 +158,7 @@ int bank_alloc(pysdr_bank* b) {
   const size_t nk = (size_t)b->nk;
   PYSDR_HIP_CHECK(b->d_y.alloc(nk * b->ypitch));
   PYSDR_HIP_CHECK(b->d_a.alloc(nk * b->apitch));
-  PYSDR_HIP_CHECK(b->d_taps.alloc((size_t)b->plan.tp));
+  PYSDR_HIP_CHECK(b->d_taps.alloc(2 * (size_t)b->plan.tp));
   PYSDR_HIP_CHECK(b->d_pmax.alloc(nk * b->plan.tiles));
   PYSDR_HIP_CHECK(b->d_psum.alloc(nk * b->plan.tiles));
   PYSDR_HIP_CHECK(b->d_state.alloc(nk));
@@ -592,6 +594,7 @@ int pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pys
   int rc = use_device(b->device);
   if (rc) { delete b; return rc; }
   b->mode = mode; b->T = ntaps_af;
+  b->fs_out = fs_out;
   b->fm_scale = (float)(fs_out / (2.0 * M_PI * kNfmFullScaleDev));
   b->ypitch = (long long)b->plan.hpad + b->out_cap;
   b->apitch = b->out_cap;
@@ -623,6 +626,25 @@ int pysdr_bank_set_mode(pysdr_bank* b, int mode, const double* af, int ntaps) {
   PYSDR_HIP_CHECK(hipMemcpyAsync(b->d_taps.get(), b->h_taps.data(), b->h_taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   b->mode = mode;
+  b->have_taps = true;
+  return PYSDR_OK;
+}
+
+int pysdr_bank_set_mode_cplx(pysdr_bank* b, int mode, const double* af_re, const double* af_im, int ntaps, double bfo_hz) {
+  if (!b || !af_re || !af_im) { set_last_error("pysdr_bank_set_mode_cplx: NULL bank or taps"); return PYSDR_ERR_ARG; }
+  if (mode != PYSDR_USB && mode != PYSDR_LSB && mode != PYSDR_CW) { set_last_error("pysdr_bank_set_mode_cplx: mode %d is none of USB, LSB, CW", mode); return PYSDR_ERR_ARG; }
+  if (ntaps != b->T) { set_last_error("pysdr_bank_set_mode_cplx: ntaps %d != ntaps_af %d", ntaps, b->T); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(b->mu);
+  PYSDR_HIP_CHECK(hipSetDevice(b->device));
+  hipStream_t st = b->stream;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // the staging vector may still feed an earlier copy
+  const size_t tp = (size_t)b->plan.tp;
+  b->h_taps.assign(2 * tp, 0.f);
+  for (int i = 0; i < ntaps; ++i) { b->h_taps[i] = (float)af_re[i]; b->h_taps[tp + i] = -(float)af_im[i]; }   // -im: every term an fma
+  PYSDR_HIP_CHECK(hipMemcpyAsync(b->d_taps.get(), b->h_taps.data(), b->h_taps.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  b->mode = mode;
+  b->fword = (mode == PYSDR_CW) ? pysdr_freq_word(bfo_hz, b->fs_out, nullptr) : 0u;
   b->have_taps = true;
   return PYSDR_OK;
 }
@@ -691,13 +713,14 @@ int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, floa
   a.y = b->d_y.get() + b->plan.hpad; a.ypitch = b->ypitch; a.a = b->d_a.get(); a.apitch = b->apitch;
   a.n_out = nf; a.T = b->T; a.tp = b->plan.tp; a.taps = b->d_taps.get(); a.fm_scale = b->fm_scale; a.noise = squelch;
   a.pmax = b->d_pmax.get(); a.psum = b->d_psum.get(); a.ptiles = b->plan.tiles;
+  a.m0_lo = (uint32_t)((s0 + D - 1) / D); a.fword = b->fword;          // CW: the BFO phase follows the absolute output index
   rc = launch_bank(b->mode, b->plan, a, ntiles, b->nk, st);
   if (rc) return rc;
   FinishArgs f{};
   f.ybase = b->d_y.get(); f.ypitch = b->ypitch; f.a = a.a; f.apitch = b->apitch;
   f.n_out = nf; f.hpad = b->plan.hpad; f.ntiles = ntiles; f.ptiles = b->plan.tiles;
   f.pmax = a.pmax; f.psum = a.psum; f.state = b->d_state.get();
-  f.agc_active = (b->agc_enable && b->mode == PYSDR_AM) ? 1 : 0;
+  f.agc_active = (b->agc_enable && b->mode != PYSDR_NFM) ? 1 : 0;      // AM, USB, LSB, CW: the oracle's AGC_MODES
   f.squelch = squelch; f.ref = b->ref; f.thresh = b->thresh;
   rc = launch_bank_finish(f, b->nk, st);
   if (rc) return rc;

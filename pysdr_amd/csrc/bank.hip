@@ -17,6 +17,17 @@
 //       squelch updates (one lane), scales the row in place where the gain is not 1, and moves the last Hpad samples of
 //       the row to its front (read, barrier, write: the ranges may overlap).
 // A call that completes no output launches neither and changes no state.
+//
+// The complex-tap modes USB / LSB / CW run bank_cplx_kernel in bank_kernel's place: with c[0 .. T)
+// complex taps,
+//   d[m]  = y[m]                                                     (USB, LSB: they differ in the taps only)
+//         = y[m] exp(j 2 pi ph(m) / 2^32),  ph(m) = fword m mod 2^32 taken as signed: m the absolute output index  (CW)
+//   a[m]  = Re sum_{i<T} c[i] d[m - i] = sum_i cr[i] dr[m - i] + sum_i (-ci[i]) di[m - i]
+// Same grid, threads and outputs per thread; the detector output lies in LDS as two planes (re, im), the taps arrive as
+// [cr | -ci] so that every term is an fma, and a step of eight taps forms one partial sum of its eight real-plane
+// products and one of its eight imaginary-plane products (tap ascending), adds the two and adds that to the output's
+// sum: the order depends on the tap index alone, so the bits do not depend on the call.  psum is written as 0 (no
+// squelch in these modes) and bank_finish follows unchanged.
 #include "objects_plan.h"
 
 namespace pysdr {
@@ -185,12 +196,119 @@ __global__ __launch_bounds__(kBankThreads) void bank_finish(const FinishArgs f) 
   if (tid < f.hpad) y[tid] = keep;
 }
 
+// ---- the complex-tap modes ---------------------------------------------------------------------------------------------
+// bank_step for complex taps: cr[0 .. 8) and cn[0 .. 8) = -ci of taps 8 b .., wr / wi the windows of the two planes.
+template <bool GUARD>
+__device__ __forceinline__ void bank_step_cplx(const float* __restrict__ cr, const float* __restrict__ cn, int left,
+                                               const float (&wr)[16], const float (&wi)[16], float (&acc)[kBankW]) {
+  float pr[kBankW], pi[kBankW];
+  const float r0 = cr[0], n0 = cn[0];
+#pragma unroll
+  for (int j = 0; j < kBankW; ++j) { pr[j] = r0 * wr[j + 7]; pi[j] = n0 * wi[j + 7]; }
+#pragma unroll
+  for (int t = 1; t < kBankW; ++t) {
+    if (GUARD && t >= left) break;
+    const float rt = cr[t], nt = cn[t];
+#pragma unroll
+    for (int j = 0; j < kBankW; ++j) {
+      pr[j] = __builtin_fmaf(rt, wr[j - t + 7], pr[j]);
+      pi[j] = __builtin_fmaf(nt, wi[j - t + 7], pi[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kBankW; ++j) acc[j] += pr[j] + pi[j];
+}
+
+template <bool BFO>   // false: USB / LSB, true: CW
+__global__ __launch_bounds__(kBankThreads) void bank_cplx_kernel(const BankArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sd[];       // two planes of E floats: re, im of d[tile0 + e - (tp - 1)]
+  __shared__ float wmax[kBankThreads / 64];
+  const int tid = threadIdx.x, row = blockIdx.y;
+  const int tile0 = blockIdx.x * kBankTile;
+  const float2* y = a.y + (size_t)row * (size_t)a.ypitch;
+  const int E = kBankTile + a.tp;                                   // a multiple of 8: the second plane is 16-byte aligned
+  float* const sr = sd;
+  float* const si = sd + E;
+  for (int e = tid; e < E; e += kBankThreads) {
+    const int rel = e - (a.tp - 1), i = tile0 + rel;               // d[i]; only rel >= -(T - 1) is ever multiplied
+    float2 d = make_float2(0.f, 0.f);
+    if (rel >= -(a.T - 1) && i < a.n_out) {
+      d = y[i];
+      if (BFO) {                                                    // stage2.hip's kDetBfo phase, once per sample
+        const uint32_t ph = a.fword * (a.m0_lo + (uint32_t)i);
+        const float half_turns = (float)(int)ph * (1.0f / 2147483648.0f);
+        float s, c;
+        sincospif(half_turns, &s, &c);                              // staging is 1 / 500 of the work: the accurate form is free
+        d = make_float2(d.x * c - d.y * s, d.x * s + d.y * c);
+      }
+    }
+    sr[e] = d.x;
+    si[e] = d.y;
+  }
+  __syncthreads();
+
+  const int o0 = kBankW * tid;
+  float acc[kBankW], wr[16], wi[16];
+#pragma unroll
+  for (int j = 0; j < kBankW; ++j) acc[j] = 0.f;
+  {
+    const float4 r0 = *reinterpret_cast<const float4*>(sr + o0 + a.tp), r1 = *reinterpret_cast<const float4*>(sr + o0 + a.tp + 4);
+    const float4 i0 = *reinterpret_cast<const float4*>(si + o0 + a.tp), i1 = *reinterpret_cast<const float4*>(si + o0 + a.tp + 4);
+    wr[8] = r0.x; wr[9] = r0.y; wr[10] = r0.z; wr[11] = r0.w; wr[12] = r1.x; wr[13] = r1.y; wr[14] = r1.z; wr[15] = r1.w;
+    wi[8] = i0.x; wi[9] = i0.y; wi[10] = i0.z; wi[11] = i0.w; wi[12] = i1.x; wi[13] = i1.y; wi[14] = i1.z; wi[15] = i1.w;
+  }
+  const float* __restrict__ cr = a.taps;                            // [tp] re, then [tp] -im
+  const float* __restrict__ cn = a.taps + a.tp;
+  const int nstep = a.tp / kBankW, nfull = a.T / kBankW;
+  for (int b = 0; b < nstep; ++b) {
+    const int at = o0 + a.tp - 8 - 8 * b;                           // d[o0 - 8 b - 7 ..]
+    const float4 r0 = *reinterpret_cast<const float4*>(sr + at), r1 = *reinterpret_cast<const float4*>(sr + at + 4);
+    const float4 i0 = *reinterpret_cast<const float4*>(si + at), i1 = *reinterpret_cast<const float4*>(si + at + 4);
+    wr[0] = r0.x; wr[1] = r0.y; wr[2] = r0.z; wr[3] = r0.w; wr[4] = r1.x; wr[5] = r1.y; wr[6] = r1.z; wr[7] = r1.w;
+    wi[0] = i0.x; wi[1] = i0.y; wi[2] = i0.z; wi[3] = i0.w; wi[4] = i1.x; wi[5] = i1.y; wi[6] = i1.z; wi[7] = i1.w;
+    if (b < nfull) bank_step_cplx<false>(cr + 8 * b, cn + 8 * b, 8, wr, wi, acc);
+    else bank_step_cplx<true>(cr + 8 * b, cn + 8 * b, a.T - 8 * b, wr, wi, acc);
+#pragma unroll
+    for (int q = 0; q < 7; ++q) { wr[8 + q] = wr[q]; wi[8 + q] = wi[q]; }
+  }
+
+  const int ib = tile0 + o0;
+  float* out = a.a + (size_t)row * (size_t)a.apitch;
+  float m = 0.f;
+  if (ib + kBankW <= a.n_out) {
+    float4* o = reinterpret_cast<float4*>(out + ib);
+    o[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    o[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
+  }
+#pragma unroll
+  for (int j = 0; j < kBankW; ++j)
+    if (ib + j < a.n_out) {
+      if (ib + kBankW > a.n_out) out[ib + j] = acc[j];
+      m = nanmax(m, fabsf(acc[j]));
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = nanmax(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) wmax[tid >> 6] = m;
+  __syncthreads();
+  if (tid == 0) {
+    float mm = wmax[0];
+#pragma unroll
+    for (int v = 1; v < kBankThreads / 64; ++v) mm = nanmax(mm, wmax[v]);
+    a.pmax[(size_t)row * a.ptiles + blockIdx.x] = mm;
+    a.psum[(size_t)row * a.ptiles + blockIdx.x] = 0.0;
+  }
+}
+
 }  // namespace
 
 int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st) {
   const size_t lds = (size_t)p.lds_floats * sizeof(float);
-  if (mode == PYSDR_AM) hipLaunchKernelGGL(bank_kernel<PYSDR_AM>, dim3(ntiles, nk), dim3(kBankThreads), lds, st, a);
-  else hipLaunchKernelGGL(bank_kernel<PYSDR_NFM>, dim3(ntiles, nk), dim3(kBankThreads), lds, st, a);
+  const dim3 grid(ntiles, nk), block(kBankThreads);
+  if (mode == PYSDR_AM) hipLaunchKernelGGL(bank_kernel<PYSDR_AM>, grid, block, lds, st, a);
+  else if (mode == PYSDR_NFM) hipLaunchKernelGGL(bank_kernel<PYSDR_NFM>, grid, block, lds, st, a);
+  else if (mode == PYSDR_USB || mode == PYSDR_LSB) hipLaunchKernelGGL(bank_cplx_kernel<false>, grid, block, 2 * lds, st, a);
+  else if (mode == PYSDR_CW) hipLaunchKernelGGL(bank_cplx_kernel<true>, grid, block, 2 * lds, st, a);
+  else { set_last_error("launch_bank: mode %d", mode); return PYSDR_ERR_ARG; }
   PYSDR_HIP_CHECK(hipGetLastError());
   return PYSDR_OK;
 }

@@ -126,7 +126,7 @@ constexpr float kAgcRefDefault = 0.5f;
 struct BankPlan {
   int tp = 0;          // taps rounded up to whole steps of 8
   int hpad = 0;        // history samples kept in front of a row, >= T + 1, a multiple of 8
-  int lds_floats = 0;  // kBankTile + tp
+  int lds_floats = 0;  // kBankTile + tp (the complex-tap modes hold two such planes)
   int tiles = 0;       // per row, for max_out outputs
 };
 
@@ -152,12 +152,14 @@ struct BankArgs {
   float* a;               // a[a * apitch + i]
   long long apitch;
   int n_out, T, tp;
-  const float* taps;      // [tp], zero beyond T (never multiplied: 0 * NaN would widen a NaN's footprint)
+  const float* taps;      // [tp], zero beyond T (never multiplied: 0 * NaN would widen a NaN's footprint); USB / LSB / CW: [2 tp], re then -im
   float fm_scale;
   int noise;              // 1: leave the squelch's partial sums
   float* pmax;            // [nk][ptiles]
   double* psum;           // [nk][ptiles]
   int ptiles;
+  uint32_t m0_lo;         // CW: low 32 bits of the absolute index of the call's first output
+  uint32_t fword;         // CW: the BFO's phase increment per output
 };
 
 struct FinishArgs {
@@ -169,11 +171,11 @@ struct FinishArgs {
   const float* pmax;
   const double* psum;
   BankState* state;
-  int agc_active;         // AGC enabled and mode AM
+  int agc_active;         // AGC enabled and mode AM, USB, LSB or CW
   int squelch;            // mode NFM and threshold > 0
   float ref, thresh;
 };
-int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st);   // mode: PYSDR_AM | PYSDR_NFM
+int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st);   // mode: PYSDR_AM | PYSDR_NFM | PYSDR_USB | PYSDR_LSB | PYSDR_CW
 int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st);
 
 }  // namespace pysdr

@@ -1,7 +1,9 @@
 """Rate probe of the channel bank (bank.hip): AM / NFM audio of every channel of a raster, against
 the only other way to the same result, six sub-receivers per context (``bench.py --workload rx6``).
 
-    python scripts/bank_rate.py [--no-rx6] [--one M D FS MODE]     (--one: a single shape, a few calls: for a profiler run)
+    python scripts/bank_rate.py [--no-rx6] [--modes AM,USB] [--one M D FS MODE]
+        (--one: a single shape, a few calls: for a profiler run; MODE may be NFM, AM, USB or CW.
+         --modes: the modes of the table, default NFM,AM; USB and CW run ``SidebandBank``)
 
 Device-resident input of 2^25 samples per call, default prototype, all M channels, 255 AF taps at 4 kHz; the results
 stay on the device.  At least 20 ms of warm-up, then at least 60 ms of queued calls ending in one synchronise.  Per shape
@@ -22,12 +24,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from pysdr_amd import _lib                                    # noqa: E402
-from pysdr_amd.bank import ChannelBank, plan                  # noqa: E402
+from pysdr_amd.bank import BANK_MODES, ChannelBank, SidebandBank, plan      # noqa: E402
 from pysdr_amd.channelizer import Channelizer                 # noqa: E402
 
 N_CALL = 1 << 25
 SHAPES = [(3.2e6, 256, 128), (8e6, 640, 320), (51.2e6, 4096, 2048)]        # 12.5 kHz rasters, fs_out = 25 kHz
 MODES = [("NFM", dict(squelch=0.3)), ("AM", dict(agc=True))]
+SIDEBAND = [("USB", dict(agc=True, af_bw=3e3)), ("CW", dict(agc=True, af_bw=500.0))]     # 255 complex taps; CW at 700 Hz
 RX6_FS, RX6_FS_OUT = 8e6, 48e3
 
 
@@ -73,7 +76,8 @@ def chan_time(lib, d_x, fs, M, D, quick=False):
 
 
 def bank_time(d_x, fs, M, D, mode, kw, quick=False):
-    b = ChannelBank(fs, M, D, mode=mode, af_bw=4e3, ntaps_af=255, max_in=N_CALL, **kw)
+    kw = dict(dict(af_bw=4e3), **kw)
+    b = (ChannelBank if mode in BANK_MODES else SidebandBank)(fs, M, D, mode=mode, ntaps_af=255, max_in=N_CALL, **kw)
     per = timed(lambda: b.push_device(d_x.value, N_CALL, sync=False), b.sync, quick)
     b.close()
     return per
@@ -99,13 +103,17 @@ def main():
     if "--one" in sys.argv:
         i = sys.argv.index("--one")
         M, D, fs, mode = int(sys.argv[i + 1]), int(sys.argv[i + 2]), float(sys.argv[i + 3]), sys.argv[i + 4]
-        per = bank_time(d_x, fs, M, D, mode, dict(MODES)[mode], quick=True)
+        per = bank_time(d_x, fs, M, D, mode, dict(MODES + SIDEBAND)[mode], quick=True)
         print(f"M {M} D {D} {mode}: {per * 1e3:.3f} ms per call of 2^25 samples, {N_CALL / per / 1e9:.2f} GS/s")
         return 0
+    modes = MODES
+    if "--modes" in sys.argv:
+        want = sys.argv[sys.argv.index("--modes") + 1].split(",")
+        modes = [(m, dict(MODES + SIDEBAND)[m]) for m in want]
     rows = []
     for fs, M, D in SHAPES:
         tc = chan_time(lib, d_x, fs, M, D)
-        for mode, kw in MODES:
+        for mode, kw in modes:
             tb = bank_time(d_x, fs, M, D, mode, kw)
             rows.append(dict(fs=fs, M=M, D=D, mode=mode, kw=kw, ms=tb * 1e3, chan_ms=tc * 1e3, gsps=N_CALL / tb / 1e9,
                              demod_sps=N_CALL / tb * M / D))
@@ -119,7 +127,7 @@ def main():
     for r in rows:
         p = plan(r["M"], 255, N_CALL // r["D"])
         txt = (f"bank {r['fs'] / 1e6:g} MS/s M {r['M']} D {r['D']} {r['mode']} {r['kw']} ({p['tile']} outputs / workgroup, "
-               f"{p['threads']} threads, {p['lds_bytes']} B LDS): {r['ms']:.3f} ms per call of 2^25 = {r['gsps']:.2f} GS/s input, "
+               f"{p['threads']} threads, {p['lds_bytes'] * (1 if r['mode'] in BANK_MODES else 2)} B LDS): {r['ms']:.3f} ms per call of 2^25 = {r['gsps']:.2f} GS/s input, "
                f"{r['demod_sps'] / 1e9:.2f} G demodulated channel-samples/s; the channelizer alone {r['chan_ms']:.3f} ms = "
                f"{100 * r['chan_ms'] / r['ms']:.0f} % of the time")
         if ref is not None:
