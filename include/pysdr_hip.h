@@ -392,6 +392,52 @@ int  pysdr_bank_state(pysdr_bank* b, float* agc, float* gain, float* maxbuf, flo
 int  pysdr_bank_fetch(pysdr_bank* b, const int* rows, int nrows, float* am, float* iq, long long pitch);
 int  pysdr_bank_sync(pysdr_bank* b);
 
+/* ---- CW skimmer: a Morse decoder on every row of a channelizer (a build feature with a definition
+ * of its own: the reference holds no Morse decoder) ----------------------------------------------------------------------
+ * Every row a < nk of the channelizer `ch` gets one decoder that walks the power of the row's samples y[m] (bit for bit
+ * what pysdr_chan_process delivers) in order: envelope, peak and noise-floor followers in float32 with every operation
+ * rounded on its own, a key decision with hysteresis, and from there integer arithmetic -- mark lengths, a dot length
+ * that follows adjacent short / long marks, the element string `code` behind a leading 1 (dot appends 0, dash 1; 0 = more
+ * than 7 elements), character and word-space events.  DESIGN.md 3 item 18 is the normative text, step by step.  The
+ * settings hold for the whole bank and arrive already derived (pysdr_amd.cw.params): the smoothing constants a_s, a_p,
+ * a_n in (0, 1], snr_min, hi >= lo and fl > 0, and the dot lengths d0, dmin, dmax in 1 / 16 sample with
+ * 16 <= dmin <= d0 <= dmax <= 2^22, and the number n0 of settling samples in [1, 2^22] during which the noise floor
+ * is the peak and no key decision is made (seen counts them; they cover the run-in of the channelizer's filter).  Any cut of a stream into calls gives the same events and the same state bits; a call
+ * that completes no output launches nothing and changes no state.
+ * pysdr_cw_plan needs no device: PYSDR_ERR_ARG for nk outside [1, 4096], max_out outside [1, 2^21] or a cfg outside
+ * these rules, else out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, 0, 0}; the event
+ * cap 2 (max_out / 3 + 1) is the most events one channel can emit in a call of max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it (pysdr_chan_reset); while a skimmer exists, feed ch
+ * only through it.  reset also resets the channelizer.
+ * process: iq as in pysdr_chan_process (device pointer where on_device != 0); the decoder is queued behind the
+ * channelizer on the channelizer's stream.  counts[nk] (events of every row in this call) and
+ * events[a * ev_pitch + j], j < counts[a], are host buffers or NULL: with NULL the results stay on the device (and a call
+ * with device input and no host buffer only queues work; pysdr_cw_sync waits for it).  An event word is
+ * (index of the output within the call) << 9 | c, c = the character's code 0 .. 255, or 256 = word space.
+ * PYSDR_ERR_STATE: n > max_in of the channelizer, the call would complete more than max_out outputs, or ev_pitch smaller
+ * than the event cap; the stream does not advance.
+ * fetch: the last call's event slots of the named rows only, events[i * pitch + j] for rows[i], pitch >= the event cap;
+ * runs of consecutive rows go as one strided copy.  After a call that completed no output it copies nothing.
+ * state: s, pk, nf [nk] and ints [nk][8] = key, run, dot, last, code, nel, sp, seen of every channel; NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_cw_cfg {
+  float a_s, a_p, a_n;      /* smoothing constants of the envelope, the peak's decay and the noise floor */
+  float snr_min, hi, lo;    /* presence: pk > snr_min nf; key down above q hi, up below q lo */
+  float fl;                 /* floor of the threshold: q >= pk^2 fl */
+  int32_t d0, dmin, dmax;   /* dot length at the start and its limits, 1 / 16 sample */
+  int32_t n0;               /* settling samples after create / reset: nf = pk and the key stays up; 1 <= n0 <= 2^22 */
+} pysdr_cw_cfg;
+typedef struct pysdr_cw pysdr_cw;
+int  pysdr_cw_plan(int nk, int max_out, const pysdr_cw_cfg* cfg, int32_t out[8]);
+int  pysdr_cw_create(pysdr_chan* ch, const pysdr_cw_cfg* cfg, int max_out, pysdr_cw** out);
+void pysdr_cw_destroy(pysdr_cw* cw);
+int  pysdr_cw_reset(pysdr_cw* cw);
+int  pysdr_cw_sync(pysdr_cw* cw);
+int  pysdr_cw_process(pysdr_cw* cw, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                      long long ev_pitch);
+int  pysdr_cw_fetch(pysdr_cw* cw, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_cw_state(pysdr_cw* cw, float* s, float* pk, float* nf, int32_t* ints);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -40,6 +40,12 @@ class Out(C.Structure):
                 ("am_is_complex", C.c_int32), ("peak_in", C.c_float)]
 
 
+class CwCfg(C.Structure):
+    _fields_ = [("a_s", C.c_float), ("a_p", C.c_float), ("a_n", C.c_float),
+                ("snr_min", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("fl", C.c_float),
+                ("d0", C.c_int32), ("dmin", C.c_int32), ("dmax", C.c_int32), ("n0", C.c_int32)]
+
+
 _vp, _i, _sz, _d, _f, _u32 = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 
@@ -130,6 +136,14 @@ PROTOTYPES = {
     "pysdr_bank_state": (_i, [_vp, _pf, _pf, _pf, _pf, C.POINTER(C.c_uint8)]),
     "pysdr_bank_fetch": (_i, [_vp, _pi, _i, _pf, _pf, C.c_longlong]),
     "pysdr_bank_sync": (_i, [_vp]),
+    "pysdr_cw_plan": (_i, [_i, _i, C.POINTER(CwCfg), C.POINTER(C.c_int32)]),
+    "pysdr_cw_create": (_i, [_vp, C.POINTER(CwCfg), _i, C.POINTER(_vp)]),
+    "pysdr_cw_destroy": (None, [_vp]),
+    "pysdr_cw_reset": (_i, [_vp]),
+    "pysdr_cw_sync": (_i, [_vp]),
+    "pysdr_cw_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong]),
+    "pysdr_cw_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
+    "pysdr_cw_state": (_i, [_vp, _pf, _pf, _pf, C.POINTER(C.c_int32)]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

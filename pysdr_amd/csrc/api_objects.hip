@@ -181,6 +181,18 @@ int bank_reset_locked(pysdr_bank* b) {
 
 }  // namespace
 
+namespace pysdr {
+
+int chan_info(pysdr_chan* c, ChanInfo* out) {
+  if (!c || !out) { set_last_error("chan_info: NULL channelizer or out"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(c->mu);
+  out->device = c->device; out->M = c->M; out->D = c->D; out->nk = c->nk; out->max_in = c->max_in;
+  out->stream = c->stream; out->n_abs = c->n_abs;
+  return PYSDR_OK;
+}
+
+}  // namespace pysdr
+
 extern "C" {
 
 // ---- waterfall ---------------------------------------------------------------------------

@@ -1,8 +1,9 @@
 // What the four stream objects -- waterfall, RTTY decoder bank, channelizer, channel bank -- share between their kernels
 // (waterfall.hip, rtty.hip, chan.hip, bank.hip), their host half (api_objects.hip) and the checking launch layer of
 // tests/host_san: constants, pure plans, kernel argument structs, and DECLARATIONS ONLY of the launch functions (defined in
-// the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  Nothing in this header calls the
-// HIP runtime; plain C++.  Not part of the public ABI.
+// the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  At its end: what the CW skimmer
+// (api_cw.hip, cw.hip; its plan and step: cw_plan.h) needs of a borrowed channelizer, and its launch.  Nothing in this
+// header calls the HIP runtime; plain C++.  Not part of the public ABI.
 #pragma once
 
 #include "common.h"
@@ -177,5 +178,16 @@ struct FinishArgs {
 };
 int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st);   // mode: PYSDR_AM | PYSDR_NFM | PYSDR_USB | PYSDR_LSB | PYSDR_CW
 int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st);
+
+// ---- CW skimmer (cw.hip, host half api_cw.hip; plan, state and kernel arguments: cw_plan.h) ----------------------------
+// What an object that borrows a channelizer needs of it (api_objects.hip; taken under the channelizer's lock).
+struct ChanInfo {
+  int device, M, D, nk, max_in;
+  hipStream_t stream;             // every launch and copy of the channelizer is queued here
+  unsigned long long n_abs;       // input samples since create / reset
+};
+int chan_info(pysdr_chan* c, ChanInfo* out);
+struct CwArgs;
+int launch_cw_decode(const CwArgs& a, hipStream_t st);
 
 }  // namespace pysdr
