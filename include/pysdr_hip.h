@@ -438,6 +438,53 @@ int  pysdr_cw_process(pysdr_cw* cw, const void* iq, int n, int on_device, int* n
 int  pysdr_cw_fetch(pysdr_cw* cw, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_cw_state(pysdr_cw* cw, float* s, float* pk, float* nf, int32_t* ints);
 
+/* ---- PSK31 skimmer: a Varicode decoder on a fine raster inside every row of a channelizer (a build
+ * feature with a definition of its own: the reference holds no PSK decoder) ------------------------------------------------
+ * The channelizer `ch` delivers rows at fs_out = S baud, S = 8 or 12 samples per symbol.  Inside every row a < nk a bank
+ * of NSUB = 4 S decoders runs, decoder j tuned (2 j - NSUB + 1) baud / 32 from the row's centre; fine row F = a NSUB + j.
+ * Each mixes the row down (table tw[NT][2] = (cos, -sin)(2 pi t / NT), NT = 32 S, indexed by (q k) mod NT of the absolute
+ * output index k), applies the matched filter g[L], L = 2 S, follows the symbol energy at every phase of the symbol,
+ * takes one symbol per S + d samples at the best phase, decides the differential bit, measures the coherence qn / qd of
+ * the doubled differential phase (the squelch `open`) and shifts Varicode bits until 00.  All float arithmetic is
+ * float32 with every operation rounded on its own; DESIGN.md 3 item 19 is the normative text, step by step.  The
+ * settings hold for the whole bank: a_t, a_q in (0, 1], 0 < lo <= hi, hy > 0, 0 < pmax <= 1e18 (all finite), 1 <= n0 <= 2^22
+ * settling symbols during which the squelch stays shut.  Any cut of a stream into calls gives the same events and the
+ * same state bits; a call that completes no output launches nothing and changes no state.
+ * pysdr_psk_plan needs no device: PYSDR_ERR_ARG for S not 8 or 12, nk < 1, nk NSUB > 2^18, max_out outside [1, 2^20] or a
+ * cfg outside these rules, else out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups,
+ * NSUB, 0}; the event cap max_out / (3 S / 2) + 1 is the most events one decoder can emit in a call of max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and g are host arrays of NT x 2 and L floats, copied.  reset also resets the channelizer.
+ * process: iq as in pysdr_chan_process (device pointer where on_device != 0); the decoders are queued behind the
+ * channelizer on the channelizer's stream.  counts[nk NSUB] (events of every fine row in this call), events[F * ev_pitch
+ * + i], i < counts[F], and the end state's qn[nk NSUB] and open[nk NSUB] are host buffers or NULL: with NULL the results
+ * stay on the device (and a call with device input and no host buffer only queues work; pysdr_psk_sync waits for it).
+ * An event word is (index of the output within the call) << 11 | code, code = the Varicode bits 1 .. 2047.
+ * PYSDR_ERR_STATE: n > max_in of the channelizer, the call would complete more than max_out outputs, or ev_pitch smaller
+ * than the event cap; the stream does not advance.
+ * fetch: the last call's event slots of the named fine rows only, events[i * pitch + k] for rows[i], pitch >= the event
+ * cap; runs of consecutive rows go as one strided copy.  After a call that completed no output it copies nothing.
+ * state: e [S][nk NSUB], f [4][nk NSUB] = qn, qd, cr, ci and ints [5][nk NSUB] = pt, cnt, sh, open, seen; NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_psk_cfg {
+  float a_t, a_q;           /* smoothing constants of the symbol energies and of the coherence sums */
+  float hi, lo;             /* squelch: opens at qn >= hi qd, shuts below lo qd */
+  float hy;                 /* the timing phase moves when the best energy exceeds hy times the current one */
+  float pmax;               /* outputs of power above this (or not finite) are blanked */
+  int32_t n0;               /* settling symbols after create / reset */
+} pysdr_psk_cfg;
+typedef struct pysdr_psk pysdr_psk;
+int  pysdr_psk_plan(int nk, int S, int max_out, const pysdr_psk_cfg* cfg, int32_t out[8]);
+int  pysdr_psk_create(pysdr_chan* ch, int S, const pysdr_psk_cfg* cfg, const float* tw, const float* g, int max_out,
+                      pysdr_psk** out);
+void pysdr_psk_destroy(pysdr_psk* psk);
+int  pysdr_psk_reset(pysdr_psk* psk);
+int  pysdr_psk_sync(pysdr_psk* psk);
+int  pysdr_psk_process(pysdr_psk* psk, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch, float* qn, int32_t* open);
+int  pysdr_psk_fetch(pysdr_psk* psk, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_psk_state(pysdr_psk* psk, float* e, float* f, int32_t* ints);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -46,6 +46,11 @@ class CwCfg(C.Structure):
                 ("d0", C.c_int32), ("dmin", C.c_int32), ("dmax", C.c_int32), ("n0", C.c_int32)]
 
 
+class PskCfg(C.Structure):
+    _fields_ = [("a_t", C.c_float), ("a_q", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("hy", C.c_float),
+                ("pmax", C.c_float), ("n0", C.c_int32)]
+
+
 _vp, _i, _sz, _d, _f, _u32 = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 
@@ -144,6 +149,15 @@ PROTOTYPES = {
     "pysdr_cw_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong]),
     "pysdr_cw_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
     "pysdr_cw_state": (_i, [_vp, _pf, _pf, _pf, C.POINTER(C.c_int32)]),
+    "pysdr_psk_plan": (_i, [_i, _i, _i, C.POINTER(PskCfg), C.POINTER(C.c_int32)]),
+    "pysdr_psk_create": (_i, [_vp, _i, C.POINTER(PskCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_psk_destroy": (None, [_vp]),
+    "pysdr_psk_reset": (_i, [_vp]),
+    "pysdr_psk_sync": (_i, [_vp]),
+    "pysdr_psk_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong, _pf,
+                               C.POINTER(C.c_int32)]),
+    "pysdr_psk_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
+    "pysdr_psk_state": (_i, [_vp, _pf, _pf, C.POINTER(C.c_int32)]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -1,0 +1,222 @@
+// C ABI of the PSK31 skimmer (include/pysdr_hip.h).  Host-side only, like api_cw.hip: the kernel and
+// its launch function live in psk.hip, what both sides share in psk_plan.h.  The skimmer borrows a channelizer as the CW
+// skimmer does and queues its decoders behind the channelizer's launch on the channelizer's stream, with no host
+// synchronisation in between.  Every device resource is an owner (host_res.h): deleting the object frees it.
+#include "psk_plan.h"
+#include "host_res.h"
+#include "objects_plan.h"
+
+using namespace pysdr;
+
+struct pysdr_psk {
+  pysdr_chan* ch = nullptr;         // borrowed; outlives the skimmer
+  int device = 0, D = 0, nk = 0, max_in = 0, max_out = 0;   // of the channelizer, fixed at its create; max_out: ours
+  hipStream_t stream = nullptr;     // the channelizer's
+  pysdr_psk_cfg cfg{};
+  PskPlan plan;
+  int last_n_out = 0;
+  DevBuf<PskC> d_y;                 // [nk][ypitch]: kPskHpad of history room, then the call's outputs
+  DevBuf<PskC> d_tw;                // [NT]
+  DevBuf<float> d_g;                // [L]
+  DevBuf<float> d_e;                // [S][nfine]
+  DevBuf<float> d_sf;               // [4][nfine]
+  DevBuf<int32_t> d_si;             // [5][nfine]
+  DevBuf<int32_t> d_events;         // [nfine][cap]
+  DevBuf<int32_t> d_counts;         // [nfine]
+  std::vector<float> h_tw, h_g;
+  std::vector<int32_t> h_si;        // the state after create / reset
+  std::mutex mu;                    // one call at a time on a handle
+};
+
+namespace {
+
+int psk_alloc(pysdr_psk* w) {
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine, S = (size_t)w->plan.S;
+  PYSDR_HIP_CHECK(w->d_y.alloc(nk * (size_t)w->plan.ypitch));
+  PYSDR_HIP_CHECK(w->d_tw.alloc(32 * S));
+  PYSDR_HIP_CHECK(w->d_g.alloc(2 * S));
+  PYSDR_HIP_CHECK(w->d_e.alloc(S * nf));
+  PYSDR_HIP_CHECK(w->d_sf.alloc((size_t)kPskStateFloats * nf));
+  PYSDR_HIP_CHECK(w->d_si.alloc((size_t)kPskStateInts * nf));
+  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap));
+  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
+  return PYSDR_OK;
+}
+
+int psk_reset_locked(pysdr_psk* w) {
+  const int rc = pysdr_chan_reset(w->ch);
+  if (rc != PYSDR_OK) return rc;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine, S = (size_t)w->plan.S;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // the host arrays may still feed an earlier copy
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_tw.get(), w->h_tw.data(), w->h_tw.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_g.get(), w->h_g.data(), w->h_g.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_si.get(), w->h_si.data(), w->h_si.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_y.get(), 0, nk * (size_t)w->plan.ypitch * sizeof(PskC), st));   // y[k] = 0 for k < 0
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_e.get(), 0, S * nf * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sf.get(), 0, (size_t)kPskStateFloats * nf * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  w->last_n_out = 0;
+  return PYSDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pysdr_psk_plan(int nk, int S, int max_out, const pysdr_psk_cfg* cfg, int32_t out[8]) {
+  if (!out) { set_last_error("pysdr_psk_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  PskPlan p;
+  if (!psk_plan(nk, S, max_out, cfg, &p)) {
+    set_last_error("pysdr_psk_plan: S %d is neither 8 nor 12, nk %d < 1 or nk 4 S > %d, max_out %d outside [1, %d], or a cfg outside the "
+                   "rules (NULL; a_t, a_q in (0, 1]; 0 < lo <= hi, hy > 0, 0 < pmax <= 1e18, all finite; 1 <= n0 <= %d)", S, nk,
+                   kPskFineMax, max_out, kPskMaxOutMax, kPskSettleMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = psk_rows(S); out[1] = psk_threads(S); out[2] = psk_lds_bytes(S); out[3] = kPskTile; out[4] = p.cap; out[5] = p.groups;
+  out[6] = p.nsub; out[7] = 0;
+  return PYSDR_OK;
+}
+
+int pysdr_psk_create(pysdr_chan* ch, int S, const pysdr_psk_cfg* cfg, const float* tw, const float* g, int max_out, pysdr_psk** out) {
+  if (!out) { set_last_error("pysdr_psk_create: out is NULL"); return PYSDR_ERR_ARG; }
+  *out = nullptr;
+  if (!ch || !cfg || !tw || !g) { set_last_error("pysdr_psk_create: NULL channelizer, cfg, tw or g"); return PYSDR_ERR_ARG; }
+  ChanInfo ci;
+  int rc = chan_info(ch, &ci);
+  if (rc != PYSDR_OK) return rc;
+  int32_t pl[8];
+  rc = pysdr_psk_plan(ci.nk, S, max_out, cfg, pl);
+  if (rc != PYSDR_OK) return rc;
+  pysdr_psk* w = new pysdr_psk();
+  w->ch = ch; w->device = ci.device; w->D = ci.D; w->nk = ci.nk; w->max_in = ci.max_in; w->stream = ci.stream;
+  w->max_out = max_out; w->cfg = *cfg;
+  psk_plan(w->nk, S, max_out, cfg, &w->plan);
+  w->h_tw.assign(tw, tw + 2 * 32 * (size_t)S);
+  w->h_g.assign(g, g + 2 * (size_t)S);
+  const size_t nf = (size_t)w->plan.nfine;
+  w->h_si.assign((size_t)kPskStateInts * nf, 0);
+  for (size_t i = 0; i < nf; ++i) w->h_si[nf + i] = S;                 // cnt = S
+  rc = use_device(w->device);
+  if (rc) { delete w; return rc; }
+  rc = psk_alloc(w);
+  if (rc) { failed_in("pysdr_psk_create", rc); pysdr_psk_destroy(w); return rc; }
+  rc = psk_reset_locked(w);
+  if (rc != PYSDR_OK) { pysdr_psk_destroy(w); return rc; }
+  *out = w;
+  return PYSDR_OK;
+}
+
+void pysdr_psk_destroy(pysdr_psk* w) {
+  if (!w) return;
+  (void)hipSetDevice(w->device);
+  if (w->stream) (void)hipStreamSynchronize(w->stream);
+  delete w;                               // (the owners free: host_res.h)
+}
+
+int pysdr_psk_reset(pysdr_psk* w) {
+  if (!w) { set_last_error("pysdr_psk_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  return psk_reset_locked(w);
+}
+
+int pysdr_psk_sync(pysdr_psk* w) {
+  if (!w) { set_last_error("pysdr_psk_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
+  return PYSDR_OK;
+}
+
+int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                      long long ev_pitch, float* qn, int32_t* open) {
+  if (!w || !n_out) { set_last_error("pysdr_psk_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
+  *n_out = 0;
+  std::lock_guard<std::mutex> lk(w->mu);
+  if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_psk_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
+  if (n > w->max_in) { set_last_error("pysdr_psk_process: n %d > max_in %d", n, w->max_in); return PYSDR_ERR_STATE; }
+  if (events && ev_pitch < w->plan.cap) {
+    set_last_error("pysdr_psk_process: ev_pitch %lld < the event cap %d", ev_pitch, w->plan.cap);
+    return PYSDR_ERR_STATE;
+  }
+  // what the channelizer is about to complete: checked before it advances its stream
+  ChanInfo ci;
+  int rc = chan_info(w->ch, &ci);
+  if (rc != PYSDR_OK) return rc;
+  const unsigned long long D = (unsigned long long)w->D, s0 = ci.n_abs, s1 = s0 + (unsigned long long)n;
+  const unsigned long long m0 = (s0 + D - 1) / D, nf_want = (s1 + D - 1) / D - m0;
+  if (nf_want > (unsigned long long)w->max_out) {
+    set_last_error("pysdr_psk_process: the call would complete %llu outputs, max_out is %d", nf_want, w->max_out);
+    return PYSDR_ERR_STATE;
+  }
+  int nf = 0;
+  rc = pysdr_chan_process(w->ch, iq, n, on_device, w->d_y.get() + kPskHpad, w->plan.ypitch, 1, &nf);
+  if (rc != PYSDR_OK) return rc;
+  if (nf != (int)nf_want) { set_last_error("pysdr_psk_process: the channelizer was fed beside its skimmer (%d outputs, %d expected)", nf, (int)nf_want); return PYSDR_ERR_STATE; }
+  w->last_n_out = nf;
+  const size_t nfine = (size_t)w->plan.nfine;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
+    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
+  } else {
+    PskArgs a{};
+    a.y = w->d_y.get() + kPskHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.m0_mod = (int)(m0 % (unsigned long long)(32 * w->plan.S));
+    a.cfg = w->cfg; a.tw = w->d_tw.get(); a.g = w->d_g.get();
+    a.e = w->d_e.get(); a.sf = w->d_sf.get(); a.si = w->d_si.get(); a.events = w->d_events.get(); a.counts = w->d_counts.get();
+    rc = launch_psk_decode(w->plan.S, a, st);
+    if (rc) return rc;
+    *n_out = nf;
+    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (events)
+      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)a.cap * sizeof(int32_t),
+                                       (size_t)a.cap * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
+  }
+  if (qn) PYSDR_HIP_CHECK(hipMemcpyAsync(qn, w->d_sf.get(), nfine * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (open) PYSDR_HIP_CHECK(hipMemcpyAsync(open, w->d_si.get() + 3 * nfine, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (counts || events || qn || open || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
+  return PYSDR_OK;
+}
+
+int pysdr_psk_fetch(pysdr_psk* w, const int* rows, int nrows, int32_t* events, long long pitch) {
+  if (!w) { set_last_error("pysdr_psk_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
+  if (nrows < 0 || (nrows > 0 && (!rows || !events))) { set_last_error("pysdr_psk_fetch: nrows %d / NULL rows or events", nrows); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  for (int i = 0; i < nrows; ++i)
+    if (rows[i] < 0 || rows[i] >= w->plan.nfine) { set_last_error("pysdr_psk_fetch: fine row %d outside [0, %d)", rows[i], w->plan.nfine); return PYSDR_ERR_ARG; }
+  const size_t cap = (size_t)w->plan.cap;
+  if (pitch < (long long)cap) { set_last_error("pysdr_psk_fetch: pitch %lld < the event cap %d", pitch, w->plan.cap); return PYSDR_ERR_STATE; }
+  if (w->last_n_out == 0 || nrows == 0) return PYSDR_OK;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  for (int i = 0; i < nrows; ++i) {
+    // runs of consecutive rows go as one strided copy
+    int run = 1;
+    while (i + run < nrows && rows[i + run] == rows[i] + run) ++run;
+    PYSDR_HIP_CHECK(hipMemcpy2DAsync(events + (size_t)i * pitch, (size_t)pitch * sizeof(int32_t),
+                                     w->d_events.get() + (size_t)rows[i] * cap, cap * sizeof(int32_t), cap * sizeof(int32_t),
+                                     (size_t)run, hipMemcpyDeviceToHost, st));
+    i += run - 1;
+  }
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  return PYSDR_OK;
+}
+
+int pysdr_psk_state(pysdr_psk* w, float* e, float* f, int32_t* ints) {
+  if (!w) { set_last_error("pysdr_psk_state: NULL skimmer"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nf = (size_t)w->plan.nfine;
+  if (e) PYSDR_HIP_CHECK(hipMemcpyAsync(e, w->d_e.get(), (size_t)w->plan.S * nf * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (f) PYSDR_HIP_CHECK(hipMemcpyAsync(f, w->d_sf.get(), (size_t)kPskStateFloats * nf * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (ints) PYSDR_HIP_CHECK(hipMemcpyAsync(ints, w->d_si.get(), (size_t)kPskStateInts * nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  return PYSDR_OK;
+}
+
+}  // extern "C"

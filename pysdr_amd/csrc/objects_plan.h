@@ -2,7 +2,8 @@
 // (waterfall.hip, rtty.hip, chan.hip, bank.hip), their host half (api_objects.hip) and the checking launch layer of
 // tests/host_san: constants, pure plans, kernel argument structs, and DECLARATIONS ONLY of the launch functions (defined in
 // the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  At its end: what the CW skimmer
-// (api_cw.hip, cw.hip; its plan and step: cw_plan.h) needs of a borrowed channelizer, and its launch.  Nothing in this
+// (api_cw.hip, cw.hip; its plan and step: cw_plan.h) needs of a borrowed channelizer, and its launch; the PSK31 skimmer's
+// launch (api_psk.hip, psk.hip; psk_plan.h).  Nothing in this
 // header calls the HIP runtime; plain C++.  Not part of the public ABI.
 #pragma once
 
@@ -189,5 +190,9 @@ struct ChanInfo {
 int chan_info(pysdr_chan* c, ChanInfo* out);
 struct CwArgs;
 int launch_cw_decode(const CwArgs& a, hipStream_t st);
+
+// ---- PSK31 skimmer (psk.hip, host half api_psk.hip; plan, steps and kernel arguments: psk_plan.h) ----------------------
+struct PskArgs;
+int launch_psk_decode(int S, const PskArgs& a, hipStream_t st);
 
 }  // namespace pysdr
