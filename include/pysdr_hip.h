@@ -335,6 +335,27 @@ int  pysdr_chan_sync(pysdr_chan* ch);
 int  pysdr_chan_process(pysdr_chan* ch, const void* iq, int n, int on_device, void* out, long long out_pitch,
                         int out_on_device, int* n_out);
 
+/* ---- fine channelizer: two channelizer stages for bands wider than 4096 channels of the wanted width (DESIGN.md 3 item
+ * 20; a build feature) ------------------------------------------------------------------------------------------------
+ * Stage 1 is the channelizer above with M1, D1, h1 and M1 / D1 in {2, 4}; stage 2 applies the same formula with M2, D2, h2
+ * (M2 = 2^a 5^b in [16, 1024], M2 / D2 in {1, 2, 4}) to every coarse row that is needed, x := the row as stage 1 rounded
+ * it, and keeps the Q = M2 D1 / M1 (even, >= 8) channels q in [-Q/2, Q/2) inside the row's own spacing.  The kept
+ * channels of all coarse rows form one raster of Mf = M1 Q fine channels fs / Mf apart: fine channel G is channel
+ * (G - c Q) mod M2 of coarse row c mod M1, c = floor((G + Q/2) / Q).  The handle is a pysdr_chan with M = Mf, D = D1 D2:
+ * process / reset / sync / destroy above and every object that borrows a channelizer work on it unchanged; row a of the
+ * output is fine channel (g_first + a) mod Mf, a < ng <= min(Mf, 65536); a call that brings the samples [s0, s1) produces
+ * the outputs with s0 <= m D < s1, and any cut of a stream into calls gives the same bits.  The rows of stage 1 never
+ * leave the device.
+ * pysdr_chan_fine_plan needs no device: PYSDR_ERR_ARG for a shape outside these rules, else out = {Q, Mf, D, M2 / D2,
+ * first coarse row, coarse rows used, frames per workgroup, LDS bytes, stage-1 outputs kept in front of every row, taps
+ * per branch of stage 2, passes, radix of pass 0 .. 4 (0 beyond the last)}.
+ * fine_set_taps sets both prototypes (1 <= n <= max_taps of the stage), from the next call on; pysdr_chan_set_taps on a
+ * fine handle and fine_set_taps on a plain one return PYSDR_ERR_STATE. */
+int  pysdr_chan_fine_plan(int M1, int D1, int M2, int D2, int ntaps1, int ntaps2, int g_first, int ng, int32_t out[16]);
+int  pysdr_chan_fine_create(int device, int M1, int D1, int M2, int D2, int g_first, int ng, int max_taps1, int max_taps2,
+                            int max_in, pysdr_chan** out);
+int  pysdr_chan_fine_set_taps(pysdr_chan* ch, const double* h1, int n1, const double* h2, int n2);
+
 /* ---- channel bank: AM / NFM audio, AGC and squelch on every row of a channelizer (a build feature:
  * the reference demodulates one sub-receiver per channel, receiver.py:826-835) -----------------------------------------
  * Every row a < nk of the channelizer `ch` gets a sub-receiver's stage 2 in mode PYSDR_AM or PYSDR_NFM: with y[m] the

@@ -129,6 +129,9 @@ PROTOTYPES = {
     "pysdr_chan_reset": (_i, [_vp]),
     "pysdr_chan_sync": (_i, [_vp]),
     "pysdr_chan_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
+    "pysdr_chan_fine_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_chan_fine_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
+    "pysdr_chan_fine_set_taps": (_i, [_vp, _pd, _i, _pd, _i]),
     "pysdr_bank_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int32)]),
     "pysdr_bank_create": (_i, [_vp, _d, _i, _i, C.POINTER(_vp)]),
     "pysdr_bank_destroy": (None, [_vp]),

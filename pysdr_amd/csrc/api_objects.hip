@@ -5,6 +5,7 @@
 // is destroyed after them; the destroy functions drain it first.
 #include <cmath>
 
+#include "chan_object.h"      // struct pysdr_chan
 #include "host_res.h"
 #include "objects_plan.h"
 
@@ -41,25 +42,6 @@ struct pysdr_rtty {
   DevBuf<double> d_snr;        // [max_dec][nb]
   DevBuf<int> d_held, d_code;  // [max_dec][nb]
   DevBuf<int> d_ndet;          // [max_lines]
-};
-
-struct pysdr_chan {
-  int device = 0, M = 0, D = 0, k_first = 0, nk = 0, max_taps = 0, max_in = 0;
-  int H = 0;               // history kept: ceil(max_taps / M) M - 1 samples
-  int P = 0;               // taps per branch of the current prototype (0: none set yet)
-  int out_cap = 0;         // row pitch of the internal output buffer: most outputs one call can complete, rounded up to 16
-  int cur = 0;             // which history buffer is current
-  unsigned long long n_abs = 0;   // input samples since create / reset
-  ChanPlan plan;
-  Stream stream;           // every launch and copy of the channelizer (and of a bank on it) is queued here
-  DevBuf<float2> d_hist[2];
-  DevBuf<float> d_taps;
-  DevBuf<float2> d_tw;
-  DevBuf<int> d_perm;
-  DevBuf<float2> d_in;     // staging of host input  [max_in]:      allocated by the first call that passes a host pointer
-  DevBuf<float2> d_out;    // staging of host output [nk][out_cap]: likewise
-  std::vector<float> h_taps;
-  std::mutex mu;           // one call at a time on a handle: set_taps / reset / sync / process
 };
 
 struct pysdr_bank {
@@ -187,7 +169,7 @@ int chan_info(pysdr_chan* c, ChanInfo* out) {
   if (!c || !out) { set_last_error("chan_info: NULL channelizer or out"); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(c->mu);
   out->device = c->device; out->M = c->M; out->D = c->D; out->nk = c->nk; out->max_in = c->max_in;
-  out->stream = c->stream; out->n_abs = c->n_abs;
+  out->stream = c->queue(); out->n_abs = c->n_abs;
   return PYSDR_OK;
 }
 
@@ -470,12 +452,14 @@ int pysdr_chan_create(int device, int M, int D, int k_first, int nk, int max_tap
 void pysdr_chan_destroy(pysdr_chan* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->queue()) (void)hipStreamSynchronize(c->queue());
+  if (c->ops) c->ops->destroy(c);
   delete c;
 }
 
 int pysdr_chan_set_taps(pysdr_chan* c, const double* h, int ntaps) {
   if (!c || !h) { set_last_error("pysdr_chan_set_taps: NULL channelizer or taps"); return PYSDR_ERR_ARG; }
+  if (c->ops) { set_last_error("pysdr_chan_set_taps: a fine channelizer takes its two prototypes through pysdr_chan_fine_set_taps"); return PYSDR_ERR_STATE; }
   if (ntaps < 1 || ntaps > c->max_taps) {
     set_last_error("pysdr_chan_set_taps: ntaps %d outside [1, max_taps = %d]", ntaps, c->max_taps);
     return PYSDR_ERR_ARG;
@@ -495,6 +479,7 @@ int pysdr_chan_set_taps(pysdr_chan* c, const double* h, int ntaps) {
 int pysdr_chan_reset(pysdr_chan* c) {
   if (!c) { set_last_error("pysdr_chan_reset: NULL channelizer"); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(c->mu);
+  if (c->ops) return c->ops->reset(c);
   PYSDR_HIP_CHECK(hipSetDevice(c->device));
   PYSDR_HIP_CHECK(hipMemsetAsync(c->d_hist[0].get(), 0, (size_t)c->H * sizeof(float2), c->stream));
   PYSDR_HIP_CHECK(hipMemsetAsync(c->d_hist[1].get(), 0, (size_t)c->H * sizeof(float2), c->stream));
@@ -508,7 +493,7 @@ int pysdr_chan_sync(pysdr_chan* c) {
   if (!c) { set_last_error("pysdr_chan_sync: NULL channelizer"); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(c->mu);
   PYSDR_HIP_CHECK(hipSetDevice(c->device));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(c->stream));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(c->queue()));
   return PYSDR_OK;
 }
 
@@ -517,6 +502,7 @@ int pysdr_chan_process(pysdr_chan* c, const void* iq, int n, int on_device, void
   if (!c || !n_out) { set_last_error("pysdr_chan_process: NULL channelizer or n_out"); return PYSDR_ERR_ARG; }
   *n_out = 0;
   std::lock_guard<std::mutex> lk(c->mu);
+  if (c->ops) return c->ops->process(c, iq, n, on_device, out, out_pitch, out_on_device, n_out);
   if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_chan_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
   if (n > c->max_in) { set_last_error("pysdr_chan_process: n %d > max_in %d", n, c->max_in); return PYSDR_ERR_STATE; }
   if (c->P == 0) { set_last_error("pysdr_chan_process: no taps set"); return PYSDR_ERR_STATE; }
@@ -596,7 +582,7 @@ int pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pys
   {
     std::lock_guard<std::mutex> lk(ch->mu);
     b->ch = ch; b->device = ch->device; b->D = ch->D; b->nk = ch->nk; b->max_in = ch->max_in; b->out_cap = ch->out_cap;
-    b->stream = ch->stream;
+    b->stream = ch->queue();
   }
   if (!bank_plan(b->nk, ntaps_af, b->out_cap, &b->plan)) {
     set_last_error("pysdr_bank_create: ntaps_af %d outside [%d, %d]", ntaps_af, kBankTapsMin, kBankTapsMax);

@@ -1,4 +1,4 @@
-// Owners of what the host half of libpysdr_hip.so (api.hip, api_objects.hip, api_cw.hip, api_psk.hip) holds on the device: typed device and pinned-host buffers,
+// Owners of what the host half of libpysdr_hip.so (api.hip, api_objects.hip, api_cw.hip, api_psk.hip, api_fine.hip) holds on the device: typed device and pinned-host buffers,
 // streams, events, and the two buffers of a pair that overlapped calls alternate between.  Move-only; the destructors
 // free and nothing else does, so a struct of these needs no free list.  Plain C++ over the HIP runtime API.
 #pragma once

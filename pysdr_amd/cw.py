@@ -83,6 +83,14 @@ def plan(nk, max_out, cfg):
     return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5]}
 
 
+def fine_channelizer(fs, band, fs_out, device=0, max_in=1 << 22):
+    """A ``fine.FineChannelizer`` for ``CW_Skimmer(fs, chan=...)``: rows at ``fs_out`` samples per second, fs_out / 2 apart
+    (M2 / D2 = 2), whose centres lie in ``band = (f_lo, f_hi)`` Hz from the centre; default prototypes."""
+    from . import fine
+    M1, D1, M2, D2 = fine.shape(fs, fs_out, 2)
+    return fine.FineChannelizer(fs, M1, M2, D1, D2, channels=fine.channels_for(band, fs, M1, D1, M2), device=device, max_in=max_in)
+
+
 def morse_keying(text, wpm, fs):
     """0 / 1 keying waveform (float32) of ``text`` at ``wpm`` words per minute and ``fs`` samples per second, timing
     1 : 3 : 1 : 3 : 7 (dot, dash, gap between elements, between characters, between words); a dot lasts 1.2 / wpm s.
@@ -122,7 +130,8 @@ class CW_Decoders:
         self.chan = chan
         self.nk, self.D, self.fs_out = chan.nk, chan.D, chan.fs_out
         self.max_out = int(max_out)
-        self.cfg = params(self.fs_out, wpm0, settle_samples(len(chan.h), self.D, self.fs_out)) if cfg is None else cfg
+        run_in = chan.run_in_taps if hasattr(chan, "run_in_taps") else len(chan.h)
+        self.cfg = params(self.fs_out, wpm0, settle_samples(run_in, self.D, self.fs_out)) if cfg is None else cfg
         self.plan = plan(self.nk, self.max_out, self.cfg)               # a bad shape fails here
         self.cap = self.plan["cap"]
         hd = C.c_void_p()
@@ -214,12 +223,15 @@ class CW_Skimmer:
     """Wideband IQ at ``fs`` -> the channelizer's raster of M channels (row a at ``freqs[a]`` Hz, ``fs / D`` samples per
     second each) -> one Morse decoder per row, without taking the rows off the device."""
 
-    def __init__(self, fs, M, D=None, h=None, channels=None, wpm0=20, device=0, max_in=1 << 22, max_out=1024):
+    def __init__(self, fs, M=None, D=None, h=None, channels=None, wpm0=20, device=0, max_in=1 << 22, max_out=1024, chan=None):
         self.chan = self.dec = None
-        nk = int(M) if channels is None else int(channels[1])
-        D_ = int(M) // 2 if D is None else int(D)
-        plan(nk, max_out, params(float(fs) / D_, wpm0))                  # a bad shape fails here, with or without a device
-        self.chan = Channelizer(fs, M, D, h, channels, device, max_in)
+        if chan is None:
+            nk = int(M) if channels is None else int(channels[1])
+            D_ = int(M) // 2 if D is None else int(D)
+            plan(nk, max_out, params(float(fs) / D_, wpm0))              # a bad shape fails here, with or without a device
+            self.chan = Channelizer(fs, M, D, h, channels, device, max_in)
+        else:
+            self.chan = chan                                             # a ready channelizer of either kind, adopted and owned
         self.dec = CW_Decoders(self.chan, wpm0, max_out)
         self.fs, self.M, self.D, self.nk = self.chan.fs, self.chan.M, self.chan.D, self.chan.nk
         self.freqs, self.fs_out = self.chan.freqs, self.chan.fs_out

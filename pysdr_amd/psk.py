@@ -85,6 +85,24 @@ def shape(fs, baud=31.25):
                      f"M = 4 D a channelizer size")
 
 
+def fine_channelizer(fs, band, baud=31.25, device=0, max_in=1 << 22):
+    """A ``fine.FineChannelizer`` for ``PSK_Skimmer(fs, baud, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4
+    apart whose centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 8 where ``fine.shape`` finds a shape, else
+    12; M2 / D2 = 4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
+    from . import fine
+    err = None
+    for S in (8, 12):
+        try:
+            M1, D1, M2, D2 = fine.shape(fs, S * float(baud), 4)
+        except ValueError as e:
+            err = e
+            continue
+        h2 = prototype(float(fs) / D1, M2, baud, S)
+        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
+                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
+    raise ValueError(f"no PSK raster in two stages for fs = {fs} and {baud} baud: {err}")
+
+
 def prototype(fs, M, baud, S):
     """The channelizer's prototype for the PSK raster: Kaiser(8.0) windowed-sinc low-pass of 4 M taps cut at fs_out / 2 =
     S baud / 2, sum 1 (the convention of ``design.channelizer_taps``).  The rows are S baud / 4 apart, so a station is
@@ -258,15 +276,26 @@ class PSK_Skimmer:
     decoders inside every row, fine row F at ``freqs_fine[F]`` Hz (signed) -> the text of the stations, each on the fine
     row that owns it."""
 
-    def __init__(self, fs, baud=31.25, channels=None, device=0, max_in=1 << 22, max_out=256):
+    def __init__(self, fs, baud=31.25, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None):
         self.chan = self.dec = None
         self.fs, self.baud = float(fs), float(baud)
-        self.S, self.D, self.M = shape(fs, baud)
-        self.nsub = 4 * self.S
-        nk = self.M if channels is None else int(channels[1])
-        plan(nk, self.S, max_out, params())                              # a bad shape fails here, with or without a device
-        self.h = prototype(fs, self.M, baud, self.S)
-        self.chan = Channelizer(fs, self.M, self.D, self.h, channels, device, max_in)
+        if chan is None:
+            self.S, self.D, self.M = shape(fs, baud)
+            self.nsub = 4 * self.S
+            nk = self.M if channels is None else int(channels[1])
+            plan(nk, self.S, max_out, params())                          # a bad shape fails here, with or without a device
+            self.h = prototype(fs, self.M, baud, self.S)
+            self.chan = Channelizer(fs, self.M, self.D, self.h, channels, device, max_in)
+        else:
+            # a ready channelizer of either kind, adopted and owned: rows S baud / 4 apart at S baud samples per second
+            self.chan = chan
+            s = chan.fs_out / self.baud
+            self.S, self.D, self.M = int(round(s)), chan.D, chan.M
+            if abs(s - self.S) > 1e-9 * s or self.S not in (8, 12) or chan.M != 4 * chan.D or float(fs) != chan.fs:
+                raise ValueError(f"PSK_Skimmer: the channelizer's rows (fs {chan.fs}, fs_out {chan.fs_out}, M / D = {chan.M / chan.D}) "
+                                 f"are not at 8 or 12 samples per symbol of {baud} baud with M / D = 4 at fs = {fs}")
+            self.nsub = 4 * self.S
+            self.h = chan.h if hasattr(chan, "h") else (chan.h1, chan.h2)
         self.dec = PSK_Decoders(self.chan, self.S, max_out)
         self.nk, self.nfine, self.fs_out = self.chan.nk, self.dec.nfine, self.chan.fs_out
         self.freqs = self.chan.freqs
