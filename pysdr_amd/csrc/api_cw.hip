@@ -1,26 +1,21 @@
 // C ABI of the CW skimmer (include/pysdr_hip.h).  Host-side only, like api_objects.hip: the kernel
 // and its launch function live in cw.hip, what both sides share in cw_plan.h.  The skimmer borrows a channelizer as the
-// channel bank does and queues its decoder behind the channelizer's launch on the channelizer's stream, with no host
-// synchronisation in between.  Every device resource is an owner (host_res.h): deleting the object frees it.
+// channel bank does (chan_client.h: what the channelizer's clients share) and queues its decoder behind the channelizer's
+// launch on the channelizer's stream.  Every device resource is an owner (host_res.h): deleting the object frees it.
+#include "chan_client.h"
 #include "cw_plan.h"
-#include "host_res.h"
-#include "objects_plan.h"
 
 using namespace pysdr;
 
-struct pysdr_cw {
-  pysdr_chan* ch = nullptr;         // borrowed; outlives the skimmer
-  int device = 0, D = 0, nk = 0, max_in = 0, max_out = 0;   // of the channelizer, fixed at its create; max_out: ours
-  hipStream_t stream = nullptr;     // the channelizer's
+struct pysdr_cw : ChanClient {
+  int max_out = 0;
   pysdr_cw_cfg cfg{};
   CwPlan plan;
-  int last_n_out = 0;
   DevBuf<float2> d_y;               // [nk][ypitch]
   DevBuf<CwState> d_state;          // [nk]
   DevBuf<int32_t> d_events;         // [nk][cap]
   DevBuf<int32_t> d_counts;         // [nk]
   std::vector<CwState> h_state;
-  std::mutex mu;                    // one call at a time on a handle
 };
 
 namespace {
@@ -71,32 +66,17 @@ int pysdr_cw_create(pysdr_chan* ch, const pysdr_cw_cfg* cfg, int max_out, pysdr_
   if (!out) { set_last_error("pysdr_cw_create: out is NULL"); return PYSDR_ERR_ARG; }
   *out = nullptr;
   if (!ch || !cfg) { set_last_error("pysdr_cw_create: NULL channelizer or cfg"); return PYSDR_ERR_ARG; }
-  ChanInfo ci;
-  int rc = chan_info(ch, &ci);
-  if (rc != PYSDR_OK) return rc;
-  int32_t pl[8];
-  rc = pysdr_cw_plan(ci.nk, max_out, cfg, pl);
-  if (rc != PYSDR_OK) return rc;
   pysdr_cw* w = new pysdr_cw();
-  w->ch = ch; w->device = ci.device; w->D = ci.D; w->nk = ci.nk; w->max_in = ci.max_in; w->stream = ci.stream;
+  int32_t pl[8];
+  int rc = client_bind(w, ch);
+  if (rc == PYSDR_OK) rc = pysdr_cw_plan(w->nk, max_out, cfg, pl);
+  if (rc != PYSDR_OK) { delete w; return rc; }
   w->max_out = max_out; w->cfg = *cfg;
   cw_plan(w->nk, max_out, cfg, &w->plan);
-  rc = use_device(w->device);
-  if (rc) { delete w; return rc; }
-  rc = cw_alloc(w);
-  if (rc) { failed_in("pysdr_cw_create", rc); pysdr_cw_destroy(w); return rc; }
-  rc = cw_reset_locked(w);
-  if (rc != PYSDR_OK) { pysdr_cw_destroy(w); return rc; }
-  *out = w;
-  return PYSDR_OK;
+  return client_create(w, "pysdr_cw_create", cw_alloc, cw_reset_locked, out);
 }
 
-void pysdr_cw_destroy(pysdr_cw* w) {
-  if (!w) return;
-  (void)hipSetDevice(w->device);
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
-  delete w;                               // (the owners free: host_res.h)
-}
+void pysdr_cw_destroy(pysdr_cw* w) { client_destroy(w); }
 
 int pysdr_cw_reset(pysdr_cw* w) {
   if (!w) { set_last_error("pysdr_cw_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
@@ -106,10 +86,7 @@ int pysdr_cw_reset(pysdr_cw* w) {
 
 int pysdr_cw_sync(pysdr_cw* w) {
   if (!w) { set_last_error("pysdr_cw_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
-  return PYSDR_OK;
+  return client_sync(w);
 }
 
 int pysdr_cw_process(pysdr_cw* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
@@ -117,27 +94,20 @@ int pysdr_cw_process(pysdr_cw* w, const void* iq, int n, int on_device, int* n_o
   if (!w || !n_out) { set_last_error("pysdr_cw_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
   *n_out = 0;
   std::lock_guard<std::mutex> lk(w->mu);
-  if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_cw_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
-  if (n > w->max_in) { set_last_error("pysdr_cw_process: n %d > max_in %d", n, w->max_in); return PYSDR_ERR_STATE; }
+  ClientStep step;
+  int rc = client_begin(w, "pysdr_cw_process", iq, n, &step);
+  if (rc != PYSDR_OK) return rc;
   if (events && ev_pitch < w->plan.cap) {
     set_last_error("pysdr_cw_process: ev_pitch %lld < the event cap %d", ev_pitch, w->plan.cap);
     return PYSDR_ERR_STATE;
   }
-  // what the channelizer is about to complete: checked before it advances its stream
-  ChanInfo ci;
-  int rc = chan_info(w->ch, &ci);
-  if (rc != PYSDR_OK) return rc;
-  const unsigned long long D = (unsigned long long)w->D, s0 = ci.n_abs, s1 = s0 + (unsigned long long)n;
-  const unsigned long long nf_want = (s1 + D - 1) / D - (s0 + D - 1) / D;
-  if (nf_want > (unsigned long long)w->max_out) {
-    set_last_error("pysdr_cw_process: the call would complete %llu outputs, max_out is %d", nf_want, w->max_out);
+  if (step.nf_want > (unsigned long long)w->max_out) {
+    set_last_error("pysdr_cw_process: the call would complete %llu outputs, max_out is %d", step.nf_want, w->max_out);
     return PYSDR_ERR_STATE;
   }
   int nf = 0;
-  rc = pysdr_chan_process(w->ch, iq, n, on_device, w->d_y.get(), w->plan.ypitch, 1, &nf);
+  rc = client_feed(w, "pysdr_cw_process", "skimmer", iq, n, on_device, w->d_y.get(), w->plan.ypitch, step, &nf);
   if (rc != PYSDR_OK) return rc;
-  if (nf != (int)nf_want) { set_last_error("pysdr_cw_process: the channelizer was fed beside its skimmer (%d outputs, %d expected)", nf, (int)nf_want); return PYSDR_ERR_STATE; }
-  w->last_n_out = nf;
   if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
     if (counts) std::memset(counts, 0, (size_t)w->nk * sizeof(int32_t));
     return PYSDR_OK;
@@ -160,26 +130,7 @@ int pysdr_cw_process(pysdr_cw* w, const void* iq, int n, int on_device, int* n_o
 
 int pysdr_cw_fetch(pysdr_cw* w, const int* rows, int nrows, int32_t* events, long long pitch) {
   if (!w) { set_last_error("pysdr_cw_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
-  if (nrows < 0 || (nrows > 0 && (!rows || !events))) { set_last_error("pysdr_cw_fetch: nrows %d / NULL rows or events", nrows); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 0 || rows[i] >= w->nk) { set_last_error("pysdr_cw_fetch: row %d outside [0, %d)", rows[i], w->nk); return PYSDR_ERR_ARG; }
-  const size_t cap = (size_t)w->plan.cap;
-  if (pitch < (long long)cap) { set_last_error("pysdr_cw_fetch: pitch %lld < the event cap %d", pitch, w->plan.cap); return PYSDR_ERR_STATE; }
-  if (w->last_n_out == 0 || nrows == 0) return PYSDR_OK;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  hipStream_t st = w->stream;
-  for (int i = 0; i < nrows; ++i) {
-    // runs of consecutive rows go as one strided copy
-    int run = 1;
-    while (i + run < nrows && rows[i + run] == rows[i] + run) ++run;
-    PYSDR_HIP_CHECK(hipMemcpy2DAsync(events + (size_t)i * pitch, (size_t)pitch * sizeof(int32_t),
-                                     w->d_events.get() + (size_t)rows[i] * cap, cap * sizeof(int32_t), cap * sizeof(int32_t),
-                                     (size_t)run, hipMemcpyDeviceToHost, st));
-    i += run - 1;
-  }
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  return PYSDR_OK;
+  return client_fetch_events(w, "pysdr_cw_fetch", "row", w->d_events.get(), w->nk, w->plan.cap, rows, nrows, events, pitch);
 }
 
 int pysdr_cw_state(pysdr_cw* w, float* s, float* pk, float* nf, int32_t* ints) {

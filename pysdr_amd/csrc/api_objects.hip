@@ -5,9 +5,8 @@
 // is destroyed after them; the destroy functions drain it first.
 #include <cmath>
 
-#include "chan_object.h"      // struct pysdr_chan
-#include "host_res.h"
-#include "objects_plan.h"
+#include "chan_client.h"      // what the bank shares with the channelizer's other clients
+#include "chan_object.h"      // struct pysdr_chan: the channelizer's own entry points and chan_info, nothing of the bank's
 
 using namespace pysdr;
 
@@ -44,10 +43,7 @@ struct pysdr_rtty {
   DevBuf<int> d_ndet;          // [max_lines]
 };
 
-struct pysdr_bank {
-  pysdr_chan* ch = nullptr;         // borrowed; outlives the bank
-  int device = 0, D = 0, nk = 0, max_in = 0, out_cap = 0;   // of the channelizer, fixed at its create
-  hipStream_t stream = nullptr;     // the channelizer's
+struct pysdr_bank : ChanClient {
   BankPlan plan;
   int mode = PYSDR_NFM, T = 0;
   bool have_taps = false;
@@ -55,7 +51,6 @@ struct pysdr_bank {
   float ref = kAgcRefDefault, thresh = 0.f, fm_scale = 0.f;
   double fs_out = 0.0;
   uint32_t fword = 0;               // CW: the BFO's phase increment per output
-  int last_n_out = 0;
   long long ypitch = 0, apitch = 0;
   DevBuf<float2> d_y;               // [nk][hpad + out_cap]
   DevBuf<float> d_a;                // [nk][out_cap]
@@ -65,7 +60,6 @@ struct pysdr_bank {
   DevBuf<BankState> d_state;
   std::vector<float> h_taps;
   std::vector<BankState> h_state;
-  std::mutex mu;                    // one call at a time on a handle
 };
 
 namespace {
@@ -169,7 +163,7 @@ int chan_info(pysdr_chan* c, ChanInfo* out) {
   if (!c || !out) { set_last_error("chan_info: NULL channelizer or out"); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(c->mu);
   out->device = c->device; out->M = c->M; out->D = c->D; out->nk = c->nk; out->max_in = c->max_in;
-  out->stream = c->queue(); out->n_abs = c->n_abs;
+  out->out_cap = c->out_cap; out->stream = c->queue(); out->n_abs = c->n_abs;
   return PYSDR_OK;
 }
 
@@ -579,37 +573,22 @@ int pysdr_bank_create(pysdr_chan* ch, double fs_out, int mode, int ntaps_af, pys
   if (mode != PYSDR_AM && mode != PYSDR_NFM) { set_last_error("pysdr_bank_create: mode %d is neither AM nor NFM", mode); return PYSDR_ERR_ARG; }
   if (!(fs_out > 0.0)) { set_last_error("pysdr_bank_create: fs_out %g", fs_out); return PYSDR_ERR_ARG; }
   pysdr_bank* b = new pysdr_bank();
-  {
-    std::lock_guard<std::mutex> lk(ch->mu);
-    b->ch = ch; b->device = ch->device; b->D = ch->D; b->nk = ch->nk; b->max_in = ch->max_in; b->out_cap = ch->out_cap;
-    b->stream = ch->queue();
-  }
+  int rc = client_bind(b, ch);
+  if (rc != PYSDR_OK) { delete b; return rc; }
   if (!bank_plan(b->nk, ntaps_af, b->out_cap, &b->plan)) {
     set_last_error("pysdr_bank_create: ntaps_af %d outside [%d, %d]", ntaps_af, kBankTapsMin, kBankTapsMax);
     delete b;
     return PYSDR_ERR_ARG;
   }
-  int rc = use_device(b->device);
-  if (rc) { delete b; return rc; }
   b->mode = mode; b->T = ntaps_af;
   b->fs_out = fs_out;
   b->fm_scale = (float)(fs_out / (2.0 * M_PI * kNfmFullScaleDev));
   b->ypitch = (long long)b->plan.hpad + b->out_cap;
   b->apitch = b->out_cap;
-  rc = bank_alloc(b);
-  if (rc) { failed_in("pysdr_bank_create", rc); pysdr_bank_destroy(b); return rc; }
-  rc = bank_reset_locked(b);
-  if (rc != PYSDR_OK) { pysdr_bank_destroy(b); return rc; }
-  *out = b;
-  return PYSDR_OK;
+  return client_create(b, "pysdr_bank_create", bank_alloc, bank_reset_locked, out);
 }
 
-void pysdr_bank_destroy(pysdr_bank* b) {
-  if (!b) return;
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  delete b;
-}
+void pysdr_bank_destroy(pysdr_bank* b) { client_destroy(b); }
 
 int pysdr_bank_set_mode(pysdr_bank* b, int mode, const double* af, int ntaps) {
   if (!b || !af) { set_last_error("pysdr_bank_set_mode: NULL bank or taps"); return PYSDR_ERR_ARG; }
@@ -672,10 +651,7 @@ int pysdr_bank_reset(pysdr_bank* b) {
 
 int pysdr_bank_sync(pysdr_bank* b) {
   if (!b) { set_last_error("pysdr_bank_sync: NULL bank"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(b->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(b->device));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(b->stream));
-  return PYSDR_OK;
+  return client_sync(b);
 }
 
 int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, float* am, long long am_pitch, int am_on_device,
@@ -683,26 +659,18 @@ int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, floa
   if (!b || !n_out) { set_last_error("pysdr_bank_process: NULL bank or n_out"); return PYSDR_ERR_ARG; }
   *n_out = 0;
   std::lock_guard<std::mutex> lk(b->mu);
-  if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_bank_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
-  if (n > b->max_in) { set_last_error("pysdr_bank_process: n %d > max_in %d", n, b->max_in); return PYSDR_ERR_STATE; }
+  ClientStep step;
+  int rc = client_begin(b, "pysdr_bank_process", iq, n, &step);
+  if (rc != PYSDR_OK) return rc;
   if (!b->have_taps) { set_last_error("pysdr_bank_process: no mode set"); return PYSDR_ERR_STATE; }
-  // what the channelizer is about to complete: checked before it advances its stream
-  unsigned long long s0;
-  {
-    std::lock_guard<std::mutex> ck(b->ch->mu);
-    s0 = b->ch->n_abs;
-  }
-  const unsigned long long D = (unsigned long long)b->D, s1 = s0 + (unsigned long long)n;
-  const int nf_want = (int)((s1 + D - 1) / D - (s0 + D - 1) / D);
-  if (am && am_pitch < nf_want) {
-    set_last_error("pysdr_bank_process: pitch %lld < the call's %d outputs", am_pitch, nf_want);
+  if (am && am_pitch < (long long)step.nf_want) {
+    set_last_error("pysdr_bank_process: pitch %lld < the call's %d outputs", am_pitch, (int)step.nf_want);
     return PYSDR_ERR_STATE;
   }
   int nf = 0;
-  int rc = pysdr_chan_process(b->ch, iq, n, on_device, b->d_y.get() + b->plan.hpad, b->ypitch, 1, &nf);
+  rc = client_feed(b, "pysdr_bank_process", "bank", iq, n, on_device, b->d_y.get() + b->plan.hpad, b->ypitch, step, &nf);
   if (rc != PYSDR_OK) return rc;
-  if (nf != nf_want) { set_last_error("pysdr_bank_process: the channelizer was fed beside its bank (%d outputs, %d expected)", nf, nf_want); return PYSDR_ERR_STATE; }
-  if (nf == 0) { b->last_n_out = 0; return PYSDR_OK; }                // no output: no AGC block, no state change, nothing to fetch
+  if (nf == 0) return PYSDR_OK;                                       // no output: no AGC block, no state change, nothing to fetch
   PYSDR_HIP_CHECK(hipSetDevice(b->device));
   hipStream_t st = b->stream;
   const int ntiles = (nf + kBankTile - 1) / kBankTile;
@@ -711,7 +679,7 @@ int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, floa
   a.y = b->d_y.get() + b->plan.hpad; a.ypitch = b->ypitch; a.a = b->d_a.get(); a.apitch = b->apitch;
   a.n_out = nf; a.T = b->T; a.tp = b->plan.tp; a.taps = b->d_taps.get(); a.fm_scale = b->fm_scale; a.noise = squelch;
   a.pmax = b->d_pmax.get(); a.psum = b->d_psum.get(); a.ptiles = b->plan.tiles;
-  a.m0_lo = (uint32_t)((s0 + D - 1) / D); a.fword = b->fword;          // CW: the BFO phase follows the absolute output index
+  a.m0_lo = (uint32_t)step.m0; a.fword = b->fword;          // CW: the BFO phase follows the absolute output index
   rc = launch_bank(b->mode, b->plan, a, ntiles, b->nk, st);
   if (rc) return rc;
   FinishArgs f{};
@@ -722,7 +690,6 @@ int pysdr_bank_process(pysdr_bank* b, const void* iq, int n, int on_device, floa
   f.squelch = squelch; f.ref = b->ref; f.thresh = b->thresh;
   rc = launch_bank_finish(f, b->nk, st);
   if (rc) return rc;
-  b->last_n_out = nf;
   *n_out = nf;
   if (am) {
     PYSDR_HIP_CHECK(hipMemcpy2DAsync(am, (size_t)am_pitch * sizeof(float), a.a, (size_t)b->apitch * sizeof(float),
@@ -756,27 +723,18 @@ int pysdr_bank_fetch(pysdr_bank* b, const int* rows, int nrows, float* am, float
   if (!b) { set_last_error("pysdr_bank_fetch: NULL bank"); return PYSDR_ERR_ARG; }
   if (nrows < 0 || (nrows > 0 && !rows)) { set_last_error("pysdr_bank_fetch: nrows %d / NULL rows", nrows); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(b->mu);
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 0 || rows[i] >= b->nk) { set_last_error("pysdr_bank_fetch: row %d outside [0, %d)", rows[i], b->nk); return PYSDR_ERR_ARG; }
+  if (!rows_inside("pysdr_bank_fetch", "row", rows, nrows, b->nk)) return PYSDR_ERR_ARG;
   const int nf = b->last_n_out;
   if (pitch < nf) { set_last_error("pysdr_bank_fetch: pitch %lld < the last call's %d outputs", pitch, nf); return PYSDR_ERR_STATE; }
   if (nf == 0 || nrows == 0 || (!am && !iq)) return PYSDR_OK;
   PYSDR_HIP_CHECK(hipSetDevice(b->device));
   hipStream_t st = b->stream;
-  for (int i = 0; i < nrows; ++i) {
-    // runs of consecutive rows go as one strided copy
-    int run = 1;
-    while (i + run < nrows && rows[i + run] == rows[i] + run) ++run;
-    const size_t r = (size_t)rows[i];
-    if (am)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(am + (size_t)i * pitch, (size_t)pitch * sizeof(float), b->d_a.get() + r * b->apitch,
-                                       (size_t)b->apitch * sizeof(float), (size_t)nf * sizeof(float), (size_t)run,
-                                       hipMemcpyDeviceToHost, st));
-    if (iq)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(iq + 2 * (size_t)i * pitch, (size_t)pitch * sizeof(float2),
-                                       b->d_y.get() + r * b->ypitch + b->plan.hpad, (size_t)b->ypitch * sizeof(float2),
-                                       (size_t)nf * sizeof(float2), (size_t)run, hipMemcpyDeviceToHost, st));
-    i += run - 1;
+  for (int i = 0, run; i < nrows; i += run) {                         // run by run, audio then IQ of each
+    run = row_run(rows, nrows, i);
+    int rc = am ? copy_row_run<float>(rows, i, run, b->d_a.get(), b->apitch, am, pitch, (size_t)nf, st) : PYSDR_OK;
+    if (rc == PYSDR_OK && iq)
+      rc = copy_row_run<float2>(rows, i, run, b->d_y.get() + b->plan.hpad, b->ypitch, reinterpret_cast<float2*>(iq), pitch, (size_t)nf, st);
+    if (rc) return rc;
   }
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   return PYSDR_OK;

@@ -1,20 +1,16 @@
 // C ABI of the PSK31 skimmer (include/pysdr_hip.h).  Host-side only, like api_cw.hip: the kernel and
 // its launch function live in psk.hip, what both sides share in psk_plan.h.  The skimmer borrows a channelizer as the CW
-// skimmer does and queues its decoders behind the channelizer's launch on the channelizer's stream, with no host
-// synchronisation in between.  Every device resource is an owner (host_res.h): deleting the object frees it.
+// skimmer does (chan_client.h: what the channelizer's clients share) and queues its decoders behind the channelizer's
+// launch on the channelizer's stream.  Every device resource is an owner (host_res.h): deleting the object frees it.
+#include "chan_client.h"
 #include "psk_plan.h"
-#include "host_res.h"
-#include "objects_plan.h"
 
 using namespace pysdr;
 
-struct pysdr_psk {
-  pysdr_chan* ch = nullptr;         // borrowed; outlives the skimmer
-  int device = 0, D = 0, nk = 0, max_in = 0, max_out = 0;   // of the channelizer, fixed at its create; max_out: ours
-  hipStream_t stream = nullptr;     // the channelizer's
+struct pysdr_psk : ChanClient {
+  int max_out = 0;
   pysdr_psk_cfg cfg{};
   PskPlan plan;
-  int last_n_out = 0;
   DevBuf<PskC> d_y;                 // [nk][ypitch]: kPskHpad of history room, then the call's outputs
   DevBuf<PskC> d_tw;                // [NT]
   DevBuf<float> d_g;                // [L]
@@ -25,7 +21,6 @@ struct pysdr_psk {
   DevBuf<int32_t> d_counts;         // [nfine]
   std::vector<float> h_tw, h_g;
   std::vector<int32_t> h_si;        // the state after create / reset
-  std::mutex mu;                    // one call at a time on a handle
 };
 
 namespace {
@@ -85,14 +80,11 @@ int pysdr_psk_create(pysdr_chan* ch, int S, const pysdr_psk_cfg* cfg, const floa
   if (!out) { set_last_error("pysdr_psk_create: out is NULL"); return PYSDR_ERR_ARG; }
   *out = nullptr;
   if (!ch || !cfg || !tw || !g) { set_last_error("pysdr_psk_create: NULL channelizer, cfg, tw or g"); return PYSDR_ERR_ARG; }
-  ChanInfo ci;
-  int rc = chan_info(ch, &ci);
-  if (rc != PYSDR_OK) return rc;
-  int32_t pl[8];
-  rc = pysdr_psk_plan(ci.nk, S, max_out, cfg, pl);
-  if (rc != PYSDR_OK) return rc;
   pysdr_psk* w = new pysdr_psk();
-  w->ch = ch; w->device = ci.device; w->D = ci.D; w->nk = ci.nk; w->max_in = ci.max_in; w->stream = ci.stream;
+  int32_t pl[8];
+  int rc = client_bind(w, ch);
+  if (rc == PYSDR_OK) rc = pysdr_psk_plan(w->nk, S, max_out, cfg, pl);
+  if (rc != PYSDR_OK) { delete w; return rc; }
   w->max_out = max_out; w->cfg = *cfg;
   psk_plan(w->nk, S, max_out, cfg, &w->plan);
   w->h_tw.assign(tw, tw + 2 * 32 * (size_t)S);
@@ -100,22 +92,10 @@ int pysdr_psk_create(pysdr_chan* ch, int S, const pysdr_psk_cfg* cfg, const floa
   const size_t nf = (size_t)w->plan.nfine;
   w->h_si.assign((size_t)kPskStateInts * nf, 0);
   for (size_t i = 0; i < nf; ++i) w->h_si[nf + i] = S;                 // cnt = S
-  rc = use_device(w->device);
-  if (rc) { delete w; return rc; }
-  rc = psk_alloc(w);
-  if (rc) { failed_in("pysdr_psk_create", rc); pysdr_psk_destroy(w); return rc; }
-  rc = psk_reset_locked(w);
-  if (rc != PYSDR_OK) { pysdr_psk_destroy(w); return rc; }
-  *out = w;
-  return PYSDR_OK;
+  return client_create(w, "pysdr_psk_create", psk_alloc, psk_reset_locked, out);
 }
 
-void pysdr_psk_destroy(pysdr_psk* w) {
-  if (!w) return;
-  (void)hipSetDevice(w->device);
-  if (w->stream) (void)hipStreamSynchronize(w->stream);
-  delete w;                               // (the owners free: host_res.h)
-}
+void pysdr_psk_destroy(pysdr_psk* w) { client_destroy(w); }
 
 int pysdr_psk_reset(pysdr_psk* w) {
   if (!w) { set_last_error("pysdr_psk_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
@@ -125,10 +105,7 @@ int pysdr_psk_reset(pysdr_psk* w) {
 
 int pysdr_psk_sync(pysdr_psk* w) {
   if (!w) { set_last_error("pysdr_psk_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  PYSDR_HIP_CHECK(hipStreamSynchronize(w->stream));
-  return PYSDR_OK;
+  return client_sync(w);
 }
 
 int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
@@ -136,27 +113,20 @@ int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n
   if (!w || !n_out) { set_last_error("pysdr_psk_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
   *n_out = 0;
   std::lock_guard<std::mutex> lk(w->mu);
-  if (n < 0 || (n > 0 && !iq)) { set_last_error("pysdr_psk_process: n %d / NULL input", n); return PYSDR_ERR_ARG; }
-  if (n > w->max_in) { set_last_error("pysdr_psk_process: n %d > max_in %d", n, w->max_in); return PYSDR_ERR_STATE; }
+  ClientStep step;
+  int rc = client_begin(w, "pysdr_psk_process", iq, n, &step);
+  if (rc != PYSDR_OK) return rc;
   if (events && ev_pitch < w->plan.cap) {
     set_last_error("pysdr_psk_process: ev_pitch %lld < the event cap %d", ev_pitch, w->plan.cap);
     return PYSDR_ERR_STATE;
   }
-  // what the channelizer is about to complete: checked before it advances its stream
-  ChanInfo ci;
-  int rc = chan_info(w->ch, &ci);
-  if (rc != PYSDR_OK) return rc;
-  const unsigned long long D = (unsigned long long)w->D, s0 = ci.n_abs, s1 = s0 + (unsigned long long)n;
-  const unsigned long long m0 = (s0 + D - 1) / D, nf_want = (s1 + D - 1) / D - m0;
-  if (nf_want > (unsigned long long)w->max_out) {
-    set_last_error("pysdr_psk_process: the call would complete %llu outputs, max_out is %d", nf_want, w->max_out);
+  if (step.nf_want > (unsigned long long)w->max_out) {
+    set_last_error("pysdr_psk_process: the call would complete %llu outputs, max_out is %d", step.nf_want, w->max_out);
     return PYSDR_ERR_STATE;
   }
   int nf = 0;
-  rc = pysdr_chan_process(w->ch, iq, n, on_device, w->d_y.get() + kPskHpad, w->plan.ypitch, 1, &nf);
+  rc = client_feed(w, "pysdr_psk_process", "skimmer", iq, n, on_device, w->d_y.get() + kPskHpad, w->plan.ypitch, step, &nf);
   if (rc != PYSDR_OK) return rc;
-  if (nf != (int)nf_want) { set_last_error("pysdr_psk_process: the channelizer was fed beside its skimmer (%d outputs, %d expected)", nf, (int)nf_want); return PYSDR_ERR_STATE; }
-  w->last_n_out = nf;
   const size_t nfine = (size_t)w->plan.nfine;
   PYSDR_HIP_CHECK(hipSetDevice(w->device));
   hipStream_t st = w->stream;
@@ -165,7 +135,7 @@ int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n
   } else {
     PskArgs a{};
     a.y = w->d_y.get() + kPskHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
-    a.m0_mod = (int)(m0 % (unsigned long long)(32 * w->plan.S));
+    a.m0_mod = (int)(step.m0 % (unsigned long long)(32 * w->plan.S));
     a.cfg = w->cfg; a.tw = w->d_tw.get(); a.g = w->d_g.get();
     a.e = w->d_e.get(); a.sf = w->d_sf.get(); a.si = w->d_si.get(); a.events = w->d_events.get(); a.counts = w->d_counts.get();
     rc = launch_psk_decode(w->plan.S, a, st);
@@ -184,26 +154,7 @@ int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n
 
 int pysdr_psk_fetch(pysdr_psk* w, const int* rows, int nrows, int32_t* events, long long pitch) {
   if (!w) { set_last_error("pysdr_psk_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
-  if (nrows < 0 || (nrows > 0 && (!rows || !events))) { set_last_error("pysdr_psk_fetch: nrows %d / NULL rows or events", nrows); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  for (int i = 0; i < nrows; ++i)
-    if (rows[i] < 0 || rows[i] >= w->plan.nfine) { set_last_error("pysdr_psk_fetch: fine row %d outside [0, %d)", rows[i], w->plan.nfine); return PYSDR_ERR_ARG; }
-  const size_t cap = (size_t)w->plan.cap;
-  if (pitch < (long long)cap) { set_last_error("pysdr_psk_fetch: pitch %lld < the event cap %d", pitch, w->plan.cap); return PYSDR_ERR_STATE; }
-  if (w->last_n_out == 0 || nrows == 0) return PYSDR_OK;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  hipStream_t st = w->stream;
-  for (int i = 0; i < nrows; ++i) {
-    // runs of consecutive rows go as one strided copy
-    int run = 1;
-    while (i + run < nrows && rows[i + run] == rows[i] + run) ++run;
-    PYSDR_HIP_CHECK(hipMemcpy2DAsync(events + (size_t)i * pitch, (size_t)pitch * sizeof(int32_t),
-                                     w->d_events.get() + (size_t)rows[i] * cap, cap * sizeof(int32_t), cap * sizeof(int32_t),
-                                     (size_t)run, hipMemcpyDeviceToHost, st));
-    i += run - 1;
-  }
-  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
-  return PYSDR_OK;
+  return client_fetch_events(w, "pysdr_psk_fetch", "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap, rows, nrows, events, pitch);
 }
 
 int pysdr_psk_state(pysdr_psk* w, float* e, float* f, int32_t* ints) {

@@ -1,9 +1,9 @@
 // What the four stream objects -- waterfall, RTTY decoder bank, channelizer, channel bank -- share between their kernels
 // (waterfall.hip, rtty.hip, chan.hip, bank.hip), their host half (api_objects.hip) and the checking launch layer of
 // tests/host_san: constants, pure plans, kernel argument structs, and DECLARATIONS ONLY of the launch functions (defined in
-// the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  At its end: what the CW skimmer
-// (api_cw.hip, cw.hip; its plan and step: cw_plan.h) needs of a borrowed channelizer, and its launch; the PSK31 skimmer's
-// launch (api_psk.hip, psk.hip; psk_plan.h).  Nothing in this
+// the four kernel files, or by the harness's stubs) and of api.hip's two create helpers.  In the channelizer's section: what
+// an object that borrows one may know of it (chan_client.h).  At its end: the launches of the CW skimmer (api_cw.hip,
+// cw.hip; its plan and step: cw_plan.h) and of the PSK31 skimmer (api_psk.hip, psk.hip; psk_plan.h).  Nothing in this
 // header calls the HIP runtime; plain C++.  Not part of the public ABI.
 #pragma once
 
@@ -116,6 +116,14 @@ int chan_prepare(const ChanPlan& p);            // more than 64 KB of LDS is an 
 int launch_chan(const ChanPlan& p, const ChanArgs& a, int grid, hipStream_t st);
 // new history = last H samples of [old history | x[0 .. n)]
 int launch_chan_roll(const float2* x, int n, const float2* old, float2* neu, int H, hipStream_t st);
+// What an object that borrows a channelizer of either kind knows of it (api_objects.hip; taken under the channelizer's lock).
+struct ChanInfo {
+  int device, M, D, nk, max_in;
+  int out_cap;                    // most outputs one call can complete, rounded up to 16
+  hipStream_t stream;             // every launch and copy of the channelizer is queued here
+  unsigned long long n_abs;       // input samples since create / reset
+};
+int chan_info(pysdr_chan* c, ChanInfo* out);
 
 // ---- channel bank (bank.hip) -----------------------------------------------------------
 constexpr int kBankThreads = 256;
@@ -181,13 +189,6 @@ int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int 
 int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st);
 
 // ---- CW skimmer (cw.hip, host half api_cw.hip; plan, state and kernel arguments: cw_plan.h) ----------------------------
-// What an object that borrows a channelizer needs of it (api_objects.hip; taken under the channelizer's lock).
-struct ChanInfo {
-  int device, M, D, nk, max_in;
-  hipStream_t stream;             // every launch and copy of the channelizer is queued here
-  unsigned long long n_abs;       // input samples since create / reset
-};
-int chan_info(pysdr_chan* c, ChanInfo* out);
 struct CwArgs;
 int launch_cw_decode(const CwArgs& a, hipStream_t st);
 

@@ -1,7 +1,7 @@
 // A HIP runtime made of the host heap, for the sanitizer build of the HOST half of libpysdr_hip.so
 // (tests/host_san): "device" memory is malloc'ed (so AddressSanitizer sees every size the host code
 // passes to a copy or to a kernel), copies are memcpy, streams and events complete at once.  Only the
-// calls pysdr_amd/csrc/api.hip and api_objects.hip make exist.  Nothing here is part of the product.
+// calls the host files of pysdr_amd/csrc (api*.hip) make exist.  Nothing here is part of the product.
 //   HOST_SAN_TRACE=<file>    one line per stream-ordered operation (copies, fills, event records, waits, synchronises; the
 //                            launch layer adds its launches).  Streams, events and allocations are named by the order in
 //                            which the TRACE first meets them (+ byte offset), never by address or creation order: allocating

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Build the HOST half of libpysdr_hip.so (pysdr_amd/csrc/api.hip, compiled as plain C++) over the fake
+# Build the HOST half of libpysdr_hip.so (pysdr_amd/csrc/api*.hip, compiled as plain C++) over the fake
 # HIP runtime + the checking launch layer, once with AddressSanitizer + UBSan and once with
 # ThreadSanitizer, and run the driver.  CPU only (SURVEY.md 5 "sanitizers on the CPU build").
 #   tests/host_san/run.sh [asan|tsan|all]
@@ -8,11 +8,12 @@ HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(cd "$HERE/../.." && pwd)
 OUT=${HOST_SAN_OUT:-/tmp/pysdr_host_san}
 mkdir -p "$OUT"
-SRC="$ROOT/pysdr_amd/csrc/api.hip $ROOT/pysdr_amd/csrc/api_objects.hip $HERE/stub_kernels.cpp $HERE/san_main.cpp"
+CS=$ROOT/pysdr_amd/csrc
+SRC="$CS/api.hip $CS/api_objects.hip $CS/api_cw.hip $CS/api_psk.hip $CS/api_fine.hip $HERE/stub_kernels.cpp $HERE/san_main.cpp"
 INC="-I$HERE/fake_hip -I$ROOT/pysdr_amd/csrc"
 build() { # name, flags...
   local name=$1; shift
-  g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall -Wno-unused-function -x c++ $INC "$@" $SRC -o "$OUT/san_$name" -ldl -lpthread
+  g++ -std=c++17 -O1 -g -fno-omit-frame-pointer -Wall -Wno-unused-function -Wno-unknown-pragmas -x c++ $INC "$@" $SRC -o "$OUT/san_$name" -ldl -lpthread
 }
 what=${1:-all}
 if [ "$what" = asan ] || [ "$what" = all ]; then

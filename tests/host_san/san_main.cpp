@@ -8,13 +8,16 @@
 // plans of the two serial loops (pysdr_amd/csrc/host_plan.h) over rates, call lengths and tunings.  `san_main allocfail`
 // runs a short scenario over every object kind with the n-th allocation / event / stream creation failing, n = 1, 2, ...
 // The four stream objects of api_objects.hip (waterfall, RTTY decoder bank, channelizer, channel bank) have a scenario each,
-// part of the default run; `san_main objects` runs those four alone (their queue trace on its own).
+// and so have the objects that borrow a channelizer beside the bank -- CW skimmer (api_cw.hip), PSK31 skimmer (api_psk.hip) --
+// the fine channelizer (api_fine.hip) and the bank's complex-tap modes; all part of the default run.  `san_main objects`
+// runs these alone (their queue trace on its own).
 //   build + run: tests/host_san/run.sh   (tests/test_host_sanitizers.py does that)
 #include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -457,7 +460,8 @@ static void channelizer_errors() {
   if (c) { std::fprintf(stderr, "a failed pysdr_chan_create left a handle\n"); std::exit(1); }
 }
 
-static void bank_scenario(int mode, int ntaps_af) {
+// cplx: 0, or the complex-tap mode (USB, LSB, CW) the bank runs in, set through pysdr_bank_set_mode_cplx on a bank created as `mode`
+static void bank_scenario(int mode, int ntaps_af, int cplx = 0) {
   const int M = 16, D = 4, nk = 5, max_in = 2049 * D + 3;
   pysdr_chan* ch = nullptr;
   OK(pysdr_chan_create(0, M, D, 13, nk, 2 * M, max_in, &ch));      // rows 13, 14, 15, 0, 1
@@ -476,6 +480,20 @@ static void bank_scenario(int mode, int ntaps_af) {
   FAILS(pysdr_bank_set_mode(b, mode, nullptr, ntaps_af));
   FAILS(pysdr_bank_set_mode(nullptr, mode, af.data(), ntaps_af));
   OK(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af));
+  const auto af_im = taps(ntaps_af, 0.5);
+  auto set_own_mode = [&] {
+    if (cplx) OK(pysdr_bank_set_mode_cplx(b, cplx, af.data(), af_im.data(), ntaps_af, 700.0));
+    else OK(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af));
+  };
+  if (cplx) {
+    FAILS(pysdr_bank_set_mode_cplx(b, cplx, af.data(), af_im.data(), ntaps_af + 1, 700.0));
+    FAILS(pysdr_bank_set_mode_cplx(b, PYSDR_AM, af.data(), af_im.data(), ntaps_af, 700.0));
+    FAILS(pysdr_bank_set_mode_cplx(b, PYSDR_IQ, af.data(), af_im.data(), ntaps_af, 700.0));
+    FAILS(pysdr_bank_set_mode_cplx(b, cplx, nullptr, af_im.data(), ntaps_af, 700.0));
+    FAILS(pysdr_bank_set_mode_cplx(b, cplx, af.data(), nullptr, ntaps_af, 700.0));
+    FAILS(pysdr_bank_set_mode_cplx(nullptr, cplx, af.data(), af_im.data(), ntaps_af, 700.0));
+    set_own_mode();
+  }
   unsigned long long s = 0;
   // am: 0 none, 1 host at pitch n_out, 2 device at pitch n_out, 3 device at a wider pitch
   auto run = [&](int n, int in_dev, int how) {
@@ -489,6 +507,7 @@ static void bank_scenario(int mode, int ntaps_af) {
   auto fetches = [&] {
     OK(pysdr_bank_fetch(b, rows_run, 3, am.data(), iq.data(), nf + 1));
     OK(pysdr_bank_fetch(b, rows_far, 3, am.data(), nullptr, nf));
+    OK(pysdr_bank_fetch(b, rows_far, 3, am.data(), iq.data(), cap));                     // three runs, audio and IQ of each in turn
     OK(pysdr_bank_fetch(b, rows_rep, 5, nullptr, iq.data(), cap));
     OK(pysdr_bank_fetch(b, rows_rep, 5, nullptr, nullptr, cap));
     OK(pysdr_bank_fetch(b, nullptr, 0, am.data(), iq.data(), cap));
@@ -502,7 +521,7 @@ static void bank_scenario(int mode, int ntaps_af) {
     if (pass == 2) {                                      // the other mode and back, then from the start
       OK(pysdr_bank_set_mode(b, mode == PYSDR_AM ? PYSDR_NFM : PYSDR_AM, af.data(), ntaps_af));
       run(2049 * D, 0, 1); fetches();
-      OK(pysdr_bank_set_mode(b, mode, af.data(), ntaps_af));
+      set_own_mode();
       OK(pysdr_bank_reset(b)); s = 0;
       OK(pysdr_bank_set_agc(b, 1, 0.5f));
     }
@@ -681,6 +700,349 @@ static void stream_objects() {
   std::printf("stream objects: %d calls\n", g_obj_calls);
 }
 
+// ---- the objects that borrow a channelizer beside the bank -- CW skimmer (api_cw.hip), PSK31 skimmer (api_psk.hip) -- the
+// fine channelizer they may borrow instead (api_fine.hip), and the bank's complex-tap modes: part of `san_main objects`
+static int g_skim_calls = 0, g_fine_calls = 0;
+
+static pysdr_cw_cfg good_cw_cfg() {
+  pysdr_cw_cfg c;
+  c.a_s = 0.3f; c.a_p = 0.01f; c.a_n = 0.01f; c.snr_min = 4.f; c.hi = 0.5f; c.lo = 0.25f; c.fl = 1e-3f;
+  c.d0 = 64; c.dmin = 16; c.dmax = 1024; c.n0 = 8;
+  return c;
+}
+static pysdr_psk_cfg good_psk_cfg() {
+  pysdr_psk_cfg c;
+  c.a_t = 0.05f; c.a_q = 0.1f; c.hi = 0.5f; c.lo = 0.25f; c.hy = 1.5f; c.pmax = 1e6f; c.n0 = 4;
+  return c;
+}
+
+// What the two skimmers' call lists have in common: one scenario runs over either.
+struct Skimmer {
+  int nrow = 0, cap = 0;     // event rows (channels / decoders) and the event cap
+  std::function<int(const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events, long long ev_pitch, bool extras)> process;
+  std::function<int(const int* rows, int nrows, int32_t* events, long long pitch)> fetch;
+  std::function<int(int which)> state;       // which: 0 every output, 1 .. some of them NULL
+  std::function<int()> reset, sync;
+};
+
+static void skimmer_scenario(const Skimmer& sk, pysdr_chan* ch, int D, int max_in, int max_out) {
+  const long long wide = sk.cap + 3;
+  std::vector<float> x(2 * (size_t)max_in, 0.25f);
+  DevMem dx(8 * (size_t)max_in);
+  std::vector<int32_t> counts(sk.nrow), events((size_t)sk.nrow * wide);
+  unsigned long long s = 0;
+  int nf = 0, k = 0;
+  // how: 0 neither counts nor events, 1 counts only, 2 both at pitch cap, 3 both at a wider pitch
+  auto run = [&](int n, int in_dev, int how) {
+    const int want = (int)((s + n + D - 1) / D - (s + D - 1) / D);
+    OK(sk.process(in_dev ? dx.p : (void*)x.data(), n, in_dev, &nf, how ? counts.data() : nullptr, how >= 2 ? events.data() : nullptr,
+                  how == 3 ? wide : sk.cap, (k % 3) != 0));
+    if (nf != want) { std::fprintf(stderr, "skimmer: %d outputs, %d expected\n", nf, want); std::exit(1); }
+    s += n; ++k; ++g_skim_calls;
+  };
+  const int rows_run[] = {0, 1, 2}, rows_far[] = {sk.nrow - 1, 0, 2}, rows_rep[] = {1, 1, 3, sk.nrow - 1, sk.nrow - 1};
+  auto fetches = [&] {
+    OK(sk.fetch(rows_run, 3, events.data(), sk.cap));
+    OK(sk.fetch(rows_far, 3, events.data(), wide));
+    OK(sk.fetch(rows_rep, 5, events.data(), wide));
+    OK(sk.fetch(nullptr, 0, events.data(), sk.cap));
+    OK(sk.fetch(rows_run, 0, nullptr, sk.cap));
+  };
+  for (int how : {3, 2, 1, 0})
+    for (int in_dev : {0, 1})
+      for (int n : {0, 1, D - 1, D, D + 1, 8 * D, 7}) { run(n, in_dev, how); fetches(); }
+  for (int which = 0; which < 3; ++which) OK(sk.state(which));
+  OK(sk.reset()); s = 0;
+  fetches();                                              // nothing to fetch after a reset: no copy
+  OK(sk.sync());
+  // refused calls, and after each a good one: the stream did not move
+  FAILS(sk.process(x.data(), (max_out + 1) * D, 0, &nf, counts.data(), nullptr, sk.cap, false));   // would complete max_out + 1
+  if (nf != 0) { std::fprintf(stderr, "skimmer: a refused call left n_out %d\n", nf); std::exit(1); }
+  run(max_out * D, 0, 2);
+  FAILS(sk.process(x.data(), D, 0, &nf, counts.data(), events.data(), sk.cap - 1, false));        // ev_pitch below the cap
+  run(D + 1, 1, 1);
+  FAILS(sk.process(x.data(), max_in + 1, 0, &nf, counts.data(), nullptr, sk.cap, false));
+  run(1, 0, 0);
+  FAILS(sk.process(x.data(), -1, 0, &nf, counts.data(), nullptr, sk.cap, false));
+  run(D, 0, 3);
+  FAILS(sk.process(nullptr, 1, 0, &nf, counts.data(), nullptr, sk.cap, false));
+  run(2, 1, 2);
+  FAILS(sk.process(x.data(), 1, 0, nullptr, counts.data(), nullptr, sk.cap, false));
+  run(D - 1, 0, 1); fetches();
+  FAILS(sk.fetch(rows_run, 3, events.data(), sk.cap - 1));                                         // pitch below the cap
+  const int bad_hi[] = {0, sk.nrow}, bad_lo[] = {-1};
+  FAILS(sk.fetch(bad_hi, 2, events.data(), sk.cap));
+  FAILS(sk.fetch(bad_lo, 1, events.data(), sk.cap));
+  FAILS(sk.fetch(rows_run, -1, events.data(), sk.cap));
+  FAILS(sk.fetch(nullptr, 1, events.data(), sk.cap));
+  FAILS(sk.fetch(rows_run, 1, nullptr, sk.cap));
+  fetches();
+  // the channelizer fed beside its skimmer, between two calls (bank_scenario): the next call is sized right
+  {
+    std::vector<float> y(2 * (size_t)sk.nrow * 16);
+    int n2 = 0;
+    OK(pysdr_chan_process(ch, x.data(), 3 * D + 1, 0, y.data(), 16, 0, &n2));
+    s += 3 * D + 1;
+    run(5 * D, 0, 3); fetches();
+  }
+  run(0, 0, 1);                                           // no output: the counts are zeroed, (PSK) qn and open still copied
+  run(0, 1, 0);
+}
+
+static void cw_scenario() {
+  const int M = 16, D = 4, nk = 5, max_out = 8, max_in = (max_out + 1) * D + 3;
+  pysdr_chan* ch = nullptr;
+  OK(pysdr_chan_create(0, M, D, 13, nk, 2 * M, max_in, &ch));      // rows 13, 14, 15, 0, 1
+  const auto h = taps(2 * M);
+  OK(pysdr_chan_set_taps(ch, h.data(), 2 * M));
+  const pysdr_cw_cfg cfg = good_cw_cfg();
+  int32_t pl[8];
+  OK(pysdr_cw_plan(nk, max_out, &cfg, pl));
+  pysdr_cw* w = nullptr;
+  OK(pysdr_cw_create(ch, &cfg, max_out, &w));
+  std::vector<float> zs(nk), pk(nk), zn(nk);
+  std::vector<int32_t> ints(8 * (size_t)nk);
+  Skimmer sk;
+  sk.nrow = nk; sk.cap = pl[4];
+  sk.process = [&](const void* iq, int n, int dev, int* n_out, int32_t* counts, int32_t* events, long long pitch, bool) {
+    return pysdr_cw_process(w, iq, n, dev, n_out, counts, events, pitch);
+  };
+  sk.fetch = [&](const int* rows, int nrows, int32_t* events, long long pitch) { return pysdr_cw_fetch(w, rows, nrows, events, pitch); };
+  sk.state = [&](int which) {
+    return which == 0 ? pysdr_cw_state(w, zs.data(), pk.data(), zn.data(), ints.data())
+         : which == 1 ? pysdr_cw_state(w, nullptr, pk.data(), nullptr, nullptr) : pysdr_cw_state(w, nullptr, nullptr, nullptr, ints.data());
+  };
+  sk.reset = [&] { return pysdr_cw_reset(w); };
+  sk.sync = [&] { return pysdr_cw_sync(w); };
+  skimmer_scenario(sk, ch, D, max_in, max_out);
+  int nf = 0;
+  FAILS(pysdr_cw_process(nullptr, h.data(), 1, 0, &nf, nullptr, nullptr, 0));
+  FAILS(pysdr_cw_fetch(nullptr, nullptr, 0, nullptr, 0));
+  FAILS(pysdr_cw_state(nullptr, nullptr, nullptr, nullptr, nullptr));
+  FAILS(pysdr_cw_reset(nullptr));
+  FAILS(pysdr_cw_sync(nullptr));
+  pysdr_cw_destroy(w);
+  pysdr_cw_destroy(nullptr);
+  // a cfg outside each rule of the plan, and the create errors
+  FAILS(pysdr_cw_plan(nk, max_out, &cfg, nullptr));
+  FAILS(pysdr_cw_plan(0, max_out, &cfg, pl));
+  FAILS(pysdr_cw_plan(4097, max_out, &cfg, pl));
+  FAILS(pysdr_cw_plan(nk, 0, &cfg, pl));
+  FAILS(pysdr_cw_plan(nk, (1 << 21) + 1, &cfg, pl));
+  FAILS(pysdr_cw_plan(nk, max_out, nullptr, pl));
+  auto bad = [&](void (*change)(pysdr_cw_cfg&)) { pysdr_cw_cfg c = cfg; change(c); FAILS(pysdr_cw_plan(nk, max_out, &c, pl)); };
+  bad([](pysdr_cw_cfg& c) { c.a_s = 0.f; });
+  bad([](pysdr_cw_cfg& c) { c.a_p = 1.5f; });
+  bad([](pysdr_cw_cfg& c) { c.a_n = NAN; });
+  bad([](pysdr_cw_cfg& c) { c.snr_min = 0.f; });
+  bad([](pysdr_cw_cfg& c) { c.hi = INFINITY; });
+  bad([](pysdr_cw_cfg& c) { c.lo = 2.f * c.hi; });
+  bad([](pysdr_cw_cfg& c) { c.fl = -1.f; });
+  bad([](pysdr_cw_cfg& c) { c.dmin = 15; });
+  bad([](pysdr_cw_cfg& c) { c.d0 = c.dmin - 1; });
+  bad([](pysdr_cw_cfg& c) { c.dmax = c.d0 - 1; });
+  bad([](pysdr_cw_cfg& c) { c.dmax = (1 << 22) + 1; });
+  bad([](pysdr_cw_cfg& c) { c.n0 = 0; });
+  bad([](pysdr_cw_cfg& c) { c.n0 = (1 << 22) + 1; });
+  w = nullptr;
+  pysdr_cw_cfg nope = cfg;
+  nope.n0 = 0;
+  FAILS(pysdr_cw_create(ch, &cfg, max_out, nullptr));
+  FAILS(pysdr_cw_create(nullptr, &cfg, max_out, &w));
+  FAILS(pysdr_cw_create(ch, nullptr, max_out, &w));
+  FAILS(pysdr_cw_create(ch, &nope, max_out, &w));
+  FAILS(pysdr_cw_create(ch, &cfg, 0, &w));
+  if (w) { std::fprintf(stderr, "a failed pysdr_cw_create left a handle\n"); std::exit(1); }
+  pysdr_chan_destroy(ch);
+}
+
+static void psk_scenario(int S) {
+  const int M = 16, D = 4, nk = 3, max_out = 8, max_in = (max_out + 1) * D + 3;
+  pysdr_chan* ch = nullptr;
+  OK(pysdr_chan_create(0, M, D, 15, nk, 2 * M, max_in, &ch));      // rows 15, 0, 1
+  const auto h = taps(2 * M);
+  OK(pysdr_chan_set_taps(ch, h.data(), 2 * M));
+  const pysdr_psk_cfg cfg = good_psk_cfg();
+  int32_t pl[8];
+  OK(pysdr_psk_plan(nk, S, max_out, &cfg, pl));
+  const int nfine = nk * pl[6];
+  std::vector<float> tw(2 * 32 * (size_t)S, 0.5f), g(2 * (size_t)S, 0.1f);
+  pysdr_psk* w = nullptr;
+  OK(pysdr_psk_create(ch, S, &cfg, tw.data(), g.data(), max_out, &w));
+  std::vector<float> qn(nfine), e((size_t)S * nfine), f(4 * (size_t)nfine);
+  std::vector<int32_t> open(nfine), ints(5 * (size_t)nfine);
+  Skimmer sk;
+  sk.nrow = nfine; sk.cap = pl[4];
+  int extras_k = 0;
+  sk.process = [&](const void* iq, int n, int dev, int* n_out, int32_t* counts, int32_t* events, long long pitch, bool extras) {
+    const int which = extras ? 1 + (extras_k++ % 3) : 0;               // qn and open: both, either alone, neither
+    return pysdr_psk_process(w, iq, n, dev, n_out, counts, events, pitch, (which & 1) ? qn.data() : nullptr, (which & 2) ? open.data() : nullptr);
+  };
+  sk.fetch = [&](const int* rows, int nrows, int32_t* events, long long pitch) { return pysdr_psk_fetch(w, rows, nrows, events, pitch); };
+  sk.state = [&](int which) {
+    return which == 0 ? pysdr_psk_state(w, e.data(), f.data(), ints.data())
+         : which == 1 ? pysdr_psk_state(w, nullptr, f.data(), nullptr) : pysdr_psk_state(w, nullptr, nullptr, nullptr);
+  };
+  sk.reset = [&] { return pysdr_psk_reset(w); };
+  sk.sync = [&] { return pysdr_psk_sync(w); };
+  skimmer_scenario(sk, ch, D, max_in, max_out);
+  int nf = 0;
+  FAILS(pysdr_psk_process(nullptr, h.data(), 1, 0, &nf, nullptr, nullptr, 0, nullptr, nullptr));
+  FAILS(pysdr_psk_fetch(nullptr, nullptr, 0, nullptr, 0));
+  FAILS(pysdr_psk_state(nullptr, nullptr, nullptr, nullptr));
+  FAILS(pysdr_psk_reset(nullptr));
+  FAILS(pysdr_psk_sync(nullptr));
+  pysdr_psk_destroy(w);
+  pysdr_psk_destroy(nullptr);
+  FAILS(pysdr_psk_plan(nk, S, max_out, &cfg, nullptr));
+  FAILS(pysdr_psk_plan(nk, 10, max_out, &cfg, pl));
+  FAILS(pysdr_psk_plan(0, S, max_out, &cfg, pl));
+  FAILS(pysdr_psk_plan((1 << 18) / (4 * S) + 1, S, max_out, &cfg, pl));
+  FAILS(pysdr_psk_plan(nk, S, 0, &cfg, pl));
+  FAILS(pysdr_psk_plan(nk, S, (1 << 20) + 1, &cfg, pl));
+  FAILS(pysdr_psk_plan(nk, S, max_out, nullptr, pl));
+  auto bad = [&](void (*change)(pysdr_psk_cfg&)) { pysdr_psk_cfg c = cfg; change(c); FAILS(pysdr_psk_plan(nk, S, max_out, &c, pl)); };
+  bad([](pysdr_psk_cfg& c) { c.a_t = 0.f; });
+  bad([](pysdr_psk_cfg& c) { c.a_q = 1.5f; });
+  bad([](pysdr_psk_cfg& c) { c.hi = INFINITY; });
+  bad([](pysdr_psk_cfg& c) { c.lo = 2.f * c.hi; });
+  bad([](pysdr_psk_cfg& c) { c.lo = 0.f; });
+  bad([](pysdr_psk_cfg& c) { c.hy = NAN; });
+  bad([](pysdr_psk_cfg& c) { c.pmax = 2e18f; });
+  bad([](pysdr_psk_cfg& c) { c.pmax = 0.f; });
+  bad([](pysdr_psk_cfg& c) { c.n0 = 0; });
+  bad([](pysdr_psk_cfg& c) { c.n0 = (1 << 22) + 1; });
+  w = nullptr;
+  FAILS(pysdr_psk_create(ch, S, &cfg, tw.data(), g.data(), max_out, nullptr));
+  FAILS(pysdr_psk_create(nullptr, S, &cfg, tw.data(), g.data(), max_out, &w));
+  FAILS(pysdr_psk_create(ch, S, nullptr, tw.data(), g.data(), max_out, &w));
+  FAILS(pysdr_psk_create(ch, S, &cfg, nullptr, g.data(), max_out, &w));
+  FAILS(pysdr_psk_create(ch, S, &cfg, tw.data(), nullptr, max_out, &w));
+  FAILS(pysdr_psk_create(ch, 10, &cfg, tw.data(), g.data(), max_out, &w));
+  FAILS(pysdr_psk_create(ch, S, &cfg, tw.data(), g.data(), 0, &w));
+  if (w) { std::fprintf(stderr, "a failed pysdr_psk_create left a handle\n"); std::exit(1); }
+  pysdr_chan_destroy(ch);
+}
+
+static void fine_errors() {
+  int32_t pl[16];
+  pysdr_chan* c = nullptr;
+  OK(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, 5, 20, pl));
+  if (pl[5] < 2) { std::fprintf(stderr, "fine: the scenario's shape uses %d coarse rows\n", pl[5]); std::exit(1); }
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, 5, 20, nullptr));
+  FAILS(pysdr_chan_fine_plan(15, 5, 16, 8, 32, 32, 0, 1, pl));             // M1 < 16
+  FAILS(pysdr_chan_fine_plan(48, 24, 16, 8, 32, 32, 0, 1, pl));            // a factor 3
+  FAILS(pysdr_chan_fine_plan(16, 16, 16, 8, 32, 32, 0, 1, pl));            // M1 / D1 = 1: a row carries its own spacing only
+  FAILS(pysdr_chan_fine_plan(16, 3, 16, 8, 32, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 8, 4, 32, 32, 0, 1, pl));              // M2 < 16
+  FAILS(pysdr_chan_fine_plan(16, 8, 2048, 1024, 32, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 48, 24, 32, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 2, 32, 32, 0, 1, pl));             // M2 / D2 = 8
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 0, 32, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 4, 16, 8, 32, 32, 0, 1, pl));             // Q = 4
+  FAILS(pysdr_chan_fine_plan(16, 4, 50, 25, 32, 32, 0, 1, pl));            // M2 not a multiple of M1 / D1
+  FAILS(pysdr_chan_fine_plan(16, 8, 50, 25, 32, 32, 0, 1, pl));            // Q = 25, odd
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 0, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 16 * 16 + 1, 32, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 0, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 16 * 16 + 1, 0, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, -1, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, 128, 1, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, 0, 0, pl));
+  FAILS(pysdr_chan_fine_plan(16, 8, 16, 8, 32, 32, 0, 129, pl));
+  FAILS(pysdr_chan_fine_create(0, 16, 8, 16, 8, 5, 20, 32, 32, 100, nullptr));
+  FAILS(pysdr_chan_fine_create(0, 16, 16, 16, 8, 5, 20, 32, 32, 100, &c));
+  FAILS(pysdr_chan_fine_create(0, 16, 8, 16, 8, 5, 20, 32, 32, 0, &c));
+  FAILS(pysdr_chan_fine_create(0, 16, 8, 16, 8, 5, 20, 32, 32, (1 << 28) + 1, &c));
+  FAILS(pysdr_chan_fine_create(1, 16, 8, 16, 8, 5, 20, 32, 32, 100, &c));  // no such device
+  if (c) { std::fprintf(stderr, "a failed pysdr_chan_fine_create left a handle\n"); std::exit(1); }
+}
+
+static void fine_scenario(int M1, int D1, int M2, int D2, int g_first, int ng) {
+  const int D = D1 * D2, max_taps1 = 2 * M1 + 5, max_taps2 = 3 * M2 + 5, max_in = 5 * D + 5;
+  pysdr_chan* c = nullptr;
+  OK(pysdr_chan_fine_create(0, M1, D1, M2, D2, g_first, ng, max_taps1, max_taps2, max_in, &c));
+  const long long pitch = max_in / D + 2;
+  std::vector<float> x(2 * (size_t)max_in, 0.25f), y(2 * (size_t)ng * pitch);
+  DevMem dx(8 * (size_t)max_in), dy(8 * (size_t)ng * (pitch + 3));
+  int nf = 0;
+  FAILS(pysdr_chan_process(c, x.data(), 1, 0, y.data(), pitch, 0, &nf));                 // no taps yet
+  const auto h1 = taps(max_taps1), h2 = taps(max_taps2);
+  FAILS(pysdr_chan_set_taps(c, h1.data(), max_taps1));                                   // a fine handle takes both prototypes at once
+  FAILS(pysdr_chan_fine_set_taps(c, h1.data(), 0, h2.data(), max_taps2));
+  FAILS(pysdr_chan_fine_set_taps(c, h1.data(), max_taps1 + 1, h2.data(), max_taps2));
+  FAILS(pysdr_chan_fine_set_taps(c, h1.data(), max_taps1, h2.data(), 0));
+  FAILS(pysdr_chan_fine_set_taps(c, h1.data(), max_taps1, h2.data(), max_taps2 + 1));
+  FAILS(pysdr_chan_fine_set_taps(c, nullptr, max_taps1, h2.data(), max_taps2));
+  FAILS(pysdr_chan_fine_set_taps(c, h1.data(), max_taps1, nullptr, max_taps2));
+  FAILS(pysdr_chan_fine_set_taps(nullptr, h1.data(), max_taps1, h2.data(), max_taps2));
+  OK(pysdr_chan_fine_set_taps(c, h1.data(), max_taps1, h2.data(), max_taps2));
+  unsigned long long s = 0;
+  auto run = [&](int n, int in_dev, int out_dev) {
+    const int want = (int)((s + n + D - 1) / D - (s + D - 1) / D);
+    OK(pysdr_chan_process(c, in_dev ? dx.p : (void*)x.data(), n, in_dev, out_dev ? dy.p : (void*)y.data(), out_dev ? pitch + 3 : pitch, out_dev, &nf));
+    if (nf != want) { std::fprintf(stderr, "fine channelizer: %d outputs, %d expected\n", nf, want); std::exit(1); }
+    s += n; ++g_fine_calls;
+  };
+  for (int combo = 0; combo < 4; ++combo)                 // host / device input x host / device output
+    for (int n : {0, 1, D - 1, D, D + 1, max_in, 7, D1, D1 + 1, max_in - 1}) run(n, combo & 1, combo >> 1);
+  OK(pysdr_chan_fine_set_taps(c, h1.data(), M1 - 3, h2.data(), M2 - 3));                 // shorter prototypes: one tap row each
+  run(max_in, 0, 0); run(3, 1, 1);
+  OK(pysdr_chan_reset(c)); s = 0;
+  run(D + 1, 0, 1); run(max_in, 1, 0);
+  OK(pysdr_chan_sync(c));
+  FAILS(pysdr_chan_process(c, x.data(), max_in + 1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, x.data(), -1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, nullptr, 1, 0, y.data(), pitch, 0, &nf));
+  FAILS(pysdr_chan_process(c, x.data(), 1, 0, y.data(), pitch, 0, nullptr));
+  FAILS(pysdr_chan_process(c, x.data(), 2 * D, 0, nullptr, pitch, 0, &nf));              // outputs and nowhere to put them
+  FAILS(pysdr_chan_process(c, x.data(), 2 * D, 0, y.data(), 1, 0, &nf));                 // pitch too small
+  run(2 * D, 0, 0);                                                                      // ... and none of them moved the stream
+  // a CW skimmer, then a bank, on the fine handle: two calls each
+  const int max_out = max_in / D + 1;
+  {
+    const pysdr_cw_cfg cfg = good_cw_cfg();
+    int32_t pl[8];
+    OK(pysdr_cw_plan(ng, max_out, &cfg, pl));
+    pysdr_cw* w = nullptr;
+    OK(pysdr_cw_create(c, &cfg, max_out, &w));
+    std::vector<int32_t> counts(ng), events((size_t)ng * pl[4]);
+    OK(pysdr_cw_process(w, x.data(), max_in, 0, &nf, counts.data(), events.data(), pl[4]));
+    OK(pysdr_cw_process(w, dx.p, D + 1, 1, &nf, counts.data(), nullptr, 0));
+    const int rows[] = {ng - 1, 0, 1};
+    OK(pysdr_cw_fetch(w, rows, 3, events.data(), pl[4]));
+    g_fine_calls += 2;
+    pysdr_cw_destroy(w);
+  }
+  {
+    pysdr_bank* b = nullptr;
+    OK(pysdr_bank_create(c, 12000.0, PYSDR_AM, 9, &b));
+    const auto af = taps(9);
+    OK(pysdr_bank_set_mode_cplx(b, PYSDR_CW, af.data(), af.data(), 9, 700.0));
+    std::vector<float> am((size_t)ng * max_out), iq(2 * (size_t)ng * max_out);
+    OK(pysdr_bank_process(b, x.data(), max_in, 0, am.data(), max_out, 0, &nf));
+    OK(pysdr_bank_process(b, dx.p, D + 1, 1, nullptr, 0, 0, &nf));
+    const int rows[] = {ng - 1, 0, 1};
+    OK(pysdr_bank_fetch(b, rows, 3, am.data(), iq.data(), max_out));
+    g_fine_calls += 2;
+    pysdr_bank_destroy(b);
+  }
+  pysdr_chan_destroy(c);
+}
+
+static void channelizer_clients() {
+  g_skim_calls = g_fine_calls = 0;
+  const int before = g_obj_calls;
+  cw_scenario();
+  for (int S : {8, 12}) psk_scenario(S);
+  fine_errors();
+  fine_scenario(16, 8, 16, 8, 5, 20);                     // the smallest shape the plan accepts, three coarse rows
+  fine_scenario(16, 8, 20, 5, 150, 25);                   // M2 = 2^2 5: a radix-5 pass; the fine range wraps
+  for (int mode : {PYSDR_USB, PYSDR_LSB, PYSDR_CW})
+    for (int ntaps_af : {3, 8, 9, 255}) bank_scenario(ntaps_af == 8 ? PYSDR_NFM : PYSDR_AM, ntaps_af, mode);
+  std::printf("channelizer clients: %d skimmer calls, %d fine calls, %d sideband bank calls\n", g_skim_calls, g_fine_calls, g_obj_calls - before);
+}
+
 // ---- `san_main allocfail`: the n-th hipMalloc / hipHostMalloc / event / stream creation of a run fails (fake_hip).  Every
 // step of the scenario that fails must leave a message, and must succeed when it is simply called again -- a half-built
 // object was destroyed by its create function, a half-added receiver slot is taken over by the next pysdr_rx_add, a
@@ -782,7 +1144,25 @@ static void allocfail_scenario() {
   OK(pysdr_bank_set_mode(bk, PYSDR_NFM, h.data(), 9));
   STEP(pysdr_bank_process(bk, xin.data(), 400, 0, out.data(), 128, 0, &nd));
   pysdr_bank_destroy(bk);
+  // the channelizer's other clients, and its second kind: create + one call + destroy of each
+  const pysdr_cw_cfg ccfg = good_cw_cfg();
+  std::vector<int32_t> counts(5 * 48);
+  pysdr_cw* cw = nullptr;
+  STEP(pysdr_cw_create(ch, &ccfg, 128, &cw));
+  STEP(pysdr_cw_process(cw, xin.data(), 400, 0, &nd, counts.data(), nullptr, 0));
+  pysdr_cw_destroy(cw);
+  const pysdr_psk_cfg pcfg = good_psk_cfg();
+  std::vector<float> ptw(2 * 32 * 12, 0.5f), pg(2 * 12, 0.1f);
+  pysdr_psk* pk = nullptr;
+  STEP(pysdr_psk_create(ch, 12, &pcfg, ptw.data(), pg.data(), 128, &pk));
+  STEP(pysdr_psk_process(pk, xin.data(), 400, 0, &nd, counts.data(), nullptr, 0, nullptr, nullptr));
+  pysdr_psk_destroy(pk);
   pysdr_chan_destroy(ch);
+  pysdr_chan* fc = nullptr;
+  STEP(pysdr_chan_fine_create(0, 16, 8, 16, 8, 5, 20, 32, 32, 400, &fc));
+  OK(pysdr_chan_fine_set_taps(fc, h.data(), 32, h.data(), 32));
+  STEP(pysdr_chan_process(fc, xin.data(), 400, 0, out.data(), 16, 0, &nd));              // the lazy staging buffers of both stages
+  pysdr_chan_destroy(fc);
 }
 
 static void allocfail() {
@@ -863,6 +1243,32 @@ static void race() {
   stop.store(true);
   bank_knobs.join();
   pysdr_bank_destroy(b);
+  // ... and a CW skimmer on the same channelizer: one thread feeds it, another reads its state and fetches rows
+  const pysdr_cw_cfg cfg = good_cw_cfg();
+  pysdr_cw* w = nullptr;
+  OK(pysdr_cw_create(ch, &cfg, 256, &w));
+  int32_t pl[8];
+  OK(pysdr_cw_plan(5, 256, &cfg, pl));
+  stop.store(false);
+  std::thread cw_reader([&] {
+    float pk[5];
+    int32_t ints[5 * 8];
+    std::vector<int32_t> ev(2 * (size_t)pl[4]);
+    const int rows[] = {3, 4};
+    while (!stop.load()) {
+      OK(pysdr_cw_state(w, nullptr, pk, nullptr, ints));
+      OK(pysdr_cw_fetch(w, rows, 2, ev.data(), pl[4]));
+      OK(pysdr_cw_sync(w));
+    }
+  });
+  std::vector<int32_t> counts(5);
+  for (int it = 0; it < 300; ++it) {
+    int nf = 0;
+    OK(pysdr_cw_process(w, x.data(), 1024 - (it % 5), 0, &nf, counts.data(), nullptr, 0));
+  }
+  stop.store(true);
+  cw_reader.join();
+  pysdr_cw_destroy(w);
   pysdr_chan_destroy(ch);
 }
 
@@ -878,6 +1284,7 @@ int main(int argc, char** argv) {
   }
   if (argc > 1 && std::strcmp(argv[1], "objects") == 0) {
     stream_objects();
+    channelizer_clients();
     return 0;
   }
   int ndev = 0;
@@ -887,6 +1294,7 @@ int main(int argc, char** argv) {
   planner_sweep();
   pll_plan_sweep();
   stream_objects();
+  channelizer_clients();
   for (int pass = 0; pass < 3; ++pass) {
   g_overlap = pass == 0 ? 0 : (pass == 1 ? 2 : 1);
   for (const Rate& r : kRates) {

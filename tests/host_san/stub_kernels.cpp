@@ -1,5 +1,6 @@
 // The launch layer of libpysdr_hip.so for the sanitizer build of its HOST half (tests/host_san):
-// every launch_* that api.hip and api_objects.hip call, as a host function that
+// every launch_* that the host files call (api.hip, api_objects.hip, api_cw.hip, api_psk.hip, api_fine.hip), as a host
+// function that
 //   * reads every input element and writes every output element the real kernel is entitled to touch
 //     (the "device" memory is malloc'ed by the fake HIP runtime, so AddressSanitizer checks the sizes and
 //     offsets the host code computed: capacities, history prefixes, strides of the per-block arrays);
@@ -17,10 +18,13 @@
 #include <utility>
 
 #include "common.h"
+#include "cw_plan.h"
+#include "fine_plan.h"
 #include "mixdec_geom.h"
 #include "mixdec_mfma_geom.h"
 #include "mixdec_plan.h"
 #include "objects_plan.h"
+#include "psk_plan.h"
 
 namespace pysdr {
 
@@ -677,20 +681,22 @@ int launch_chan_roll(const float2* x, int n, const float2* old, float2* neu, int
 
 // ---- channel bank
 // bank_kernel, per row: the detector at d[i], i in [-(T - 1), n_out), reads y[i] (AM) or y[i - 2 .. i] (NFM); taps[0, tp);
-// writes a[row apitch + i], i < n_out (whole float4 pairs where 8 outputs fit) and pmax / psum[row ptiles + t], t < ntiles
+// writes a[row apitch + i], i < n_out (whole float4 pairs where 8 outputs fit) and pmax / psum[row ptiles + t], t < ntiles.
+// bank_cplx_kernel (USB, LSB, CW) in its place: d[i] reads y[i] alone, the taps are [2 tp] (re, then -im); the same writes
 int launch_bank(int mode, const BankPlan& p, const BankArgs& a, int ntiles, int nk, hipStream_t st) {
   if (fake_hip::tracing())
     Line("launch_bank").st(st).i("mode", mode).i("ntiles", ntiles).i("nk", nk).i("lds_floats", p.lds_floats).i("ypitch", a.ypitch).i("apitch", a.apitch)
         .i("n_out", a.n_out).i("T", a.T).i("tp", a.tp).f("fm_scale", a.fm_scale).i("noise", a.noise).i("ptiles", a.ptiles)
-        .p("y", a.y).p("a", a.a).p("taps", a.taps).p("pmax", a.pmax).p("psum", a.psum);
-  SAN_CHECK(mode == PYSDR_AM || mode == PYSDR_NFM, "mode %d", mode);
+        .i("m0_lo", a.m0_lo).i("fword", a.fword).p("y", a.y).p("a", a.a).p("taps", a.taps).p("pmax", a.pmax).p("psum", a.psum);
+  const bool cplx = mode == PYSDR_USB || mode == PYSDR_LSB || mode == PYSDR_CW;
+  SAN_CHECK(mode == PYSDR_AM || mode == PYSDR_NFM || cplx, "mode %d", mode);
   SAN_CHECK(a.tp % 8 == 0 && a.tp == p.tp && a.T >= kBankTapsMin && a.T <= a.tp && a.tp - a.T < 8, "T %d tp %d", a.T, a.tp);
   SAN_CHECK(p.hpad >= a.T + 1 && p.hpad % 8 == 0 && p.hpad <= 256, "hpad %d for %d taps", p.hpad, a.T);
   SAN_CHECK(ntiles <= a.ptiles && ntiles == (a.n_out + kBankTile - 1) / kBankTile && a.n_out >= 1, "%d tiles for %d outputs, room for %d", ntiles, a.n_out, a.ptiles);
   SAN_CHECK(p.lds_floats == kBankTile + a.tp, "lds_floats %d", p.lds_floats);
   SAN_CHECK(a.apitch % 4 == 0 && a.apitch >= a.n_out && (reinterpret_cast<uintptr_t>(a.a) & 15u) == 0, "a: pitch %lld, float4 stores", a.apitch);
-  const int back = mode == PYSDR_AM ? a.T - 1 : a.T + 1;
-  read_all(a.taps, (size_t)a.tp);
+  const int back = mode == PYSDR_NFM ? a.T + 1 : a.T - 1;
+  read_all(a.taps, (size_t)(cplx ? 2 : 1) * a.tp);
   for (int r = 0; r < nk; ++r) {
     read_all(a.y + (size_t)r * (size_t)a.ypitch - back, (size_t)back + a.n_out);
     write_all(a.a + (size_t)r * (size_t)a.apitch, (size_t)a.n_out);
@@ -715,6 +721,120 @@ int launch_bank_finish(const FinishArgs& f, int nk, hipStream_t st) {
     read_all(f.a + (size_t)r * (size_t)f.apitch, (size_t)f.n_out); write_all(f.a + (size_t)r * (size_t)f.apitch, (size_t)f.n_out);
     float2* y = f.ybase + (size_t)r * (size_t)f.ypitch;
     std::memmove(y, y + f.n_out, (size_t)f.hpad * sizeof(float2));
+  }
+  return PYSDR_OK;
+}
+
+// ==== the channelizer's other clients and its second kind (api_cw.hip, api_psk.hip, api_fine.hip; footprints read off
+// cw.hip / psk.hip / fine.hip, geometry checked with cw_plan.h / psk_plan.h / fine_plan.h) ====
+
+// ---- CW skimmer
+// cw_kernel, one lane per row < nk: reads y[row ypitch + i], i < n_out (the staging loads are guarded by r < nk and
+// i < n_out); state[row] read and written; writes events[row cap + e], e < cap at the most, and counts[row]
+int launch_cw_decode(const CwArgs& a, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_cw_decode").st(st).i("ypitch", a.ypitch).i("n_out", a.n_out).i("nk", a.nk).i("cap", a.cap).i("d0", a.cfg.d0).i("n0", a.cfg.n0)
+        .p("y", a.y).p("state", a.state).p("events", a.events).p("counts", a.counts);
+  CwPlan p;
+  SAN_CHECK(a.n_out >= 1 && cw_plan(a.nk, a.n_out, &a.cfg, &p), "no plan for nk %d and %d outputs", a.nk, a.n_out);
+  SAN_CHECK(a.cap >= p.cap && a.cap == cw_event_cap((a.cap / 2 - 1) * 3), "cap %d for %d outputs (their own cap %d)", a.cap, a.n_out, p.cap);
+  SAN_CHECK(a.ypitch >= p.ypitch && a.ypitch % 16 == 0, "ypitch %lld for %d outputs", a.ypitch, a.n_out);
+  SAN_CHECK(cw_tiles(a.n_out) * kCwTile >= a.n_out && cw_event_index(cw_pack(a.n_out - 1, kCwWordSpace)) == a.n_out - 1, "tiles / event word");
+  const float2* y = static_cast<const float2*>(a.y);
+  for (int r = 0; r < a.nk; ++r) {
+    read_all(y + (size_t)r * (size_t)a.ypitch, (size_t)a.n_out);
+    read_all(a.state + r, 1); write_all(a.state + r, 1);
+    write_all(a.events + (size_t)r * (size_t)a.cap, (size_t)a.cap);
+    write_all(a.counts + r, 1);
+  }
+  return PYSDR_OK;
+}
+
+// ---- PSK31 skimmer
+// psk_kernel<S>, NSUB = 4 S decoders per row < nk: reads y[row ypitch + i], i in [-(L - 1), n_out) -- the stub reads all
+// kPskHpad >= L - 1 samples of room the plan keeps in front of a row -- tw[0, NT), g[0, L); e[S][nfine], sf[4][nfine],
+// si[5][nfine] read and written; writes events[dec cap + e], e < cap at the most, and counts[dec], dec < nfine; moves the
+// row's last L - 1 samples of [history | outputs] to y[-(L - 1), 0)
+int launch_psk_decode(int S, const PskArgs& a, hipStream_t st) {
+  if (fake_hip::tracing())
+    Line("launch_psk_decode").st(st).i("S", S).i("ypitch", a.ypitch).i("n_out", a.n_out).i("nk", a.nk).i("cap", a.cap).i("nfine", a.nfine)
+        .i("m0_mod", a.m0_mod).i("n0", a.cfg.n0).p("y", a.y).p("tw", a.tw).p("g", a.g).p("e", a.e).p("sf", a.sf).p("si", a.si)
+        .p("events", a.events).p("counts", a.counts);
+  PskPlan p;
+  SAN_CHECK(a.n_out >= 1 && psk_plan(a.nk, S, a.n_out, &a.cfg, &p), "no plan for S %d, nk %d and %d outputs", S, a.nk, a.n_out);
+  SAN_CHECK(a.nfine == p.nfine && a.cap >= p.cap, "nfine %d / %d, cap %d for %d outputs (their own cap %d)", a.nfine, p.nfine, a.cap, a.n_out, p.cap);
+  SAN_CHECK(a.ypitch >= p.ypitch && (a.ypitch - kPskHpad) % 16 == 0, "ypitch %lld for %d outputs", a.ypitch, a.n_out);
+  const int L = 2 * S, NT = 32 * S;
+  SAN_CHECK(L - 1 <= kPskHpad && a.m0_mod >= 0 && a.m0_mod < NT, "m0_mod %d of %d", a.m0_mod, NT);
+  SAN_CHECK(p.groups * psk_rows(S) >= a.nk && psk_event_index(psk_pack(a.n_out - 1, 2047)) == a.n_out - 1, "groups / event word");
+  read_all(a.tw, (size_t)NT);
+  read_all(a.g, (size_t)L);
+  const size_t nf = (size_t)a.nfine;
+  read_all(a.e, (size_t)S * nf); write_all(a.e, (size_t)S * nf);
+  read_all(a.sf, (size_t)kPskStateFloats * nf); write_all(a.sf, (size_t)kPskStateFloats * nf);
+  read_all(a.si, (size_t)kPskStateInts * nf); write_all(a.si, (size_t)kPskStateInts * nf);
+  write_all(a.events, nf * (size_t)a.cap);
+  write_all(a.counts, nf);
+  for (int r = 0; r < a.nk; ++r) {
+    PskC* y = a.y + (size_t)r * (size_t)a.ypitch;
+    read_all(y - kPskHpad, (size_t)kPskHpad + a.n_out);
+    std::memmove(y - (L - 1), y + a.n_out - (L - 1), (size_t)(L - 1) * sizeof(PskC));
+  }
+  return PYSDR_OK;
+}
+
+// ---- fine channelizer, second stage
+int fine_prepare(const FinePlan& p) {
+  SAN_CHECK(p.mp == (p.M2 | 1) && p.lds_bytes == p.slots * p.mp * 8 && p.lds_bytes <= 160 * 1024 && p.slots >= 1 && p.slots <= kFineSlotsMax, "LDS %d", p.lds_bytes);
+  return PYSDR_OK;
+}
+// fine_kernel, row j < nk1 and frame fr < nframes: tap idx = p M2 + r < L2 reads rows[j pitch1 + off + fr D2 - idx], the
+// lowest off - (L2 - 1) >= hist - (P2 M2 - 1) -- the stub reads every row from its start, all hist samples in front of the
+// call's, to the last frame's newest sample; taps[0, L2); tw[0, M2); perm[0, Q); a0[0, nk1).
+// Writes y[row pitch + fr], row = fine_row_of(a0[j], u, Mf) where that is < ng, u < Q.
+int launch_fine(const FinePlan& p, const FineArgs& a, int gx, int gy, hipStream_t st) {
+  if (fake_hip::tracing()) {
+    Line l("launch_fine");
+    l.st(st).i("gx", gx).i("gy", gy).i("lds", p.lds_bytes).i("pitch1", a.pitch1).i("hist", a.hist).i("M2", a.M2).i("D2", a.D2).i("C2", a.C2)
+        .i("P2", a.P2).i("L2", a.L2).i("mp", a.mp).i("off", a.off).i("mf_lo", a.mf_lo).i("nframes", a.nframes).i("nk1", a.nk1).i("fw", a.fw)
+        .i("rw", a.rw).i("fw_shift", a.fw_shift).i("Q", a.Q).i("Mf", a.Mf).i("ng", a.ng).i("pitch", a.pitch).i("npass", a.npass)
+        .i("magic_M2", a.magic_M2).i("magic_Q", a.magic_Q)
+        .p("rows", a.rows).p("taps", a.taps).p("tw", a.tw).p("perm", a.perm).p("a0", a.a0).p("y", a.y);
+    for (int s = 0; s < a.npass; ++s) l.i(rk("radix", s).c_str(), a.radix[s]).i(rk("mper", s).c_str(), a.magic_per[s]).i(rk("mnq", s).c_str(), a.magic_nq[s]);
+  }
+  SAN_CHECK(a.nframes >= 1, "nframes %d", a.nframes);
+  const FineTile t = fine_tile(p, a.nframes);
+  SAN_CHECK(gx == t.gx && gy == t.gy && a.fw == t.fw && a.rw == t.rw && (1 << a.fw_shift) == a.fw && a.fw * a.rw == p.slots, "grid %d x %d, tile %d x %d", gx, gy, a.fw, a.rw);
+  SAN_CHECK(a.M2 == p.M2 && a.D2 == p.D2 && a.C2 == p.C2 && a.mp == p.mp && a.Q == p.Q && a.Mf == p.Mf && a.ng == p.ng && a.nk1 == p.nk1 && a.hist == p.hist, "plan");
+  SAN_CHECK(a.P2 >= 1 && a.P2 <= p.P2 && a.L2 > (a.P2 - 1) * a.M2 && a.L2 <= a.P2 * a.M2, "P2 %d (room for %d), L2 %d", a.P2, p.P2, a.L2);
+  SAN_CHECK(a.mf_lo >= 0 && a.mf_lo < 4 && a.magic_M2 == magic_of(a.M2) && a.magic_Q == magic_of(a.Q), "mf_lo %d / magic", a.mf_lo);
+  const long long last = (long long)a.off + (long long)(a.nframes - 1) * a.D2;       // the last frame's newest sample
+  SAN_CHECK(a.off >= a.hist && a.off - (a.L2 - 1) >= 0 && last < a.pitch1, "window [%d, %lld] of a row of %lld", a.off - (a.L2 - 1), last, a.pitch1);
+  SAN_CHECK(a.pitch >= a.nframes, "pitch %lld < %d frames", a.pitch, a.nframes);
+  int nb = a.M2;
+  for (int s = 0; s < a.npass; ++s) { SAN_CHECK(a.radix[s] == p.radix[s] && nb % a.radix[s] == 0, "radix"); nb /= a.radix[s]; }
+  SAN_CHECK(nb == 1 && a.npass == p.npass, "passes do not make M2");
+  read_all(a.taps, (size_t)a.L2);
+  read_all(a.tw, 2 * (size_t)a.M2);
+  for (int u = 0; u < a.Q; ++u) SAN_CHECK(a.perm[u] >= 0 && a.perm[u] < a.M2, "perm[%d] = %d", u, a.perm[u]);
+  for (int j = 0; j < a.nk1; ++j) {
+    read_all(a.rows + 2 * (size_t)j * (size_t)a.pitch1, 2 * (size_t)(last + 1));
+    SAN_CHECK(a.a0[j] == fine_a0(p, j), "a0[%d] = %d", j, a.a0[j]);
+    for (int u = 0; u < a.Q; ++u) {
+      const int row = fine_row_of(a.a0[j], u, a.Mf);
+      if (row < a.ng) write_all(a.y + 2 * (size_t)row * (size_t)a.pitch, 2 * (size_t)a.nframes);
+    }
+  }
+  return PYSDR_OK;
+}
+// fine_roll, one workgroup per row < nk1: rows[j pitch1 + e] = rows[j pitch1 + e + n1], e < hist (all reads first)
+int launch_fine_roll(float* rows, long long pitch1, int hist, int n1, int nk1, hipStream_t st) {
+  if (fake_hip::tracing()) Line("launch_fine_roll").st(st).i("pitch1", pitch1).i("hist", hist).i("n1", n1).i("nk1", nk1).p("rows", rows);
+  SAN_CHECK(n1 >= 1 && hist >= 1 && hist <= kFineRollThreads * kFineRollPer && fine_roll_elem(kFineRollThreads - 1, kFineRollPer - 1) + 1 >= hist, "hist %d n1 %d", hist, n1);
+  SAN_CHECK(pitch1 >= (long long)hist + n1, "row of %lld holds %d + %d", pitch1, hist, n1);
+  for (int j = 0; j < nk1; ++j) {
+    float* row = rows + 2 * (size_t)j * (size_t)pitch1;
+    std::memmove(row, row + 2 * (size_t)n1, (size_t)hist * 2 * sizeof(float));
   }
   return PYSDR_OK;
 }

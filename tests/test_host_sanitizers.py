@@ -1,14 +1,19 @@
 """SURVEY.md 5 "sanitizers on the CPU build": the HOST half of libpysdr_hip.so -- pysdr_amd/csrc/api.hip
 (context / receiver bookkeeping, tile geometry handed to the mix + decimate kernel, PLL plans, the setter
-snapshot, the ingest ring's slot state machine, the spectrum object) and api_objects.hip (waterfall, RTTY decoder
-bank, channelizer, channel bank: ring wraparound, row pitches, strided copies, lazy staging) compiled as plain C++ over a fake
+snapshot, the ingest ring's slot state machine, the spectrum object), api_objects.hip (waterfall, RTTY decoder
+bank, channelizer, channel bank in its five modes: ring wraparound, row pitches, strided copies, lazy staging), api_cw.hip
+and api_psk.hip (the two skimmers that borrow a channelizer, with chan_client.h, the core they share with the bank: event
+caps and pitches, the history room in front of a row, half-built objects) and api_fine.hip (the fine channelizer behind the
+same handle: the row buffer of its first stage, the roll) compiled as plain C++ over a fake
 HIP runtime whose "device" memory is the host heap, with a launch layer that touches exactly what each
 kernel may touch and re-walks every mixdec tile with the kernel's own geometry code
 (pysdr_amd/csrc/mixdec_geom.h) -- built and run under AddressSanitizer + UBSan, and the RX-thread-vs-Qt-
 thread scenario under ThreadSanitizer.  CPU only; no GPU sanitizer exists on this pool.
 
 Seeded-bug check done when the harness was written: halving the d_am allocation is reported by ASan in
-launch_apply (IQ mode writes 2 floats per output), removing the lock of apply_pending by TSan."""
+launch_apply (IQ mode writes 2 floats per output), removing the lock of apply_pending by TSan.  Repeated when the
+channelizer's clients came under the harness: halving the CW skimmer's d_events is reported by ASan in launch_cw_decode,
+dropping kPskHpad from the PSK31 skimmer's row pointer in launch_psk_decode."""
 import os
 import shutil
 import subprocess
@@ -38,6 +43,7 @@ def test_host_half_and_mixdec_plans_under_address_and_ub_sanitizers(tmp_path):
     assert "planner sweep: 1920 plans" in out
     assert "pll plan sweep:" in out
     assert "stream objects: 432 calls" in out
+    assert "channelizer clients: 195 skimmer calls, 98 fine calls, 324 sideband bank calls" in out
     assert "HOST_SAN_ALLOCFAIL_OK" in out
 
 
