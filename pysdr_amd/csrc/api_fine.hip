@@ -3,8 +3,6 @@
 // channelizer's handle type (chan_object.h): it owns a first-stage channelizer of the needed coarse rows, which writes
 // its rows straight behind the history of the row buffer, and queues the second stage and the roll behind it on the first
 // stage's stream.  Every device resource is an owner (host_res.h): deleting the object frees it.
-#include <cmath>
-
 #include "chan_object.h"
 #include "fine_plan.h"
 
@@ -36,30 +34,16 @@ FineExt* ext_of(pysdr_chan* c) { return static_cast<FineExt*>(c->ext); }
 
 int fine_alloc(pysdr_chan* c, FineExt* e) {
   const FinePlan& p = e->plan;
-  std::vector<float2> tw(p.M2);
-  for (int j = 0; j < p.M2; ++j) {
-    const double ph = 2.0 * M_PI * (double)j / (double)p.M2;
-    tw[j] = make_float2((float)std::cos(ph), (float)std::sin(ph));
-  }
-  // where the in-place passes leave second-stage channel k: k = k1 + R1 (k2 + R2 (...)) sits at k1 M2 / R1 + k2 M2 / (R1 R2) + ...
-  std::vector<int> perm(p.Q), a0(p.nk1);
-  for (int u = 0; u < p.Q; ++u) {
-    int k = fine_k2(u - p.Q / 2, p.M2), nb = p.M2, pos = 0;
-    for (int s = 0; s < p.npass; ++s) {
-      const int R = p.radix[s];
-      nb /= R;
-      pos += (k % R) * nb;
-      k /= R;
-    }
-    perm[u] = pos;
-  }
+  const std::vector<float> tw = fft_twiddles(p.M2);
+  std::vector<int> perm(p.Q), a0(p.nk1);          // where the passes leave the second-stage channel of kept channel u
+  for (int u = 0; u < p.Q; ++u) perm[u] = fft_position(fine_k2(u - p.Q / 2, p.M2), p.M2, p.npass, p.radix);
   for (int j = 0; j < p.nk1; ++j) a0[j] = fine_a0(p, j);
   PYSDR_HIP_CHECK(e->d_rows.alloc((size_t)p.nk1 * (size_t)e->pitch1));
   PYSDR_HIP_CHECK(e->d_taps.alloc((size_t)p.P2 * p.M2));
   PYSDR_HIP_CHECK(e->d_tw.alloc((size_t)p.M2));
   PYSDR_HIP_CHECK(e->d_perm.alloc((size_t)p.Q));
   PYSDR_HIP_CHECK(e->d_a0.alloc((size_t)p.nk1));
-  PYSDR_HIP_CHECK(hipMemcpy(e->d_tw.get(), tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+  PYSDR_HIP_CHECK(hipMemcpy(e->d_tw.get(), tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
   PYSDR_HIP_CHECK(hipMemcpy(e->d_perm.get(), perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice));
   PYSDR_HIP_CHECK(hipMemcpy(e->d_a0.get(), a0.data(), a0.size() * sizeof(int), hipMemcpyHostToDevice));
   return fine_prepare(p);
@@ -120,15 +104,8 @@ int fine_process(pysdr_chan* c, const void* iq, int n, int on_device, void* out,
     a.Q = pl.Q; a.Mf = pl.Mf; a.ng = pl.ng;
     a.y = reinterpret_cast<float*>(out_on_device ? static_cast<float2*>(out) : c->d_out.get());
     a.pitch = out_on_device ? out_pitch : (long long)c->out_cap;
-    a.npass = pl.npass;
     a.magic_M2 = magic_of(pl.M2); a.magic_Q = magic_of(pl.Q);
-    int nb = pl.M2;
-    for (int s = 0; s < pl.npass; ++s) {
-      a.radix[s] = pl.radix[s];
-      a.magic_per[s] = magic_of(pl.M2 / pl.radix[s]);
-      a.magic_nq[s] = nb / pl.radix[s] > 1 ? magic_of(nb / pl.radix[s]) : 0;
-      nb /= pl.radix[s];
-    }
+    a.fft = fft_passes(pl.M2, pl.npass, pl.radix);
     rc = launch_fine(pl, a, t.gx, t.gy, st);
     if (rc) return rc;
   }

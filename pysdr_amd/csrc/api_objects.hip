@@ -101,31 +101,16 @@ int rtty_alloc(pysdr_rtty* r) {
 
 int chan_alloc(pysdr_chan* c) {
   const int M = c->M, nk = c->nk;
-  // twiddles in float64, and where the in-place passes leave channel k: k = k1 + R1 (k2 + R2 (...)) sits at
-  // k1 M / R1 + k2 M / (R1 R2) + ...
-  std::vector<float2> tw(M);
-  for (int j = 0; j < M; ++j) {
-    const double ph = 2.0 * M_PI * (double)j / (double)M;
-    tw[j] = make_float2((float)std::cos(ph), (float)std::sin(ph));
-  }
-  std::vector<int> perm(nk);
-  for (int a = 0; a < nk; ++a) {
-    int k = (c->k_first + a) % M, nb = M, pos = 0;
-    for (int s = 0; s < c->plan.npass; ++s) {
-      const int R = c->plan.radix[s];
-      nb /= R;
-      pos += (k % R) * nb;
-      k /= R;
-    }
-    perm[a] = pos;
-  }
+  const std::vector<float> tw = fft_twiddles(M);
+  std::vector<int> perm(nk);                      // where the passes leave the channel of row a
+  for (int a = 0; a < nk; ++a) perm[a] = fft_position((c->k_first + a) % M, M, c->plan.npass, c->plan.radix);
   PYSDR_HIP_CHECK(c->stream.create(hipStreamNonBlocking));
   PYSDR_HIP_CHECK(c->d_hist[0].alloc((size_t)c->H));
   PYSDR_HIP_CHECK(c->d_hist[1].alloc((size_t)c->H));
   PYSDR_HIP_CHECK(c->d_taps.alloc((size_t)(c->H + 1)));            // [Pmax][M]
   PYSDR_HIP_CHECK(c->d_tw.alloc((size_t)M));
   PYSDR_HIP_CHECK(c->d_perm.alloc((size_t)nk));
-  PYSDR_HIP_CHECK(hipMemcpy(c->d_tw.get(), tw.data(), (size_t)M * sizeof(float2), hipMemcpyHostToDevice));
+  PYSDR_HIP_CHECK(hipMemcpy(c->d_tw.get(), tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice));
   PYSDR_HIP_CHECK(hipMemcpy(c->d_perm.get(), perm.data(), (size_t)nk * sizeof(int), hipMemcpyHostToDevice));
   return chan_prepare(c->plan);
 }
@@ -525,15 +510,8 @@ int pysdr_chan_process(pysdr_chan* c, const void* iq, int n, int on_device, void
     a.taps = c->d_taps.get(); a.tw = c->d_tw.get(); a.perm = c->d_perm.get(); a.nk = c->nk;
     a.y = out_on_device ? static_cast<float2*>(out) : c->d_out.get();
     a.pitch = out_on_device ? out_pitch : (long long)c->out_cap;
-    a.npass = pl.npass;
     a.magic_M = magic_of(c->M); a.magic_fw = magic_of(pl.fw);
-    int nb = c->M;
-    for (int s = 0; s < pl.npass; ++s) {
-      a.radix[s] = pl.radix[s];
-      a.magic_per[s] = magic_of(c->M / pl.radix[s]);
-      a.magic_nq[s] = nb / pl.radix[s] > 1 ? magic_of(nb / pl.radix[s]) : 0;
-      nb /= pl.radix[s];
-    }
+    a.fft = fft_passes(c->M, pl.npass, pl.radix);
     const int grid = (nf + pl.fw - 1) / pl.fw;
     a.xq = grid / 8; a.xr = grid % 8;
     rc = launch_chan(pl, a, grid, st);

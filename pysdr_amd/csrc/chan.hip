@@ -9,77 +9,17 @@
 //      item keeps a sliding register window of FI samples, shifts it by C per tap row and loads only C new samples: the
 //      input comes from memory once, its re-use across work items from the L2.  No window is staged in LDS, so a 256 KB
 //      window (M = 4096, 8 taps per branch) needs no special case.  v_m[r] goes to LDS at index (r - mD) mod M.
-//   2. FFT: in-place decimation-in-frequency passes of radix 5 / 4 / 2 over all fw frames in LDS; twiddles from a table
-//      e^{+j 2 pi j / M} computed in float64 on the host.  The result is left in digit-reversed order.
+//   2. FFT: in-place decimation-in-frequency passes of radix 5 / 4 / 2 over all fw frames in LDS (fft_lds.h, shared with
+//      fine.hip); twiddles from a table e^{+j 2 pi j / M} computed in float64 on the host.  The result is left in
+//      digit-reversed order.
 //   3. Store: row a = channel (k_first + a) mod M of the channel-major output takes its fw frames from LDS position
 //      perm[a] (the digit reversal, a host table); consecutive lanes write consecutive frames of a row.
 // No intermediate goes through memory; the only other launch of a call is the roll of the input history.
+#include "fft_lds.h"
 #include "objects_plan.h"
 
 namespace pysdr {
 namespace {
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) {
-  return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// DFT of R points with the kernel e^{+j 2 pi n k / R}
-template <int R>
-__device__ __forceinline__ void bfly(float2* v);
-template <>
-__device__ __forceinline__ void bfly<2>(float2* v) {
-  const float2 a = v[0], b = v[1];
-  v[0] = cadd(a, b);
-  v[1] = csub(a, b);
-}
-template <>
-__device__ __forceinline__ void bfly<4>(float2* v) {
-  const float2 s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]), s13 = cadd(v[1], v[3]), d13 = csub(v[1], v[3]);
-  v[0] = cadd(s02, s13);
-  v[2] = csub(s02, s13);
-  v[1] = make_float2(d02.x - d13.y, d02.y + d13.x);      // d02 + j d13
-  v[3] = make_float2(d02.x + d13.y, d02.y - d13.x);      // d02 - j d13
-}
-template <>
-__device__ __forceinline__ void bfly<5>(float2* v) {
-  constexpr float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;    // cos(2 pi / 5), cos(4 pi / 5)
-  constexpr float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;     // sin(2 pi / 5), sin(4 pi / 5)
-  const float2 a = v[0];
-  const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]), t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
-  v[0] = cadd(cadd(a, t1), t2);
-  const float2 m1 = make_float2((a.x + c1 * t1.x) + c2 * t2.x, (a.y + c1 * t1.y) + c2 * t2.y);
-  const float2 m2 = make_float2((a.x + c2 * t1.x) + c1 * t2.x, (a.y + c2 * t1.y) + c1 * t2.y);
-  const float2 n1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
-  const float2 n2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-  v[1] = make_float2(m1.x - n1.y, m1.y + n1.x);          // m1 + j n1
-  v[4] = make_float2(m1.x + n1.y, m1.y - n1.x);
-  v[2] = make_float2(m2.x - n2.y, m2.y + n2.x);          // m2 + j n2
-  v[3] = make_float2(m2.x + n2.y, m2.y - n2.x);
-}
-
-// One in-place decimation-in-frequency pass over every frame: blocks of nb points split into R blocks of nq = nb / R;
-// output k1 of the butterfly at n2 is turned by e^{+j 2 pi n2 k1 / nb} (nothing to turn in the last pass, nq = 1).
-template <int R>
-__device__ __forceinline__ void fft_pass(float2* sm, const ChanArgs& a, int nb, uint32_t magic_per, uint32_t magic_nq) {
-  const int nq = nb / R, per = a.M / R, total = a.fw * per, tws = a.M / nb;
-  for (int it = threadIdx.x; it < total; it += blockDim.x) {
-    const int f = (int)__umulhi((uint32_t)it, magic_per), j = it - f * per;
-    const int b = nq > 1 ? (int)__umulhi((uint32_t)j, magic_nq) : j, n2 = j - b * nq;
-    float2* p = sm + f * a.mp + b * nb + n2;
-    float2 v[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) v[i] = p[i * nq];
-    bfly<R>(v);
-    if (nq > 1) {
-#pragma unroll
-      for (int i = 1; i < R; ++i) v[i] = cmul(v[i], a.tw[n2 * i * tws]);
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) p[i * nq] = v[i];
-  }
-}
 
 template <int C, int FI>
 __global__ __launch_bounds__(1024) void chan_kernel(const ChanArgs a) {
@@ -136,11 +76,11 @@ __global__ __launch_bounds__(1024) void chan_kernel(const ChanArgs a) {
   __syncthreads();
   // ---- 2. inverse DFT of every frame, in place, digit-reversed result
   int nb = a.M;
-  for (int s = 0; s < a.npass; ++s) {
-    const int R = a.radix[s];
-    if (R == 4) fft_pass<4>(sm, a, nb, a.magic_per[s], a.magic_nq[s]);
-    else if (R == 5) fft_pass<5>(sm, a, nb, a.magic_per[s], a.magic_nq[s]);
-    else fft_pass<2>(sm, a, nb, a.magic_per[s], a.magic_nq[s]);
+  for (int s = 0; s < a.fft.npass; ++s) {
+    const int R = a.fft.radix[s];
+    if (R == 4) fft_pass<4>(sm, a.tw, a.M, a.mp, a.fw, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
+    else if (R == 5) fft_pass<5>(sm, a.tw, a.M, a.mp, a.fw, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
+    else fft_pass<2>(sm, a.tw, a.M, a.mp, a.fw, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
     nb /= R;
     __syncthreads();
   }

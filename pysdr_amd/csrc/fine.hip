@@ -10,79 +10,15 @@
 // (fine_tile, fine_plan.h) -- all frames when a call completes many, many rows when it completes one or two, which
 // chan.hip with its single input stream has no use for.  Work items:
 //   1. FIR: one (row, frame, branch r); consecutive lanes read consecutive samples, the re-use comes from the L2.
-//   2. FFT: as chan.hip's passes, over the workgroup's slots.  (The butterflies are written out here again: chan.hip
-//      stays as it is, bit for bit.)
+//   2. FFT: the very passes of chan.hip, over the workgroup's slots (fft_lds.h holds them for both).
 //   3. Store: consecutive lanes = consecutive frames of one output row.
 // fine_roll then moves the last `hist` samples of every row to its front: one workgroup per row reads all of them into
 // registers before it writes any.
-#include "common.h"
+#include "fft_lds.h"
 #include "fine_plan.h"
 
 namespace pysdr {
 namespace {
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 w) {
-  return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
-}
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// DFT of R points with the kernel e^{+j 2 pi n k / R}
-template <int R>
-__device__ __forceinline__ void bfly(float2* v);
-template <>
-__device__ __forceinline__ void bfly<2>(float2* v) {
-  const float2 a = v[0], b = v[1];
-  v[0] = cadd(a, b);
-  v[1] = csub(a, b);
-}
-template <>
-__device__ __forceinline__ void bfly<4>(float2* v) {
-  const float2 s02 = cadd(v[0], v[2]), d02 = csub(v[0], v[2]), s13 = cadd(v[1], v[3]), d13 = csub(v[1], v[3]);
-  v[0] = cadd(s02, s13);
-  v[2] = csub(s02, s13);
-  v[1] = make_float2(d02.x - d13.y, d02.y + d13.x);      // d02 + j d13
-  v[3] = make_float2(d02.x + d13.y, d02.y - d13.x);      // d02 - j d13
-}
-template <>
-__device__ __forceinline__ void bfly<5>(float2* v) {
-  constexpr float c1 = 0.30901699437494742f, c2 = -0.80901699437494742f;    // cos(2 pi / 5), cos(4 pi / 5)
-  constexpr float s1 = 0.95105651629515357f, s2 = 0.58778525229247313f;     // sin(2 pi / 5), sin(4 pi / 5)
-  const float2 a = v[0];
-  const float2 t1 = cadd(v[1], v[4]), t2 = cadd(v[2], v[3]), t3 = csub(v[1], v[4]), t4 = csub(v[2], v[3]);
-  v[0] = cadd(cadd(a, t1), t2);
-  const float2 m1 = make_float2((a.x + c1 * t1.x) + c2 * t2.x, (a.y + c1 * t1.y) + c2 * t2.y);
-  const float2 m2 = make_float2((a.x + c2 * t1.x) + c1 * t2.x, (a.y + c2 * t1.y) + c1 * t2.y);
-  const float2 n1 = make_float2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
-  const float2 n2 = make_float2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
-  v[1] = make_float2(m1.x - n1.y, m1.y + n1.x);          // m1 + j n1
-  v[4] = make_float2(m1.x + n1.y, m1.y - n1.x);
-  v[2] = make_float2(m2.x - n2.y, m2.y + n2.x);          // m2 + j n2
-  v[3] = make_float2(m2.x + n2.y, m2.y - n2.x);
-}
-
-// One in-place decimation-in-frequency pass over every slot: blocks of nb points split into R blocks of nq = nb / R;
-// output k1 of the butterfly at n2 is turned by e^{+j 2 pi n2 k1 / nb} (nothing to turn in the last pass, nq = 1).
-template <int R>
-__device__ __forceinline__ void fft_pass(float2* sm, const FineArgs& a, const float2* tw, int slots, int nb, uint32_t magic_per,
-                                         uint32_t magic_nq) {
-  const int nq = nb / R, per = a.M2 / R, total = slots * per, tws = a.M2 / nb;
-  for (int it = threadIdx.x; it < total; it += blockDim.x) {
-    const int f = (int)__umulhi((uint32_t)it, magic_per), j = it - f * per;
-    const int b = nq > 1 ? (int)__umulhi((uint32_t)j, magic_nq) : j, n2 = j - b * nq;
-    float2* p = sm + f * a.mp + b * nb + n2;
-    float2 v[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) v[i] = p[i * nq];
-    bfly<R>(v);
-    if (nq > 1) {
-#pragma unroll
-      for (int i = 1; i < R; ++i) v[i] = cmul(v[i], tw[n2 * i * tws]);
-    }
-#pragma unroll
-    for (int i = 0; i < R; ++i) p[i * nq] = v[i];
-  }
-}
 
 __global__ __launch_bounds__(kFineThreads) void fine_kernel(const FineArgs a) {
   extern __shared__ float2 sm[];
@@ -114,11 +50,11 @@ __global__ __launch_bounds__(kFineThreads) void fine_kernel(const FineArgs a) {
   __syncthreads();
   // ---- 2. inverse DFT of every slot, in place, digit-reversed result
   int nb = a.M2;
-  for (int s = 0; s < a.npass; ++s) {
-    const int R = a.radix[s];
-    if (R == 4) fft_pass<4>(sm, a, tw, slots, nb, a.magic_per[s], a.magic_nq[s]);
-    else if (R == 5) fft_pass<5>(sm, a, tw, slots, nb, a.magic_per[s], a.magic_nq[s]);
-    else fft_pass<2>(sm, a, tw, slots, nb, a.magic_per[s], a.magic_nq[s]);
+  for (int s = 0; s < a.fft.npass; ++s) {
+    const int R = a.fft.radix[s];
+    if (R == 4) fft_pass<4>(sm, tw, a.M2, a.mp, slots, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
+    else if (R == 5) fft_pass<5>(sm, tw, a.M2, a.mp, slots, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
+    else fft_pass<2>(sm, tw, a.M2, a.mp, slots, nb, a.fft.magic_per[s], a.fft.magic_nq[s]);
     nb /= R;
     __syncthreads();
   }

@@ -2,12 +2,15 @@
 // second, batched stage runs an M2-channel channelizer on every coarse row that is needed and keeps the Q = M2 / C1
 // channels that lie inside the row's own spacing.  Here: the shape rules, the map between a fine channel G and (coarse
 // row k1, second-stage channel k2), the range of coarse rows a circular range of G uses, the launch geometry of fine.hip
-// and the arithmetic of the row buffer (history in front of every row, roll).  The kernel (fine.hip), the host half
+// and the arithmetic of the row buffer (history in front of every row, roll); the second stage's FFT is the first
+// stage's, and its pure half is fft_plan.h.  The kernel (fine.hip), the host half
 // (api_fine.hip) and tests/fine_plan/plan_main.cpp use the very same functions.  Plain C++: nothing here calls the HIP
 // runtime, and the only trace of the device is the function qualifier below.
 #pragma once
 
 #include <cstdint>
+
+#include "fft_plan.h"
 
 #if defined(__HIPCC__)
 #define PYSDR_FINE_HD __host__ __device__
@@ -17,7 +20,6 @@
 
 namespace pysdr {
 
-constexpr int kFineMaxPass = 8;
 constexpr int kFineM2Min = 16, kFineM2Max = 1024;
 constexpr int kFineNgMax = 1 << 16;          // fine rows one object may deliver
 constexpr int kFineLdsElems = 8192;          // complex elements of LDS a workgroup fills with frames (64 KB: two workgroups per CU)
@@ -34,7 +36,7 @@ struct FinePlan {
   int D = 0;           // D1 D2
   int g_first = 0, ng = 0;
   int k1_first = 0, nk1 = 0;   // the circular range of coarse rows the fine range uses
-  int npass = 0, radix[kFineMaxPass] = {};
+  int npass = 0, radix[kFftMaxPass] = {};     // fft_factor(M2)
   int P2 = 0;          // taps per branch of the second stage
   int hist = 0;        // stage-1 outputs kept in front of every row: P2 M2 rounded up to 16 (>= the P2 M2 - 1 a window reaches back)
   int slots = 0;       // frames per workgroup, a power of two; a launch splits them into rw rows times fw frames
@@ -58,15 +60,6 @@ PYSDR_FINE_HD inline int fine_join(int k1, int q, int Q, int Mf) { return fine_m
 // Output row of kept channel u = q + Q/2 in [0, Q) of the j-th used coarse row; kept if < ng.  a0 = fine_a0(j).
 PYSDR_FINE_HD inline int fine_row_of(int a0, int u, int Mf) { const int a = a0 + u; return a >= Mf ? a - Mf : a; }
 
-inline bool fine_2a5b(int M, int* twos, int* fives) {
-  int t = 0, f = 0;
-  if (M < 1) return false;
-  while (M % 2 == 0) { M /= 2; ++t; }
-  while (M % 5 == 0) { M /= 5; ++f; }
-  *twos = t; *fives = f;
-  return M == 1;
-}
-
 // output row of the first kept channel (q = -Q/2) of the j-th used coarse row
 inline int fine_a0(const FinePlan& p, int j) {
   const int k1 = (p.k1_first + j) % p.M1;
@@ -75,11 +68,12 @@ inline int fine_a0(const FinePlan& p, int j) {
 
 // Pure arithmetic: the plan of a fine channelizer of this shape; false: outside the rules of DESIGN §3 item 20.
 inline bool fine_plan(int M1, int D1, int M2, int D2, int ntaps1, int ntaps2, int g_first, int ng, FinePlan* out) {
-  int t, f;
-  if (M1 < 16 || M1 > 4096 || D1 < 1 || M1 % D1 != 0 || !fine_2a5b(M1, &t, &f)) return false;
+  FinePlan p;
+  int npass1, radix1[kFftMaxPass];                               // the first stage's own plan keeps its passes (chan_plan)
+  if (M1 < 16 || M1 > 4096 || D1 < 1 || M1 % D1 != 0 || !fft_factor(M1, &npass1, radix1)) return false;
   const int C1 = M1 / D1;
   if (C1 != 2 && C1 != 4) return false;                          // a coarse row must carry more than its own spacing
-  if (M2 < kFineM2Min || M2 > kFineM2Max || D2 < 1 || M2 % D2 != 0 || !fine_2a5b(M2, &t, &f)) return false;
+  if (M2 < kFineM2Min || M2 > kFineM2Max || D2 < 1 || M2 % D2 != 0 || !fft_factor(M2, &p.npass, p.radix)) return false;
   const int C2 = M2 / D2;
   if (C2 != 1 && C2 != 2 && C2 != 4) return false;
   if (M2 % C1 != 0) return false;
@@ -88,16 +82,12 @@ inline bool fine_plan(int M1, int D1, int M2, int D2, int ntaps1, int ntaps2, in
   if (ntaps1 < 1 || ntaps1 > 16 * M1 || ntaps2 < 1 || ntaps2 > 16 * M2) return false;
   const int Mf = M1 * Q;
   if (g_first < 0 || g_first >= Mf || ng < 1 || ng > Mf || ng > kFineNgMax) return false;
-  FinePlan p;
   p.M1 = M1; p.D1 = D1; p.M2 = M2; p.D2 = D2; p.C1 = C1; p.C2 = C2; p.Q = Q; p.Mf = Mf; p.D = D1 * D2;
   p.g_first = g_first; p.ng = ng;
   // coarse rows: from the row of g_first to the row of the last channel, never more than all of them
   const int c0 = fine_floor_div(g_first + Q / 2, Q), c1 = fine_floor_div(g_first + ng - 1 + Q / 2, Q);
   p.k1_first = fine_mod(c0, M1);
   p.nk1 = c1 - c0 + 1 > M1 ? M1 : c1 - c0 + 1;
-  for (int i = 0; i < f; ++i) p.radix[p.npass++] = 5;
-  for (int i = 0; i < t / 2; ++i) p.radix[p.npass++] = 4;
-  if (t & 1) p.radix[p.npass++] = 2;
   p.P2 = (ntaps2 + M2 - 1) / M2;
   p.hist = (p.P2 * M2 + 15) & ~15;
   p.mp = M2 | 1;
@@ -150,8 +140,8 @@ struct FineArgs {
   int Q, Mf, ng;
   float* y;               // float2 y[a * pitch + (m - mf)]
   long long pitch;
-  int npass, radix[kFineMaxPass];
-  uint32_t magic_M2, magic_Q, magic_per[kFineMaxPass], magic_nq[kFineMaxPass];
+  uint32_t magic_M2, magic_Q;
+  FftPasses fft;          // of M2 points (fft_plan.h)
 };
 
 }  // namespace pysdr

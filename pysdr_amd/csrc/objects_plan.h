@@ -8,6 +8,7 @@
 #pragma once
 
 #include "common.h"
+#include "fft_plan.h"
 
 namespace pysdr {
 
@@ -50,13 +51,12 @@ struct RttyArgs {         // one decode call: lines n0 .. n0 + nlines - 1, decis
 };
 int launch_rtty_decode(const RttyArgs& a, hipStream_t st);   // rt_gather .. rt_sc2, (rt_decide, rt_emit,) rt_find
 
-// ---- polyphase channelizer (chan.hip) --------------------------------------------------
-constexpr int kChanMaxPass = 8;
+// ---- polyphase channelizer (chan.hip; its FFT's passes, multipliers, positions and twiddles: fft_plan.h) ----------------
 constexpr int kChanLdsElems = 16384;      // complex LDS elements a workgroup may hold (128 KB of the 160 KB)
 constexpr int kChanMaxIn = 1 << 28;
 
 struct ChanPlan {
-  int npass = 0, radix[kChanMaxPass] = {};
+  int npass = 0, radix[kFftMaxPass] = {};     // fft_factor(M)
   int C = 0;          // M / D
   int fw = 0;         // frames per workgroup
   int fi = 0;         // frames per FIR work item
@@ -70,15 +70,9 @@ inline bool chan_plan(int M, int D, ChanPlan* p) {
   if (M < 16 || M > 4096 || D < 1 || M % D != 0) return false;
   const int C = M / D;
   if (C != 1 && C != 2 && C != 4) return false;
-  int twos = 0, fives = 0, m = M;
-  while (m % 2 == 0) { m /= 2; ++twos; }
-  while (m % 5 == 0) { m /= 5; ++fives; }
-  if (m != 1) return false;
   ChanPlan q;
+  if (!fft_factor(M, &q.npass, q.radix)) return false;
   q.C = C;
-  for (int i = 0; i < fives; ++i) q.radix[q.npass++] = 5;
-  for (int i = 0; i < twos / 2; ++i) q.radix[q.npass++] = 4;
-  if (twos & 1) q.radix[q.npass++] = 2;
   // 16 frames = 128-byte row segments while they fit the LDS; small M: as many groups of 16 as fill 256 branches
   if (M <= 256) q.fw = 16 * (256 / M);
   else if (M * 16 <= kChanLdsElems) q.fw = 16;
@@ -91,8 +85,6 @@ inline bool chan_plan(int M, int D, ChanPlan* p) {
   *p = q;
   return true;
 }
-
-inline uint32_t magic_of(int d) { return (uint32_t)(0x100000000ull / (unsigned)d) + 1u; }   // d >= 2; exact n / d while n d < 2^32
 
 struct ChanArgs {
   const float2* x;        // this call's samples, x[0] = absolute sample s0
@@ -108,8 +100,8 @@ struct ChanArgs {
   int nk;
   float2* y;              // y[a * pitch + (m - mf)]
   long long pitch;
-  int npass, radix[kChanMaxPass];
-  uint32_t magic_M, magic_fw, magic_per[kChanMaxPass], magic_nq[kChanMaxPass];
+  uint32_t magic_M, magic_fw;
+  FftPasses fft;          // of M points (fft_plan.h)
   int xq, xr;             // grid / 8, grid % 8: the workgroups that share an L2 take consecutive runs of frames
 };
 int chan_prepare(const ChanPlan& p);            // more than 64 KB of LDS is an opt-in per kernel

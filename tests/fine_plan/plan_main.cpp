@@ -2,7 +2,10 @@
 // re-derivation, the map between fine channels and (coarse row, kept channel) against brute force, the tiles of a launch,
 // and a stream of ragged calls walked with the very index functions the kernel and the host half use -- every tap read
 // of every frame must find the stage-1 output it wants in a row buffer of exactly the planned size (AddressSanitizer
-// watches its ends), and the roll must leave the history the next call needs.  Built and run by tests/test_fine_plan.py.
+// watches its ends), and the roll must leave the history the next call needs.  Before that, the pure half of the FFT
+// both stages share (pysdr_amd/csrc/fft_plan.h) for every size either stage accepts: the passes, where they leave every
+// channel, the multipliers of their index arithmetic and the twiddle table.  Built and run by tests/test_fine_plan.py.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <set>
@@ -73,7 +76,7 @@ static void check_tiles(const FinePlan& p) {
   CHECK(p.hist >= p.P2 * p.M2 && p.hist % 16 == 0 && p.hist <= kFineRollThreads * kFineRollPer);
   int prod = 1;
   for (int s = 0; s < p.npass; ++s) prod *= p.radix[s];
-  CHECK(prod == p.M2 && p.npass <= kFineMaxPass);
+  CHECK(prod == p.M2 && p.npass <= kFftMaxPass);
   for (int nf : {1, 2, 3, 15, 16, 17, 63, 64, 65, 257}) {
     const FineTile t = fine_tile(p, nf);
     CHECK(t.fw * t.rw == p.slots && (t.fw & (t.fw - 1)) == 0);
@@ -140,7 +143,88 @@ static void walk_stream(const FinePlan& p, int ntaps2, unsigned seed) {
   CHECK(frames > 0);
 }
 
+// ---- the FFT's pure half (fft_plan.h), shared by both stages: every M = 2^a 5^b in [16, 4096]
+static long ffts = 0;
+
+// frames a workgroup of either stage holds for M points, written down again (chan_plan, fine_plan): the most work items a
+// pass can present is that many times M / R
+static int most_slots(int M) {
+  const int fw = M <= 256 ? 16 * (256 / M) : M * 16 <= 16384 ? 16 : M * 8 <= 16384 ? 8 : 4;
+  int s = 1;
+  while (2 * s * M <= 8192 && 2 * s <= 64) s *= 2;
+  return M <= 1024 && s > fw ? s : fw;
+}
+
+static void check_fft(int M) {
+  int npass = -1, radix[kFftMaxPass];
+  const bool ok = fft_factor(M, &npass, radix);
+  CHECK(ok == smooth(M));
+  if (!ok) return;
+  ++ffts;
+  // the passes: fives, fours, then a two, making M
+  int prod = 1;
+  CHECK(npass >= 1 && npass <= kFftMaxPass);
+  for (int s = 0; s < npass; ++s) {
+    prod *= radix[s];
+    CHECK(radix[s] == 5 || radix[s] == 4 || (radix[s] == 2 && s == npass - 1));
+    CHECK(s == 0 || radix[s] <= radix[s - 1]);
+  }
+  CHECK(prod == M);
+  // where channel k is left: a permutation, the mixed-radix digit reversal -- digit s of k (least significant first,
+  // radix[s]) becomes the s-th most significant digit of the position
+  std::vector<int> hit(M, 0);
+  for (int k = 0; k < M; ++k) {
+    const int pos = fft_position(k, M, npass, radix);
+    CHECK(pos >= 0 && pos < M);
+    if (pos >= 0 && pos < M) ++hit[pos];
+    int rest = k, want = 0;
+    for (int s = 0; s < npass; ++s) {
+      want = want * radix[s] + rest % radix[s];
+      rest /= radix[s];
+    }
+    CHECK(rest == 0 && pos == want);
+  }
+  for (int i = 0; i < M; ++i) CHECK(hit[i] == 1);
+  // the multipliers divide exactly, for every work item a pass of either kernel can present
+  const FftPasses f = fft_passes(M, npass, radix);
+  CHECK(f.npass == npass);
+  const int slots = most_slots(M);
+  CHECK(slots * M <= 16384);
+  int nb = M;
+  for (int s = 0; s < npass; ++s) {
+    const int R = radix[s], per = M / R, nq = nb / R;
+    CHECK(f.radix[s] == R && f.magic_per[s] == magic_of(per));
+    for (int it = 0; it < slots * per; ++it) CHECK((int)(((uint64_t)it * f.magic_per[s]) >> 32) == it / per);
+    if (nq > 1) {
+      CHECK(f.magic_nq[s] == magic_of(nq));
+      for (int j = 0; j < per; ++j) CHECK((int)(((uint64_t)j * f.magic_nq[s]) >> 32) == j / nq);
+    } else {
+      CHECK(f.magic_nq[s] == 0 && s == npass - 1);
+    }
+    nb /= R;
+  }
+  CHECK(nb == 1);
+  for (int s = npass; s < kFftMaxPass; ++s) CHECK(f.radix[s] == 0 && f.magic_per[s] == 0 && f.magic_nq[s] == 0);
+}
+
+static void check_twiddles(int M) {
+  const std::vector<float> tw = fft_twiddles(M);
+  CHECK(tw.size() == 2 * (size_t)M);
+  for (int j = 0; j < M; ++j) {
+    const double ph = 2.0 * M_PI * (double)j / (double)M;
+    CHECK(tw.at(2 * (size_t)j) == (float)std::cos(ph) && tw.at(2 * (size_t)j + 1) == (float)std::sin(ph));
+  }
+  CHECK(tw[0] == 1.0f && tw[1] == 0.0f);
+}
+
 int main() {
+  for (int M = 16; M <= 4096; ++M) check_fft(M);
+  {
+    int n, r[kFftMaxPass];
+    CHECK(!fft_factor(0, &n, r) && !fft_factor(-16, &n, r) && !fft_factor(48, &n, r) && fft_factor(1, &n, r) && n == 0);
+    CHECK(!fft_factor(1 << 17, &n, r) && fft_factor(1 << 16, &n, r) && n == kFftMaxPass);   // never more passes than the arrays hold
+  }
+  for (int M : {16, 625, 4096}) check_twiddles(M);
   const int M1s[] = {8, 16, 20, 48, 64, 250, 4096, 8192}, C1s[] = {1, 2, 4, 8};
   const int M2s[] = {8, 10, 16, 20, 24, 32, 40, 50, 64, 250, 640, 1024, 1280, 2048}, C2s[] = {1, 2, 4, 5, 8};
   for (int M1 : M1s) for (int C1 : C1s) for (int M2 : M2s) for (int C2 : C2s) {
@@ -175,6 +259,6 @@ int main() {
       walk_stream(p, n2, 7u + (unsigned)n2);
     }
   if (failures) return 1;
-  std::printf("FINE_PLAN_OK %ld plans\n", plans);
+  std::printf("FINE_PLAN_OK %ld plans, %ld FFT sizes\n", plans, ffts);
   return 0;
 }

@@ -634,6 +634,27 @@ int launch_rtty_decode(const RttyArgs& a, hipStream_t st) {
   return PYSDR_OK;
 }
 
+// ---- the FFT passes of both channelizer stages (fft_lds.h, the loop in each kernel): what a kernel is handed for M points against the plan's
+// npass / radix[] -- the same passes, making M; every multiplier magic_of of the divisor it stands for (M / R, and
+// nq = nb / R or 0 where nq = 1); tw[0, M) read; every entry of perm[0, nperm) an LDS position of a frame
+static void trace_passes(Line& l, const FftPasses& f) {
+  for (int s = 0; s < f.npass; ++s) l.i(rk("radix", s).c_str(), f.radix[s]).i(rk("mper", s).c_str(), f.magic_per[s]).i(rk("mnq", s).c_str(), f.magic_nq[s]);
+}
+static void check_passes(const FftPasses& f, int M, int npass, const int* radix, const float* tw, const int* perm, int nperm) {
+  SAN_CHECK(f.npass == npass && npass >= 1 && npass <= kFftMaxPass, "npass %d, the plan's %d", f.npass, npass);
+  int nb = M;
+  for (int s = 0; s < f.npass; ++s) {
+    const int R = f.radix[s];
+    SAN_CHECK(R == radix[s] && R >= 2 && nb % R == 0, "radix[%d] = %d, the plan's %d", s, R, radix[s]);
+    SAN_CHECK(f.magic_per[s] == magic_of(M / R), "magic_per[%d] = %u for %d", s, f.magic_per[s], M / R);
+    SAN_CHECK(f.magic_nq[s] == (nb / R > 1 ? magic_of(nb / R) : 0u), "magic_nq[%d] = %u for %d", s, f.magic_nq[s], nb / R);
+    nb /= R;
+  }
+  SAN_CHECK(nb == 1, "passes do not make %d", M);
+  read_all(tw, 2 * (size_t)M);
+  for (int r = 0; r < nperm; ++r) SAN_CHECK(perm[r] >= 0 && perm[r] < M, "perm[%d] = %d", r, perm[r]);
+}
+
 // ---- polyphase channelizer
 int chan_prepare(const ChanPlan& p) {
   SAN_CHECK(p.lds_bytes == p.fw * p.mp * (int)sizeof(float2) && p.lds_bytes <= 160 * 1024, "LDS %d", p.lds_bytes);
@@ -647,9 +668,9 @@ int launch_chan(const ChanPlan& p, const ChanArgs& a, int grid, hipStream_t st) 
     Line l("launch_chan");
     l.st(st).i("grid", grid).i("threads", p.threads).i("lds", p.lds_bytes).i("C", p.C).i("fi", p.fi).i("H", a.H).i("n", a.n).i("off0", a.off0)
         .i("mf_lo", a.mf_lo).i("nframes", a.nframes).i("M", a.M).i("D", a.D).i("P", a.P).i("mp", a.mp).i("fw", a.fw).i("nk", a.nk).i("pitch", a.pitch)
-        .i("npass", a.npass).i("magic_M", a.magic_M).i("magic_fw", a.magic_fw).i("xq", a.xq).i("xr", a.xr)
+        .i("npass", a.fft.npass).i("magic_M", a.magic_M).i("magic_fw", a.magic_fw).i("xq", a.xq).i("xr", a.xr)
         .p("x", a.x).p("hist", a.hist).p("taps", a.taps).p("tw", a.tw).p("perm", a.perm).p("y", a.y);
-    for (int s = 0; s < a.npass; ++s) l.i(rk("radix", s).c_str(), a.radix[s]).i(rk("mper", s).c_str(), a.magic_per[s]).i(rk("mnq", s).c_str(), a.magic_nq[s]);
+    trace_passes(l, a.fft);
   }
   SAN_CHECK(grid == a.xq * 8 + a.xr && a.xr >= 0 && a.xr < 8, "grid %d != xq %d * 8 + xr %d", grid, a.xq, a.xr);
   SAN_CHECK(a.nframes >= 1 && (long long)grid * a.fw >= a.nframes && (long long)(grid - 1) * a.fw < a.nframes, "grid %d of %d frames covers %d", grid, a.fw, a.nframes);
@@ -657,14 +678,11 @@ int launch_chan(const ChanPlan& p, const ChanArgs& a, int grid, hipStream_t st) 
   SAN_CHECK(a.off0 >= 0 && a.off0 < a.D && (long long)(a.nframes - 1) * a.D + a.off0 < a.n, "last frame ends at %lld of %d", (long long)(a.nframes - 1) * a.D + a.off0, a.n);
   SAN_CHECK(a.P >= 1 && a.P * a.M - 1 <= a.H, "P %d M %d reach behind the history of %d", a.P, a.M, a.H);
   SAN_CHECK(a.pitch >= a.nframes, "pitch %lld < %d frames", a.pitch, a.nframes);
-  int nb = a.M;
-  for (int s = 0; s < a.npass; ++s) { SAN_CHECK(a.radix[s] >= 2 && nb % a.radix[s] == 0, "radix"); nb /= a.radix[s]; }
-  SAN_CHECK(nb == 1, "passes do not make M");
+  SAN_CHECK(a.magic_M == magic_of(a.M) && a.magic_fw == magic_of(a.fw), "magic_M %u for %d, magic_fw %u for %d", a.magic_M, a.M, a.magic_fw, a.fw);
+  check_passes(a.fft, a.M, p.npass, p.radix, reinterpret_cast<const float*>(a.tw), a.perm, a.nk);
   read_all(a.x, (size_t)a.n);
   read_all(a.hist, (size_t)a.H);
   read_all(a.taps, (size_t)a.P * a.M);
-  read_all(a.tw, (size_t)a.M);
-  for (int r = 0; r < a.nk; ++r) SAN_CHECK(a.perm[r] >= 0 && a.perm[r] < a.M, "perm[%d] = %d", r, a.perm[r]);
   for (int r = 0; r < a.nk; ++r) write_all(a.y + (size_t)r * (size_t)a.pitch, (size_t)a.nframes);
   return PYSDR_OK;
 }
@@ -797,10 +815,10 @@ int launch_fine(const FinePlan& p, const FineArgs& a, int gx, int gy, hipStream_
     Line l("launch_fine");
     l.st(st).i("gx", gx).i("gy", gy).i("lds", p.lds_bytes).i("pitch1", a.pitch1).i("hist", a.hist).i("M2", a.M2).i("D2", a.D2).i("C2", a.C2)
         .i("P2", a.P2).i("L2", a.L2).i("mp", a.mp).i("off", a.off).i("mf_lo", a.mf_lo).i("nframes", a.nframes).i("nk1", a.nk1).i("fw", a.fw)
-        .i("rw", a.rw).i("fw_shift", a.fw_shift).i("Q", a.Q).i("Mf", a.Mf).i("ng", a.ng).i("pitch", a.pitch).i("npass", a.npass)
+        .i("rw", a.rw).i("fw_shift", a.fw_shift).i("Q", a.Q).i("Mf", a.Mf).i("ng", a.ng).i("pitch", a.pitch).i("npass", a.fft.npass)
         .i("magic_M2", a.magic_M2).i("magic_Q", a.magic_Q)
         .p("rows", a.rows).p("taps", a.taps).p("tw", a.tw).p("perm", a.perm).p("a0", a.a0).p("y", a.y);
-    for (int s = 0; s < a.npass; ++s) l.i(rk("radix", s).c_str(), a.radix[s]).i(rk("mper", s).c_str(), a.magic_per[s]).i(rk("mnq", s).c_str(), a.magic_nq[s]);
+    trace_passes(l, a.fft);
   }
   SAN_CHECK(a.nframes >= 1, "nframes %d", a.nframes);
   const FineTile t = fine_tile(p, a.nframes);
@@ -811,12 +829,8 @@ int launch_fine(const FinePlan& p, const FineArgs& a, int gx, int gy, hipStream_
   const long long last = (long long)a.off + (long long)(a.nframes - 1) * a.D2;       // the last frame's newest sample
   SAN_CHECK(a.off >= a.hist && a.off - (a.L2 - 1) >= 0 && last < a.pitch1, "window [%d, %lld] of a row of %lld", a.off - (a.L2 - 1), last, a.pitch1);
   SAN_CHECK(a.pitch >= a.nframes, "pitch %lld < %d frames", a.pitch, a.nframes);
-  int nb = a.M2;
-  for (int s = 0; s < a.npass; ++s) { SAN_CHECK(a.radix[s] == p.radix[s] && nb % a.radix[s] == 0, "radix"); nb /= a.radix[s]; }
-  SAN_CHECK(nb == 1 && a.npass == p.npass, "passes do not make M2");
+  check_passes(a.fft, a.M2, p.npass, p.radix, a.tw, a.perm, a.Q);
   read_all(a.taps, (size_t)a.L2);
-  read_all(a.tw, 2 * (size_t)a.M2);
-  for (int u = 0; u < a.Q; ++u) SAN_CHECK(a.perm[u] >= 0 && a.perm[u] < a.M2, "perm[%d] = %d", u, a.perm[u]);
   for (int j = 0; j < a.nk1; ++j) {
     read_all(a.rows + 2 * (size_t)j * (size_t)a.pitch1, 2 * (size_t)(last + 1));
     SAN_CHECK(a.a0[j] == fine_a0(p, j), "a0[%d] = %d", j, a.a0[j]);

@@ -1,7 +1,8 @@
 """The fine channelizer's plan (pysdr_chan_fine_plan, include/pysdr_hip.h; pysdr_amd/csrc/fine_plan.h): what it accepts and
 refuses and what it reports -- through the library, which needs no device for this -- and the rules, the channel map, the
 tiles, the tap reads and the roll of a stream of ragged calls against brute force in a stand-alone C++ program
-(tests/fine_plan/plan_main.cpp) built with AddressSanitizer + UBSan and run here.  CPU only; nothing that is loaded into
+(tests/fine_plan/plan_main.cpp) built with AddressSanitizer + UBSan and run here.  The same program checks the pure half
+of the FFT that both channelizer stages share (pysdr_amd/csrc/fft_plan.h): passes, digit reversal, multipliers, twiddles.  CPU only; nothing that is loaded into
 Python runs under a sanitizer."""
 import ctypes as C
 import os
@@ -96,6 +97,7 @@ def test_rules_map_tiles_and_the_roll_against_brute_force(tmp_path):
             print("sanitizer runtime not usable here, running the plain build:", p.stderr[-200:])
             continue
         assert p.returncode == 0 and "FINE_PLAN_OK" in p.stdout, (name, p.stdout[-1500:], p.stderr[-3000:])
+        assert "35 FFT sizes" in p.stdout, p.stdout[-1500:]     # every 2^a 5^b in [16, 4096] went through the shared FFT plan's checks
         ran = name
         print(name + ":", p.stdout.strip())
         break
