@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # the diagnostic build (work-skipping ablation switches compiled in) is a different file and is
@@ -201,6 +202,52 @@ def check(rc, what=""):
         msg = L.pysdr_strerror(rc).decode()
         detail = L.pysdr_last_error().decode()
         raise PysdrError(f"{what}: {msg} ({rc}) {detail}")
+
+
+def plan_call(name, nwords, *args):
+    """One ``pysdr_*_plan`` call (no device needed): ``args`` and an int32 array of ``nwords`` for the answer -> the words
+    as a list.  Raises PysdrError outside the plan's rules."""
+    out = (C.c_int32 * nwords)()
+    check(getattr(lib(), name)(*args, out), name)
+    return list(out)
+
+
+class Handle:
+    """One owned object of the C ABI: the library ``_L``, the handle ``_h`` (None before create and after close) and
+    ``DESTROY``, the name of its ``pysdr_*_destroy``.  ``close()`` may be called any number of times; a class that owns
+    more than the handle frees it in ``_release()``."""
+    DESTROY = None
+    _L = _h = None
+
+    def _create(self, name, *args):
+        """the object's create call: ``args`` and, last, where the handle goes"""
+        self._L = lib()
+        hd = C.c_void_p()
+        check(getattr(self._L, name)(*args, C.byref(hd)), name)
+        self._h = hd
+
+    def _check_open(self):
+        if self._h is None:
+            raise PysdrError(f"{type(self).__name__} is closed")
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self.DESTROY)(self._h)
+            self._h = None
+        self._release()
+
+    def _release(self):
+        """what goes after the handle; runs on every close()"""
+
+    def __del__(self):
+        # at interpreter shutdown the HIP runtime may already be torn down: leave the device
+        # memory to process exit rather than call into a dead runtime
+        if sys is None or sys.is_finalizing():
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def device_count():

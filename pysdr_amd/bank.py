@@ -7,7 +7,6 @@ USB, LSB and CW."""
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
@@ -25,9 +24,7 @@ BFO_DEFAULT = 700.0        # Hz, the reference's CW pitch
 def plan(nk, ntaps_af, max_out):
     """What a bank of this shape launches (no device needed): dict of outputs per workgroup, threads, LDS bytes,
     workgroups per row, history samples kept per row.  Raises PysdrError outside the rules."""
-    out = (C.c_int32 * 8)()
-    check(_lib.lib().pysdr_bank_plan(int(nk), int(ntaps_af), int(max_out), out), "pysdr_bank_plan")
-    v = list(out)
+    v = _lib.plan_call("pysdr_bank_plan", 8, int(nk), int(ntaps_af), int(max_out))
     return {"tile": v[0], "threads": v[1], "lds_bytes": v[2], "tiles_per_row": v[3], "history": v[4], "taps_padded": v[5]}
 
 
@@ -51,15 +48,14 @@ def sideband_taps(fs_out, ntaps, mode, af_bw, bfo=BFO_DEFAULT):
     return np.conj(c) if mode == "LSB" else c
 
 
-class ChannelBank:
+class ChannelBank(_lib.Handle):
     """Row a of every output is channel ``(k_first + a) % M`` at ``freqs[a]`` Hz, as for ``Channelizer``."""
     MODES = BANK_MODES
+    DESTROY = "pysdr_bank_destroy"
+    chan = None
 
     def __init__(self, fs, M, D=None, h=None, channels=None, mode="NFM", af_bw=4e3, ntaps_af=255, squelch=0.0, agc=True,
                  device=0, max_in=1 << 22):
-        self._L = _lib.lib()
-        self._h = None
-        self.chan = None
         self.ntaps_af = int(ntaps_af)
         if mode not in self.MODES:
             raise _lib.PysdrError(f"{type(self).__name__}: mode {mode!r} is not one of {self.MODES}")
@@ -68,11 +64,8 @@ class ChannelBank:
         self.chan = Channelizer(fs, M, D, h, channels, device, max_in)
         self.fs, self.M, self.D, self.nk = self.chan.fs, self.chan.M, self.chan.D, self.chan.nk
         self.freqs, self.fs_out = self.chan.freqs, self.chan.fs_out
-        hd = C.c_void_p()
         start = mode if mode in BANK_MODES else BANK_MODES[0]        # create names a real-tap mode; set_mode below sets the real one
-        check(self._L.pysdr_bank_create(self.chan._h, self.fs_out, MODE_INDEX[start], self.ntaps_af, C.byref(hd)),
-              "pysdr_bank_create")
-        self._h = hd
+        self._create("pysdr_bank_create", self.chan._h, self.fs_out, MODE_INDEX[start], self.ntaps_af)
         self.mode, self.af_bw = mode, float(af_bw)
         self.set_mode(mode, af_bw)
         self._agc, self._squelch = True, 0.0
@@ -80,20 +73,9 @@ class ChannelBank:
         self.squelch = squelch
         self.last_n_out = 0
 
-    def close(self):
-        if self._h:
-            self._L.pysdr_bank_destroy(self._h)
-            self._h = None
+    def _release(self):
         if self.chan is not None:
-            self.chan.close()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+            self.chan.close()                                         # after the bank, which holds a pointer into it
 
     def n_out_for(self, n):
         return self.chan.n_out_for(n)

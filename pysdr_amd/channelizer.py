@@ -4,7 +4,6 @@ UP = 1 and the prototype ``h`` would deliver its ``rx.iq`` -- but the input is r
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
@@ -16,57 +15,27 @@ from .design import channelizer_taps
 def plan(M, D, ntaps, k_first=0, nk=None):
     """What a channelizer of this shape launches (no device needed): dict of radices, frames per workgroup, frames per
     FIR work item, threads, LDS bytes, history length, taps per branch.  Raises PysdrError outside the rules."""
-    out = (C.c_int32 * 16)()
-    check(_lib.lib().pysdr_chan_plan(int(M), int(D), int(ntaps), int(k_first), int(M if nk is None else nk), out),
-          "pysdr_chan_plan")
-    v = list(out)
+    v = _lib.plan_call("pysdr_chan_plan", 16, int(M), int(D), int(ntaps), int(k_first), int(M if nk is None else nk))
     return {"radices": v[1:1 + v[0]], "frames_per_wg": v[9], "frames_per_item": v[10], "threads": v[11],
             "lds_bytes": v[12], "history": v[13], "taps_per_branch": v[14]}
 
 
-class Channelizer:
-    """``channels``: None = all M rows, or ``(k_first, nk)``: the circular range of channels k_first, k_first + 1, ...
-    (mod M).  Row a of every output is channel ``(k_first + a) % M`` at ``freqs[a]`` Hz (signed)."""
+class ChannelizerCore(_lib.Handle):
+    """What the one-stage and the two-stage channelizer have in common, and all that their clients (the bank, the CW and
+    PSK decoders) know of them: ``fs``, the raster ``M``, ``D``, ``k_first``, ``nk``, ``freqs``, ``fs_out``, ``max_in``,
+    the count ``n_in`` of samples taken since create / reset, the handle, and two things a kind declares: ``run_in_taps``,
+    the length of its (equivalent) prototype in input samples, and ``prototypes``, ``h`` or ``(h1, h2)``."""
+    DESTROY = "pysdr_chan_destroy"
 
-    def __init__(self, fs, M, D=None, h=None, channels=None, device=0, max_in=1 << 22):
-        self.fs, self.M = float(fs), int(M)
-        self.D = self.M // 2 if D is None else int(D)
-        h = channelizer_taps(self.M) if h is None else np.asarray(h, np.float64)
-        self.k_first, self.nk = (0, self.M) if channels is None else (int(channels[0]), int(channels[1]))
-        self.device, self.max_in = int(device), int(max_in)
-        self.max_taps = max(len(h), 8 * self.M)                      # what a later set_taps may bring
-        self._L = _lib.lib()
-        self._h = None
-        plan(self.M, self.D, len(h), self.k_first, self.nk)           # a bad shape fails here, with or without a device
+    def _start(self, create, args, taps):
+        """once the kind has its shape and has planned it: the C object, its taps, the raster of its rows"""
         _lib.require_gpu()
-        hd = C.c_void_p()
-        check(self._L.pysdr_chan_create(self.device, self.M, self.D, self.k_first, self.nk, self.max_taps, self.max_in,
-                                        C.byref(hd)), "pysdr_chan_create")
-        self._h = hd
-        self.set_taps(h)
+        self._create(create, *args)
+        self.set_taps(*taps)
         self.fs_out = self.fs / self.D
         k = (self.k_first + np.arange(self.nk)) % self.M
         self.freqs = np.where(k >= (self.M + 1) // 2, k - self.M, k) * (self.fs / self.M)
         self.n_in = 0
-
-    def close(self):
-        if self._h:
-            self._L.pysdr_chan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_taps(self, h):
-        """New prototype from the next call on, for the whole window of that call's outputs (``rx.dec.h``)."""
-        h = np.ascontiguousarray(h, np.float64)
-        check(self._L.pysdr_chan_set_taps(self._h, _lib.as_pd(h), len(h)), "pysdr_chan_set_taps")
-        self.h = h
 
     def reset(self):
         check(self._L.pysdr_chan_reset(self._h), "pysdr_chan_reset")
@@ -105,3 +74,27 @@ class Channelizer:
 
     def sync(self):
         check(self._L.pysdr_chan_sync(self._h), "pysdr_chan_sync")
+
+
+class Channelizer(ChannelizerCore):
+    """``channels``: None = all M rows, or ``(k_first, nk)``: the circular range of channels k_first, k_first + 1, ...
+    (mod M).  Row a of every output is channel ``(k_first + a) % M`` at ``freqs[a]`` Hz (signed)."""
+
+    def __init__(self, fs, M, D=None, h=None, channels=None, device=0, max_in=1 << 22):
+        self.fs, self.M = float(fs), int(M)
+        self.D = self.M // 2 if D is None else int(D)
+        h = channelizer_taps(self.M) if h is None else np.asarray(h, np.float64)
+        self.k_first, self.nk = (0, self.M) if channels is None else (int(channels[0]), int(channels[1]))
+        self.device, self.max_in = int(device), int(max_in)
+        self.max_taps = max(len(h), 8 * self.M)                      # what a later set_taps may bring
+        plan(self.M, self.D, len(h), self.k_first, self.nk)           # a bad shape fails here, with or without a device
+        self._start("pysdr_chan_create", (self.device, self.M, self.D, self.k_first, self.nk, self.max_taps, self.max_in), (h,))
+
+    run_in_taps = property(lambda self: len(self.h), doc="the prototype's length in input samples")
+    prototypes = property(lambda self: self.h)
+
+    def set_taps(self, h):
+        """New prototype from the next call on, for the whole window of that call's outputs (``rx.dec.h``)."""
+        h = np.ascontiguousarray(h, np.float64)
+        check(self._L.pysdr_chan_set_taps(self._h, _lib.as_pd(h), len(h)), "pysdr_chan_set_taps")
+        self.h = h

@@ -5,13 +5,13 @@ hold for the whole bank; they are derived here, once, and handed to the library 
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
 from . import _lib
-from ._lib import CwCfg, check
+from ._lib import CwCfg
 from .channelizer import Channelizer
+from .skimmer import DecoderBank, Skimmer
 
 WORD_SPACE = 256
 STATE_INTS = ("key", "run", "dot", "last", "code", "nel", "sp", "seen")
@@ -77,9 +77,7 @@ def cfg_dict(cfg):
 def plan(nk, max_out, cfg):
     """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
     samples, event cap per channel and call, workgroups.  Raises PysdrError outside the rules."""
-    out = (C.c_int32 * 8)()
-    check(_lib.lib().pysdr_cw_plan(int(nk), int(max_out), C.byref(cfg) if cfg is not None else None, out), "pysdr_cw_plan")
-    v = list(out)
+    v = _lib.plan_call("pysdr_cw_plan", 8, int(nk), int(max_out), C.byref(cfg) if cfg is not None else None)
     return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5]}
 
 
@@ -121,88 +119,24 @@ def morse_keying(text, wpm, fs):
     return k
 
 
-class CW_Decoders:
+class CW_Decoders(DecoderBank):
     """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
+    KIND, DESTROY = "cw", "pysdr_cw_destroy"
 
     def __init__(self, chan, wpm0=20, max_out=1024, cfg=None):
-        self._L = _lib.lib()
-        self._h = None
-        self.chan = chan
-        self.nk, self.D, self.fs_out = chan.nk, chan.D, chan.fs_out
-        self.max_out = int(max_out)
-        run_in = chan.run_in_taps if hasattr(chan, "run_in_taps") else len(chan.h)
-        self.cfg = params(self.fs_out, wpm0, settle_samples(run_in, self.D, self.fs_out)) if cfg is None else cfg
+        super().__init__(chan, max_out)
+        self.cfg = params(self.fs_out, wpm0, settle_samples(chan.run_in_taps, self.D, self.fs_out)) if cfg is None else cfg
         self.plan = plan(self.nk, self.max_out, self.cfg)               # a bad shape fails here
-        self.cap = self.plan["cap"]
-        hd = C.c_void_p()
-        check(self._L.pysdr_cw_create(chan._h, C.byref(self.cfg), self.max_out, C.byref(hd)), "pysdr_cw_create")
-        self._h = hd
-        chan.n_in = 0
-        self._counts = np.zeros(self.nk, np.int32)
-        self.last_n_out = 0
-
-    def close(self):
-        if self._h:
-            self._L.pysdr_cw_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        check(self._L.pysdr_cw_reset(self._h), "pysdr_cw_reset")
-        self.chan.n_in = 0
-        self.last_n_out = 0
-
-    def sync(self):
-        check(self._L.pysdr_cw_sync(self._h), "pysdr_cw_sync")
-
-    def max_samples(self):
-        """the longest next call: it completes at most max_out outputs and holds at most max_in samples"""
-        return min(self.chan.max_in, (-self.chan.n_in) % self.D + self.max_out * self.D)
-
-    def fetch(self, rows):
-        """The last call's event slots [len(rows)][cap] of the named rows (int32 words; only the first counts[row] of a
-        row are events)."""
-        rows = np.ascontiguousarray(rows, np.int32)
-        ev = np.zeros((len(rows), self.cap), np.int32)
-        check(self._L.pysdr_cw_fetch(self._h, _lib.as_pi(rows), len(rows), ev.ctypes.data_as(C.POINTER(C.c_int32)), self.cap),
-              "pysdr_cw_fetch")
-        return ev
+        self._open(self.nk, C.byref(self.cfg))
 
     def decode_raw(self, x, n=None, on_device=False, events="all"):
         """One call of the C ABI: host samples (complex64 [n]) or a device pointer.  -> dict of n_out, m0 (the absolute
         index of the call's first output), counts [nk] and events: every row's slots [nk][cap] ("all"), a dict
         {row: words} of the rows that have events, downloaded after the counts ("rows"), or nothing (None: counts is None
         too, everything stays on the device and the call only queues work when the input is on the device)."""
-        if self._h is None:
-            raise _lib.PysdrError("CW_Decoders is closed")
-        if on_device:
-            ptr, n = C.c_void_p(int(x)), int(n)
-        else:
-            x = np.ascontiguousarray(x, np.complex64)
-            ptr, n = C.c_void_p(x.ctypes.data), len(x)
-        m0 = -(-self.chan.n_in // self.D)
-        n_out = C.c_int(0)
-        counts = ev = None
-        pc = pe = None
-        if events is not None:
-            counts = self._counts
-            pc = counts.ctypes.data_as(C.POINTER(C.c_int32))
-        if events == "all":
-            ev = np.zeros((self.nk, self.cap), np.int32)
-            pe = ev.ctypes.data_as(C.POINTER(C.c_int32))
-        check(self._L.pysdr_cw_process(self._h, ptr, n, 1 if on_device else 0, C.byref(n_out), pc, pe, self.cap),
-              "pysdr_cw_process")
-        self.chan.n_in += n
-        self.last_n_out = n_out.value
-        out = dict(n_out=n_out.value, m0=m0, counts=None if counts is None else counts.copy(), events=ev)
+        out = self._decode(x, n, on_device, events)
         if events == "rows":
+            counts = out["counts"]
             rows = np.flatnonzero(counts)
             words = self.fetch(rows) if len(rows) else np.zeros((0, self.cap), np.int32)
             out["events"] = {int(r): words[i, :counts[r]].copy() for i, r in enumerate(rows)}
@@ -212,19 +146,17 @@ class CW_Decoders:
         """dict of float32 [nk] s, pk, nf and int32 [nk] key, run, dot, last, code, nel, sp, seen"""
         out = {k: np.empty(self.nk, np.float32) for k in ("s", "pk", "nf")}
         ints = np.empty((self.nk, 8), np.int32)
-        check(self._L.pysdr_cw_state(self._h, _lib.as_pf(out["s"]), _lib.as_pf(out["pk"]), _lib.as_pf(out["nf"]),
-                                     ints.ctypes.data_as(C.POINTER(C.c_int32))), "pysdr_cw_state")
+        self._call("state", _lib.as_pf(out["s"]), _lib.as_pf(out["pk"]), _lib.as_pf(out["nf"]), ints.ctypes.data_as(C.POINTER(C.c_int32)))
         for i, k in enumerate(STATE_INTS):
             out[k] = ints[:, i].copy()
         return out
 
 
-class CW_Skimmer:
+class CW_Skimmer(Skimmer):
     """Wideband IQ at ``fs`` -> the channelizer's raster of M channels (row a at ``freqs[a]`` Hz, ``fs / D`` samples per
     second each) -> one Morse decoder per row, without taking the rows off the device."""
 
     def __init__(self, fs, M=None, D=None, h=None, channels=None, wpm0=20, device=0, max_in=1 << 22, max_out=1024, chan=None):
-        self.chan = self.dec = None
         if chan is None:
             nk = int(M) if channels is None else int(channels[1])
             D_ = int(M) // 2 if D is None else int(D)
@@ -237,45 +169,14 @@ class CW_Skimmer:
         self.freqs, self.fs_out = self.chan.freqs, self.chan.fs_out
         self.text = {a: "" for a in range(self.nk)}
 
-    def close(self):
-        if self.dec is not None:
-            self.dec.close()
-        if self.chan is not None:
-            self.chan.close()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self):
         self.dec.reset()
         self.text = {a: "" for a in range(self.nk)}
 
-    def sync(self):
-        self.dec.sync()
-
-    def push(self, x):
-        """complex64 [n] -> the events (m, row, text) of the outputs this input completes, sorted by (m, row); m is the
-        absolute output index since create / reset.  ``text`` gains them.  The counts come off the device first, then
-        only the rows that have events."""
-        x = np.ascontiguousarray(x, np.complex64)
-        ev, i = [], 0
-        while i < len(x):
-            n = min(len(x) - i, self.dec.max_samples())
-            r = self.dec.decode_raw(x[i:i + n], events="rows")
-            i += n
-            for row, words in r["events"].items():
-                for w in words:
-                    j, c = unpack(w)
-                    ev.append((r["m0"] + j, row, code_text(c)))
-        ev.sort(key=lambda e: (e[0], e[1]))
-        for _, row, ch in ev:
-            self.text[row] += ch
-        return ev
+    def _events(self, x):
+        """one call: the counts come off the device first, then only the rows that have events"""
+        r = self.dec.decode_raw(x, events="rows")
+        return [(r["m0"] + j, row, code_text(c)) for row, words in r["events"].items() for j, c in map(unpack, words)]
 
     def state(self):
         """The decoders' state: the raw fields of ``CW_Decoders.state`` plus wpm = 19.2 fs_out / dot, snr_db =

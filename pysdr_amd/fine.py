@@ -2,19 +2,17 @@
 kernel ``fine.hip``, host half ``api_fine.hip``).  A first-stage ``Channelizer`` (M1, D1) cuts the band into coarse rows;
 a second, batched stage runs an M2-channel channelizer on every coarse row that is needed, on the device and in the same
 stream, and keeps the ``Q = M2 D1 / M1`` channels inside the row's own spacing.  The kept channels of all coarse rows form
-one raster of ``Mf = M1 Q`` fine channels ``fs / Mf`` apart at ``fs / (D1 D2)`` samples per second.  The object has the
-attributes and methods of ``Channelizer`` that its users and borrowers touch, so ``CW_Decoders``, ``PSK_Decoders`` and the
-bank's C object run on it unchanged."""
+one raster of ``Mf = M1 Q`` fine channels ``fs / Mf`` apart at ``fs / (D1 D2)`` samples per second.  Everything but the shape,
+the create call and the taps is ``channelizer.ChannelizerCore``, which is also all that ``CW_Decoders``, ``PSK_Decoders`` and
+the bank's C object know of a channelizer, so they run on this one unchanged."""
 from __future__ import annotations
-
-import ctypes as C
-import sys
 
 import numpy as np
 from scipy.signal import firwin
 
 from . import _lib
 from ._lib import check
+from .channelizer import ChannelizerCore
 from .design import channelizer_taps
 
 NG_MAX = 1 << 16
@@ -30,9 +28,7 @@ def plan(M1, D1, M2, D2, ntaps1=None, ntaps2=None, g_first=0, ng=None):
     if ng is None:
         Mf = M1 * (M2 * D1 // M1) if M1 > 0 and D1 > 0 else 0
         ng = max(1, min(Mf, NG_MAX))
-    out = (C.c_int32 * 16)()
-    check(_lib.lib().pysdr_chan_fine_plan(M1, D1, M2, D2, n1, n2, int(g_first), int(ng), out), "pysdr_chan_fine_plan")
-    v = list(out)
+    v = _lib.plan_call("pysdr_chan_fine_plan", 16, M1, D1, M2, D2, n1, n2, int(g_first), int(ng))
     return {"Q": v[0], "Mf": v[1], "D": v[2], "C2": v[3], "k1_first": v[4], "nk1": v[5], "frames_per_wg": v[6], "lds_bytes": v[7],
             "history": v[8], "taps_per_branch": v[9], "radices": v[11:11 + v[10]]}
 
@@ -81,7 +77,7 @@ def channels_for(band, fs, M1, D1, M2):
     return lo % Mf, hi - lo + 1
 
 
-class FineChannelizer:
+class FineChannelizer(ChannelizerCore):
     """``channels``: None = all Mf rows, or ``(g_first, ng)``: the circular range of fine channels g_first, g_first + 1, ...
     (mod Mf).  Row a of every output is fine channel ``(g_first + a) % Mf`` at ``freqs[a]`` Hz (signed)."""
 
@@ -93,83 +89,21 @@ class FineChannelizer:
         h2 = channelizer_taps(self.M2) if h2 is None else np.asarray(h2, np.float64)
         self.device, self.max_in = int(device), int(max_in)
         self.max_taps1, self.max_taps2 = max(len(h1), 8 * self.M1), max(len(h2), 8 * self.M2)   # what a later set_taps may bring
-        self._L = _lib.lib()
-        self._h = None
         g_first, ng = (0, None) if channels is None else (int(channels[0]), int(channels[1]))
         p = plan(self.M1, self.D1, self.M2, self.D2, len(h1), len(h2), g_first, ng)   # a bad shape fails here, with or without a device
         self.Q, self.M, self.D = p["Q"], p["Mf"], p["D"]
         self.k_first, self.nk = g_first, self.M if ng is None else ng
         self.k1_first, self.nk1 = p["k1_first"], p["nk1"]
         self.frames_per_wg = p["frames_per_wg"]
-        _lib.require_gpu()
-        hd = C.c_void_p()
-        check(self._L.pysdr_chan_fine_create(self.device, self.M1, self.D1, self.M2, self.D2, self.k_first, self.nk, self.max_taps1,
-                                             self.max_taps2, self.max_in, C.byref(hd)), "pysdr_chan_fine_create")
-        self._h = hd
-        self.set_taps(h1, h2)
-        self.fs_out = self.fs / self.D
-        g = (self.k_first + np.arange(self.nk)) % self.M
-        self.freqs = np.where(g >= (self.M + 1) // 2, g - self.M, g) * (self.fs / self.M)
-        self.n_in = 0
+        self._start("pysdr_chan_fine_create", (self.device, self.M1, self.D1, self.M2, self.D2, self.k_first, self.nk, self.max_taps1,
+                                               self.max_taps2, self.max_in), (h1, h2))
 
-    @property
-    def run_in_taps(self):
-        """the equivalent prototype length in input samples"""
-        return len(self.h1) + self.D1 * (len(self.h2) - 1)
-
-    def close(self):
-        if self._h:
-            self._L.pysdr_chan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+    run_in_taps = property(lambda self: len(self.h1) + self.D1 * (len(self.h2) - 1),
+                           doc="the equivalent prototype length in input samples")
+    prototypes = property(lambda self: (self.h1, self.h2))
 
     def set_taps(self, h1, h2):
         """New prototypes from the next call on; each stage applies its own to the whole window of that call's outputs."""
         h1, h2 = np.ascontiguousarray(h1, np.float64), np.ascontiguousarray(h2, np.float64)
         check(self._L.pysdr_chan_fine_set_taps(self._h, _lib.as_pd(h1), len(h1), _lib.as_pd(h2), len(h2)), "pysdr_chan_fine_set_taps")
         self.h1, self.h2 = h1, h2
-
-    def reset(self):
-        check(self._L.pysdr_chan_reset(self._h), "pysdr_chan_reset")
-        self.n_in = 0
-
-    def n_out_for(self, n):
-        """Outputs the next call of n samples produces: those with s0 <= m D < s0 + n."""
-        return -(-(self.n_in + n) // self.D) - -(-self.n_in // self.D)
-
-    def push(self, x):
-        """complex64 [n] -> complex64 [nk, n_out]"""
-        x = np.ascontiguousarray(x, np.complex64)
-        parts = []
-        for i in range(0, max(len(x), 1), self.max_in):
-            xi = x[i:i + self.max_in]
-            cap = self.n_out_for(len(xi))
-            y = np.empty((self.nk, cap), np.complex64)
-            n_out = C.c_int(0)
-            check(self._L.pysdr_chan_process(self._h, C.c_void_p(xi.ctypes.data), len(xi), 0, C.c_void_p(y.ctypes.data),
-                                             max(cap, 1), 0, C.byref(n_out)), "pysdr_chan_process")
-            assert n_out.value == cap, (n_out.value, cap)
-            self.n_in += len(xi)
-            parts.append(y)
-        return parts[0] if len(parts) == 1 else np.concatenate(parts, axis=1)
-
-    def push_device(self, d_x, n, d_out, pitch, sync=True):
-        """Device pointers: n complex samples at d_x -> d_out[a * pitch + i]; returns n_out.  ``sync=False`` only queues
-        the work on the channelizer's stream (``sync()`` waits for it)."""
-        n_out = C.c_int(0)
-        check(self._L.pysdr_chan_process(self._h, C.c_void_p(d_x), int(n), 1, C.c_void_p(d_out), int(pitch), 1,
-                                         C.byref(n_out)), "pysdr_chan_process")
-        self.n_in += int(n)
-        if sync:
-            self.sync()
-        return n_out.value
-
-    def sync(self):
-        check(self._L.pysdr_chan_sync(self._h), "pysdr_chan_sync")

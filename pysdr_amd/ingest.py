@@ -7,7 +7,6 @@ results come back into pinned buffers the same way (``pysdr_ingest_*`` in the C 
 from __future__ import annotations
 
 import ctypes as C
-import sys
 
 import numpy as np
 
@@ -85,10 +84,4 @@ class IngestRing:
             if self in getattr(self.ctx, '_rings', []):
                 self.ctx._rings.remove(self)
 
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _lib.Handle.__del__            # the shared guard; the attributes stay ``h`` and ``L``

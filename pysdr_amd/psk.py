@@ -8,15 +8,15 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-import sys
 
 import numpy as np
 from scipy.signal import firwin
 
 from . import _lib
 from . import channelizer as _chan
-from ._lib import PskCfg, check
+from ._lib import PskCfg
 from .channelizer import Channelizer
+from .skimmer import DecoderBank, Skimmer
 
 STATE_FLOATS = ("qn", "qd", "cr", "ci")
 STATE_INTS = ("pt", "cnt", "sh", "open", "seen")
@@ -135,10 +135,7 @@ def cfg_dict(cfg):
 def plan(nk, S, max_out, cfg):
     """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
     samples, event cap per decoder and call, workgroups, decoders per row.  Raises PysdrError outside the rules."""
-    out = (C.c_int32 * 8)()
-    check(_lib.lib().pysdr_psk_plan(int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None, out),
-          "pysdr_psk_plan")
-    v = list(out)
+    v = _lib.plan_call("pysdr_psk_plan", 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
     return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6]}
 
 
@@ -167,102 +164,36 @@ def owners(qn, is_open, circular, prev=None, keep=KEEP):
     return own
 
 
-class PSK_Decoders:
+class PSK_Decoders(DecoderBank):
     """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
+    KIND, DESTROY = "psk", "pysdr_psk_destroy"
 
     def __init__(self, chan, S, max_out=256, cfg=None):
-        self._L = _lib.lib()
-        self._h = None
-        self.chan = chan
+        super().__init__(chan, max_out)
         self.S, self.nsub = int(S), 4 * int(S)
-        self.nk, self.D, self.fs_out = chan.nk, chan.D, chan.fs_out
         self.nfine = self.nk * self.nsub
-        self.max_out = int(max_out)
         self.cfg = params() if cfg is None else cfg
         self.plan = plan(self.nk, self.S, self.max_out, self.cfg)         # a bad shape fails here
-        self.cap = self.plan["cap"]
         self.tw, self.g = tables(self.S)
-        hd = C.c_void_p()
-        check(self._L.pysdr_psk_create(chan._h, self.S, C.byref(self.cfg), _lib.as_pf(self.tw), _lib.as_pf(self.g), self.max_out,
-                                       C.byref(hd)), "pysdr_psk_create")
-        self._h = hd
-        chan.n_in = 0
-        self._counts = np.zeros(self.nfine, np.int32)
-        self.last_n_out = 0
-
-    def close(self):
-        if self._h:
-            self._L.pysdr_psk_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def reset(self):
-        check(self._L.pysdr_psk_reset(self._h), "pysdr_psk_reset")
-        self.chan.n_in = 0
-        self.last_n_out = 0
-
-    def sync(self):
-        check(self._L.pysdr_psk_sync(self._h), "pysdr_psk_sync")
-
-    def max_samples(self):
-        """the longest next call: it completes at most max_out outputs and holds at most max_in samples"""
-        return min(self.chan.max_in, (-self.chan.n_in) % self.D + self.max_out * self.D)
-
-    def fetch(self, rows):
-        """The last call's event slots [len(rows)][cap] of the named fine rows (int32 words; only the first counts[F] of
-        a row are events)."""
-        rows = np.ascontiguousarray(rows, np.int32)
-        ev = np.zeros((len(rows), self.cap), np.int32)
-        check(self._L.pysdr_psk_fetch(self._h, _lib.as_pi(rows), len(rows), ev.ctypes.data_as(C.POINTER(C.c_int32)), self.cap),
-              "pysdr_psk_fetch")
-        return ev
+        self._open(self.nfine, self.S, C.byref(self.cfg), _lib.as_pf(self.tw), _lib.as_pf(self.g))
 
     def decode_raw(self, x, n=None, on_device=False, events="all", squelch=False):
         """One call of the C ABI: host samples (complex64 [n]) or a device pointer.  -> dict of n_out, m0 (the absolute
         index of the call's first output), counts [nfine] and events: every fine row's slots [nfine][cap] ("all") or
         nothing ("counts": the counts alone; None: counts is None too, everything stays on the device and the call only
         queues work when the input is on the device).  ``squelch``: the end state's qn and open [nfine] as well."""
-        if self._h is None:
-            raise _lib.PysdrError("PSK_Decoders is closed")
-        if on_device:
-            ptr, n = C.c_void_p(int(x)), int(n)
-        else:
-            x = np.ascontiguousarray(x, np.complex64)
-            ptr, n = C.c_void_p(x.ctypes.data), len(x)
-        m0 = -(-self.chan.n_in // self.D)
-        n_out = C.c_int(0)
-        pi32 = C.POINTER(C.c_int32)
-        counts = ev = qn = is_open = None
-        pc = pe = pq = po = None
-        if events is not None:
-            counts = self._counts
-            pc = counts.ctypes.data_as(pi32)
-        if events == "all":
-            ev = np.zeros((self.nfine, self.cap), np.int32)
-            pe = ev.ctypes.data_as(pi32)
+        qn = is_open = pq = po = None
         if squelch:
             qn, is_open = np.zeros(self.nfine, np.float32), np.zeros(self.nfine, np.int32)
-            pq, po = _lib.as_pf(qn), is_open.ctypes.data_as(pi32)
-        check(self._L.pysdr_psk_process(self._h, ptr, n, 1 if on_device else 0, C.byref(n_out), pc, pe, self.cap, pq, po),
-              "pysdr_psk_process")
-        self.chan.n_in += n
-        self.last_n_out = n_out.value
-        return dict(n_out=n_out.value, m0=m0, counts=None if counts is None else counts.copy(), events=ev, qn=qn, open=is_open)
+            pq, po = _lib.as_pf(qn), is_open.ctypes.data_as(C.POINTER(C.c_int32))
+        return dict(self._decode(x, n, on_device, events, pq, po), qn=qn, open=is_open)
 
     def state(self):
         """dict of float32 e [nfine][S], qn, qd, cr, ci [nfine] and int32 pt, cnt, sh, open, seen [nfine]"""
         e = np.empty((self.S, self.nfine), np.float32)
         f = np.empty((4, self.nfine), np.float32)
         ints = np.empty((5, self.nfine), np.int32)
-        check(self._L.pysdr_psk_state(self._h, _lib.as_pf(e), _lib.as_pf(f), ints.ctypes.data_as(C.POINTER(C.c_int32))),
-              "pysdr_psk_state")
+        self._call("state", _lib.as_pf(e), _lib.as_pf(f), ints.ctypes.data_as(C.POINTER(C.c_int32)))
         out = {"e": np.ascontiguousarray(e.T)}
         for i, k in enumerate(STATE_FLOATS):
             out[k] = f[i].copy()
@@ -271,13 +202,12 @@ class PSK_Decoders:
         return out
 
 
-class PSK_Skimmer:
+class PSK_Skimmer(Skimmer):
     """Wideband IQ at ``fs`` -> a channelizer of M = 4 D rows S baud / 4 apart at S baud samples per second -> NSUB = 4 S
     decoders inside every row, fine row F at ``freqs_fine[F]`` Hz (signed) -> the text of the stations, each on the fine
     row that owns it."""
 
     def __init__(self, fs, baud=31.25, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None):
-        self.chan = self.dec = None
         self.fs, self.baud = float(fs), float(baud)
         if chan is None:
             self.S, self.D, self.M = shape(fs, baud)
@@ -295,7 +225,7 @@ class PSK_Skimmer:
                 raise ValueError(f"PSK_Skimmer: the channelizer's rows (fs {chan.fs}, fs_out {chan.fs_out}, M / D = {chan.M / chan.D}) "
                                  f"are not at 8 or 12 samples per symbol of {baud} baud with M / D = 4 at fs = {fs}")
             self.nsub = 4 * self.S
-            self.h = chan.h if hasattr(chan, "h") else (chan.h1, chan.h2)
+            self.h = chan.prototypes
         self.dec = PSK_Decoders(self.chan, self.S, max_out)
         self.nk, self.nfine, self.fs_out = self.chan.nk, self.dec.nfine, self.chan.fs_out
         self.freqs = self.chan.freqs
@@ -305,54 +235,23 @@ class PSK_Skimmer:
         self.text = collections.defaultdict(str)
         self.owner = np.zeros(self.nfine, bool)                          # of the last call that completed an output
 
-    def close(self):
-        if self.dec is not None:
-            self.dec.close()
-        if self.chan is not None:
-            self.chan.close()
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self):
         self.dec.reset()
         self.text = collections.defaultdict(str)
         self.owner[:] = False
 
-    def sync(self):
-        self.dec.sync()
-
-    def push(self, x):
-        """complex64 [n] -> the events (m, F, text) of the outputs this input completes, owners only, sorted by (m, F); m
-        is the absolute output index since create / reset.  ``text[F]`` gains them.  Per call the counts and the squelch
-        state come off the device first, then only the owners that have events.  Ownership is decided per call, on the
-        call's end state and the last call's owners."""
-        x = np.ascontiguousarray(x, np.complex64)
-        ev, i = [], 0
-        while i < len(x):
-            n = min(len(x) - i, self.dec.max_samples())
-            r = self.dec.decode_raw(x[i:i + n], events="counts", squelch=True)
-            i += n
-            if r["n_out"] == 0:
-                continue
-            self.owner = owners(r["qn"], r["open"], self.circular, self.owner)
-            rows = np.flatnonzero(self.owner & (r["counts"] > 0))
-            if not len(rows):
-                continue
-            words = self.dec.fetch(rows)
-            for k, F in enumerate(rows):
-                for w in words[k, :r["counts"][F]]:
-                    j, c = unpack(w)
-                    ev.append((r["m0"] + j, int(F), code_text(c)))
-        ev.sort(key=lambda e: (e[0], e[1]))
-        for _, F, ch in ev:
-            self.text[F] += ch
-        return ev
+    def _events(self, x):
+        """one call: the counts and the squelch state come off the device first, then only the owners that have events;
+        ownership is decided per call, on the call's end state and the last call's owners"""
+        r = self.dec.decode_raw(x, events="counts", squelch=True)
+        if r["n_out"] == 0:
+            return []
+        self.owner = owners(r["qn"], r["open"], self.circular, self.owner)
+        rows = np.flatnonzero(self.owner & (r["counts"] > 0))
+        if not len(rows):
+            return []
+        words = self.dec.fetch(rows)
+        return [(r["m0"] + j, int(F), code_text(c)) for k, F in enumerate(rows) for j, c in map(unpack, words[k, :r["counts"][F]])]
 
     def state(self):
         """The decoders' state: the raw fields of ``PSK_Decoders.state`` plus coh = qn / qd (1 for a BPSK signal on tune, 0

@@ -13,7 +13,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import sys
 
 import numpy as np
 
@@ -40,7 +39,10 @@ class RTTY_Params:
         self.mark_bins = np.array(mark_bins)
 
 
-class RTTY_Filterbank:
+class RTTY_Filterbank(_lib.Handle):
+    DESTROY = "pysdr_spectrum_destroy"
+    _d_in = _d_out = None
+
     def __init__(self, FS_OUT, max_symbols=512, device=0, mark_bins=(559,)):
         _lib.require_gpu()
         self.RTTY = RTTY_Params(FS_OUT, mark_bins)
@@ -48,15 +50,11 @@ class RTTY_Filterbank:
         self.device = device
         self.max_symbols = int(max_symbols)
         self.window = np.kaiser(p.N, 8.6)
-        self._L = _lib.lib()
-        h = C.c_void_p()
         win = np.ascontiguousarray(self.window, np.float32)
         # the four quarter-symbol lines of a symbol start N/4 apart: when that is a whole number of
         # samples (48 kHz: N = 1056) all 4k lines of k symbols are ONE batch with hop N/4
         self._uniform = all(int(p.NSTART[i]) * 4 == i * p.N for i in range(4))
-        check(self._L.pysdr_spectrum_create(device, p.N, p.NFFT, 4 * self.max_symbols, _lib.as_pf(win),
-                                            C.byref(h)), "pysdr_spectrum_create")
-        self._h = h
+        self._create("pysdr_spectrum_create", device, p.N, p.NFFT, 4 * self.max_symbols, _lib.as_pf(win))
         self._d_in = C.c_void_p()
         self._d_out = C.c_void_p()
         check(self._L.pysdr_dev_alloc(device, (self.max_symbols + 1) * p.N * 8, C.byref(self._d_in)), "alloc")
@@ -64,20 +62,11 @@ class RTTY_Filterbank:
         self._fifo = np.zeros(0, np.complex64)
         self._prev = None
 
-    def close(self):
-        if self._h:
-            self._L.pysdr_spectrum_destroy(self._h)
-            self._L.pysdr_dev_free(self.device, self._d_in)
-            self._L.pysdr_dev_free(self.device, self._d_out)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _release(self):
+        for d in (self._d_in, self._d_out):                              # the two device buffers go after the spectrum object
+            if d:
+                self._L.pysdr_dev_free(self.device, d)
+                d.value = None
 
     def _staged(self, iq):
         """Append baseband IQ; for every batch of k symbols it completes, upload [prev, k symbols] to the
@@ -162,13 +151,14 @@ def code_text(code):
     return (FIGS if code >= 32 else LTRS)[code & 31]
 
 
-class RTTY_Decoders:
+class RTTY_Decoders(_lib.Handle):
     """The reference's RTTY decoders (``RTTY_Decoder``, ``rtty.py:431-701``) on every bin of a range, with its
     signal finder (``find_sigs``, ``:744-764``), driven as its executive drives them (``:847-853``).
     ``bins=None``: a decoder on every bin with a space bin, [0, NFFT - NBINS); otherwise the bins given (the
     decoders run on [min, max] and events are reported for the given ones).  ``find_bins`` is the reference's
     ``YLIM``: the finder scans the mark bins [lo, hi - NBINS).  Lines are numbered 1, 2, ... from construction
     or ``reset()``; characters are decided at lines n = 30 j."""
+    DESTROY = "pysdr_rtty_destroy"
 
     def __init__(self, FS_OUT, bins=None, find_bins=(800, 1250), device=0, max_lines=2048):
         _lib.require_gpu()
@@ -186,11 +176,7 @@ class RTTY_Decoders:
         self.find_lo, self.find_hi = int(find_bins[0]), int(find_bins[1]) - p.NBINS
         self.device = device
         self.max_lines = int(max_lines)
-        self._L = _lib.lib()
-        h = C.c_void_p()
-        check(self._L.pysdr_rtty_create(device, p.NFFT, p.NBINS, self.bin_lo, self.bin_hi, self.find_lo, self.find_hi,
-                                        self.max_lines, C.byref(h)), "pysdr_rtty_create")
-        self._h = h
+        self._create("pysdr_rtty_create", device, p.NFFT, p.NBINS, self.bin_lo, self.bin_hi, self.find_lo, self.find_hi, self.max_lines)
         self.nb = self.bin_hi - self.bin_lo
         nd = self.max_lines // p.M + 1
         self._codes = np.empty((nd, self.nb), np.int32)
@@ -208,25 +194,11 @@ class RTTY_Decoders:
         check(self._L.pysdr_rtty_reset(self._h), "pysdr_rtty_reset")
         self._reset_host()
 
-    def close(self):
-        if self._h:
-            self._L.pysdr_rtty_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        if sys is None or sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def decode_raw(self, lines, nlines, on_device, flipped, per_line=False):
         """One call of the C ABI on at most ``max_lines`` lines: host lines (float32 [nlines][NFFT]) or a device
         pointer.  -> dict of n (decision lines), codes / t / snr2 [decision][bin - bin_lo], ndet [nlines] and, with
         ``per_line``, isym / best [nlines][bins]."""
-        if self._h is None:
-            raise _lib.PysdrError("RTTY_Decoders is closed")
+        self._check_open()
         nlines = int(nlines)
         if on_device:
             ptr = C.c_void_p(int(lines))

@@ -14,7 +14,6 @@ chunk is uploaded and read once for every RX (the reference loops
 from __future__ import annotations
 
 import ctypes as C
-import sys
 import multiprocessing as mp
 import queue
 import threading
@@ -90,15 +89,7 @@ class _StreamContext:
             self.L.pysdr_destroy(self.h)
             self.h = None
 
-    def __del__(self):
-        # at interpreter shutdown the HIP runtime may already be torn down: leave the device
-        # memory to process exit rather than call into a dead runtime
-        if sys.is_finalizing():
-            return
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _lib.Handle.__del__            # the shared guard; the attributes stay ``h`` and ``L``, which multi.py and the rings read
 
     def add(self, rx, mode, lo_freq, h, af, bfo):
         irx = C.c_int(-1)
@@ -488,11 +479,12 @@ class Receiver:
 
 
 # ----------------------------------------------------------------------------------------
-class spectrum:
+class spectrum(_lib.Handle):
     """``dsp.spectrum(fs_kHz, chunk_size, NFFT, overlap, TAG=)`` (``Plotting.py:376``;
     ``gui.py:611-631`` pass fs in kHz).  ``periodogram(y, True)`` slides ``len(y)`` new
     samples into the ``chunk_size`` window, then window -> zero-pad -> FFT (rocFFT) ->
     ``10*log10(re^2+im^2)`` -> fftshift on the GPU (formula: ``rtty.py:839-841``)."""
+    DESTROY = "pysdr_spectrum_destroy"
 
     def __init__(self, fs, chunk_size, NFFT, overlap, TAG='', device=0):
         _lib.require_gpu()
@@ -507,22 +499,7 @@ class spectrum:
         self.frq = self.frq2.copy()
         self._buf = np.zeros(self.chunk_size, np.complex64)
         win = np.ascontiguousarray(design.psd_window(self.chunk_size), np.float32)
-        h = C.c_void_p()
-        check(_lib.lib().pysdr_spectrum_create(device, self.chunk_size, self.NFFT, 1,
-                                               _lib.as_pf(win), C.byref(h)), "pysdr_spectrum_create")
-        self._h = h
-
-    def __del__(self):
-        # at interpreter shutdown the HIP runtime may already be torn down: leave the device
-        # memory to process exit rather than call into a dead runtime
-        if sys.is_finalizing():
-            return
-        try:
-            if self._h:
-                _lib.lib().pysdr_spectrum_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._create("pysdr_spectrum_create", device, self.chunk_size, self.NFFT, 1, _lib.as_pf(win))
 
     def periodogram(self, y, db=True):
         y = np.asarray(y)

@@ -4,8 +4,6 @@
 from __future__ import annotations
 
 import ctypes as C
-import sys
-
 import math
 
 import numpy as np
@@ -14,28 +12,15 @@ from . import _lib
 from ._lib import check
 
 
-class Waterfall:
+class Waterfall(_lib.Handle):
+    DESTROY = "pysdr_waterfall_destroy"
+
     def __init__(self, nfft, ncols=100, device=0):
         _lib.require_gpu()
         self.nfft, self.ncols, self.device = int(nfft), int(ncols), device
         self.wf_cnt = 0                  # Plotting.py:386
         self.wf_fc = 0                   # Plotting.py:387
-        h = C.c_void_p()
-        check(_lib.lib().pysdr_waterfall_create(device, self.nfft, self.ncols, C.byref(h)),
-              "pysdr_waterfall_create")
-        self._h = h
-
-    def __del__(self):
-        # at interpreter shutdown the HIP runtime may already be torn down: leave the device
-        # memory to process exit rather than call into a dead runtime
-        if sys.is_finalizing():
-            return
-        try:
-            if self._h:
-                _lib.lib().pysdr_waterfall_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self._create("pysdr_waterfall_create", device, self.nfft, self.ncols)
 
     def push(self, PSD, flip=False):
         """``wf = concatenate((wf[:,1:], line), axis=1)`` (``Plotting.py:536-547``); ``flip`` is

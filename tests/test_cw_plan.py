@@ -1,16 +1,14 @@
 """The CW skimmer's plan (pysdr_cw_plan, include/pysdr_hip.h; pysdr_amd/csrc/cw_plan.h): what it refuses, the event cap,
 the event word -- through the library, which needs no device for this -- and the tile walk, the bank-conflict rule and the
-event slots in a stand-alone C++ program (tests/cw_plan/plan_main.cpp) built with AddressSanitizer + UBSan and run here.
+event slots in a stand-alone C++ program (tests/cw_plan/plan_main.cpp) built and run by tests/plan_program.py, under
+AddressSanitizer + UBSan where they are usable.
 CPU only; nothing that is loaded into Python runs under a sanitizer."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import plan_program
 
 
 def good():
@@ -88,20 +86,4 @@ def test_cap_follows_the_bound_and_the_word_round_trips():
 
 
 def test_tiles_cover_every_sample_once_and_the_slots_hold_the_cap(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "cw_plan")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function",
-           "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-I" + os.path.join(ROOT, "tests", "host_san", "fake_hip"), "-I" + os.path.join(ROOT, "pysdr_amd", "csrc"),
-           os.path.join(ROOT, "tests", "cw_plan", "plan_main.cpp"), "-o", exe]
-    p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    if p.returncode != 0 and ("cannot find -lasan" in p.stderr or "cannot find -lubsan" in p.stderr):
-        pytest.skip("sanitizer runtime not usable here: " + p.stderr[-200:])
-    assert p.returncode == 0, p.stderr[-3000:]
-    p = subprocess.run([exe], cwd=ROOT, capture_output=True, text=True, timeout=600,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
-    if p.returncode != 0 and "unexpected memory mapping" in p.stderr:
-        pytest.skip("sanitizer runtime not usable here: " + p.stderr[-200:])
-    assert p.returncode == 0 and "CW_PLAN_OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
-    print(p.stdout.strip())
+    plan_program.run("tests/cw_plan/plan_main.cpp", "CW_PLAN_OK", tmp_path)

@@ -1,17 +1,14 @@
 """The fine channelizer's plan (pysdr_chan_fine_plan, include/pysdr_hip.h; pysdr_amd/csrc/fine_plan.h): what it accepts and
 refuses and what it reports -- through the library, which needs no device for this -- and the rules, the channel map, the
 tiles, the tap reads and the roll of a stream of ragged calls against brute force in a stand-alone C++ program
-(tests/fine_plan/plan_main.cpp) built with AddressSanitizer + UBSan and run here.  The same program checks the pure half
+(tests/fine_plan/plan_main.cpp) built and run by tests/plan_program.py, under AddressSanitizer + UBSan where they are usable.  The same program checks the pure half
 of the FFT that both channelizer stages share (pysdr_amd/csrc/fft_plan.h): passes, digit reversal, multipliers, twiddles.  CPU only; nothing that is loaded into
 Python runs under a sanitizer."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import plan_program
 
 
 def call(lib, *a):
@@ -76,29 +73,5 @@ def test_plan_refuses_bad_shapes(hiplib):
 
 
 def test_rules_map_tiles_and_the_roll_against_brute_force(tmp_path):
-    """The program runs under AddressSanitizer + UBSan where their runtime is usable; where it is not (no libasan to link, or
-    a host whose memory layout the runtime refuses) the same program is built and run without them, and the output says
-    which: its own checks do not depend on the sanitizers."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    base = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-            "-I" + os.path.join(ROOT, "pysdr_amd", "csrc"), os.path.join(ROOT, "tests", "fine_plan", "plan_main.cpp")]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    ran = None
-    for name, flags in (("sanitized", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]), ("plain", [])):
-        exe = str(tmp_path / ("fine_plan_" + name))
-        p = subprocess.run(base + flags + ["-o", exe], cwd=ROOT, capture_output=True, text=True, timeout=600)
-        if p.returncode != 0 and flags and ("cannot find -lasan" in p.stderr or "cannot find -lubsan" in p.stderr):
-            print("sanitizer runtime not linkable here, running the plain build:", p.stderr[-200:])
-            continue
-        assert p.returncode == 0, p.stderr[-3000:]
-        p = subprocess.run([exe], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
-        if p.returncode != 0 and flags and "unexpected memory mapping" in p.stderr:
-            print("sanitizer runtime not usable here, running the plain build:", p.stderr[-200:])
-            continue
-        assert p.returncode == 0 and "FINE_PLAN_OK" in p.stdout, (name, p.stdout[-1500:], p.stderr[-3000:])
-        assert "35 FFT sizes" in p.stdout, p.stdout[-1500:]     # every 2^a 5^b in [16, 4096] went through the shared FFT plan's checks
-        ran = name
-        print(name + ":", p.stdout.strip())
-        break
-    assert ran is not None
+    out = plan_program.run("tests/fine_plan/plan_main.cpp", "FINE_PLAN_OK", tmp_path, includes=("pysdr_amd/csrc",))
+    assert "35 FFT sizes" in out, out[-1500:]     # every 2^a 5^b in [16, 4096] went through the shared FFT plan's checks

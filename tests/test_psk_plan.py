@@ -1,15 +1,13 @@
 """The PSK31 skimmer's plan (pysdr_psk_plan, include/pysdr_hip.h; pysdr_amd/csrc/psk_plan.h): what it refuses, the event
 cap, the event word -- through the library, which needs no device for this -- and the tile walk, the LDS layout and the
-event slots in a stand-alone C++ program (tests/psk_plan/plan_main.cpp) built with AddressSanitizer + UBSan and run here.
+event slots in a stand-alone C++ program (tests/psk_plan/plan_main.cpp) built and run by tests/plan_program.py, under
+AddressSanitizer + UBSan where they are usable.
 CPU only; nothing that is loaded into Python runs under a sanitizer."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import plan_program
 
 
 def good():
@@ -75,29 +73,5 @@ def test_plan_refuses_bad_shapes_and_settings(hiplib):
 
 
 def test_tiles_cover_every_sample_once_and_the_slots_hold_the_cap(tmp_path):
-    """The program runs under AddressSanitizer + UBSan where their runtime is usable; where it is not (no libasan to link, or
-    a host whose memory layout the runtime refuses) the same program is built and run without them: its own checks -- the
-    tile walk, the filter against the definition, the cap -- do not depend on the sanitizers."""
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    base = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-            "-ffp-contract=off", "-I" + os.path.join(ROOT, "tests", "host_san", "fake_hip"), "-I" + os.path.join(ROOT, "pysdr_amd", "csrc"),
-            os.path.join(ROOT, "tests", "psk_plan", "plan_main.cpp")]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    ran = None
-    for name, flags in (("sanitized", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]), ("plain", [])):
-        exe = str(tmp_path / ("psk_plan_" + name))
-        p = subprocess.run(base + flags + ["-o", exe], cwd=ROOT, capture_output=True, text=True, timeout=600)
-        if p.returncode != 0 and flags and ("cannot find -lasan" in p.stderr or "cannot find -lubsan" in p.stderr):
-            print("sanitizer runtime not linkable here, running the plain build:", p.stderr[-200:])
-            continue
-        assert p.returncode == 0, p.stderr[-3000:]
-        p = subprocess.run([exe], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
-        if p.returncode != 0 and flags and "unexpected memory mapping" in p.stderr:
-            print("sanitizer runtime not usable here, running the plain build:", p.stderr[-200:])
-            continue
-        assert p.returncode == 0 and "PSK_PLAN_OK" in p.stdout, (name, p.stdout[-1500:], p.stderr[-3000:])
-        ran = name
-        print(name + ":", p.stdout.strip())
-        break
-    assert ran is not None
+    """the tile walk, the filter against the definition, the cap"""
+    plan_program.run("tests/psk_plan/plan_main.cpp", "PSK_PLAN_OK", tmp_path, extra_flags=("-ffp-contract=off",))
