@@ -506,6 +506,56 @@ int  pysdr_psk_process(pysdr_psk* psk, const void* iq, int n, int on_device, int
 int  pysdr_psk_fetch(pysdr_psk* psk, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_psk_state(pysdr_psk* psk, float* e, float* f, int32_t* ints);
 
+/* ---- RTTY raster skimmer: a Baudot decoder on a fine raster inside every row of a channelizer (a
+ * build feature with a definition of its own: the reference's RTTY decoder, pysdr_rtty_*, works on dB lines of its own
+ * FFT and cannot run on channelizer rows) ---------------------------------------------------------------------------------
+ * 45.45 baud (500 / 11), 170 Hz shift, mark the upper tone.  The channelizer `ch` delivers rows at fs_out = S baud, S = 22
+ * or 33 samples per bit.  Inside every row a < nk a bank of NSUB = S decoders runs, decoder j centred (2 j - S + 1) baud / 8
+ * from the row's centre; fine row F = a S + j.  Each mixes the row down to its space tone, q = 2 j - S - 14, and its mark
+ * tone, q = 2 j - S + 16, in units of baud / 8 (table tw[NT][2] = (cos, -sin)(2 pi t / NT), NT = 8 S, indexed by (q k) mod
+ * NT of the absolute output index k), applies the one-bit window g[S] to both and compares the two powers at every output;
+ * a mark-to-space edge starts a character, whose start, five data and stop bits are sampled S outputs apart from half a
+ * bit after the edge; the contrast qn / qd of the two powers and the balance of the two tones' levels bm, bs gate the
+ * output (the squelch `open`).  All float arithmetic is float32 with every operation rounded on its own; DESIGN.md 3 item
+ * 21 is the normative text, step by step.  The settings hold for the whole bank: a_q, a_b in (0, 1], 0 < lo <= hi <= 1,
+ * 0 < bal <= 1, 0 < pmax <= 1e18 (all finite), 1 <= n0 <= 2^22 settling instants during which the squelch stays shut.  Any
+ * cut of a stream into calls gives the same events and the same state bits; a call that completes no output launches
+ * nothing and changes no state.
+ * pysdr_fsk_plan needs no device: PYSDR_ERR_ARG for S not 22 or 33, nk < 1, nk S > 2^18, max_out outside [1, 2^20] or a cfg
+ * outside these rules, else out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, NSUB, 0};
+ * the event cap max_out / (6 S + S / 2 + 1) + 1 is the most events one decoder can emit in a call of max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and g are host arrays of NT x 2 and S floats, copied.  reset also resets the channelizer.
+ * process: iq as in pysdr_chan_process (device pointer where on_device != 0); the decoders are queued behind the
+ * channelizer on the channelizer's stream.  counts[nk S] (events of every fine row in this call), events[F * ev_pitch + i],
+ * i < counts[F], and the end state's qn[nk S] and open[nk S] are host buffers or NULL: with NULL the results stay on the
+ * device (and a call with device input and no host buffer only queues work; pysdr_fsk_sync waits for it).
+ * An event word is (index of the output within the call) << 6 | code, code = the five data bits + 32 in figures shift.
+ * PYSDR_ERR_STATE: n > max_in of the channelizer, the call would complete more than max_out outputs, or ev_pitch smaller
+ * than the event cap; the stream does not advance.
+ * fetch: the last call's event slots of the named fine rows only, events[i * pitch + k] for rows[i], pitch >= the event
+ * cap; runs of consecutive rows go as one strided copy.  After a call that completed no output it copies nothing.
+ * state: f [4][nk S] = qn, qd, bm, bs and ints [8][nk S] = st, cnt, sh, nb, prev, fig, open, seen; NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_fsk_cfg {
+  float a_q, a_b;           /* smoothing constants of the contrast sums and of the two tones' levels */
+  float hi, lo;             /* squelch: opens at qn >= hi qd, shuts below lo qd */
+  float bal;                /* and only while the weaker tone's level is at least bal times the stronger's */
+  float pmax;               /* tone powers above this (or not finite) are blanked */
+  int32_t n0;               /* settling instants after create / reset */
+} pysdr_fsk_cfg;
+typedef struct pysdr_fsk pysdr_fsk;
+int  pysdr_fsk_plan(int nk, int S, int max_out, const pysdr_fsk_cfg* cfg, int32_t out[8]);
+int  pysdr_fsk_create(pysdr_chan* ch, int S, const pysdr_fsk_cfg* cfg, const float* tw, const float* g, int max_out,
+                      pysdr_fsk** out);
+void pysdr_fsk_destroy(pysdr_fsk* fsk);
+int  pysdr_fsk_reset(pysdr_fsk* fsk);
+int  pysdr_fsk_sync(pysdr_fsk* fsk);
+int  pysdr_fsk_process(pysdr_fsk* fsk, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch, float* qn, int32_t* open);
+int  pysdr_fsk_fetch(pysdr_fsk* fsk, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_fsk_state(pysdr_fsk* fsk, float* f, int32_t* ints);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

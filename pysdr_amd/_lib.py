@@ -52,7 +52,12 @@ class PskCfg(C.Structure):
                 ("pmax", C.c_float), ("n0", C.c_int32)]
 
 
-_vp, _i, _sz, _d, _f, _u32 = C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
+class FskCfg(C.Structure):
+    _fields_ = [("a_q", C.c_float), ("a_b", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("bal", C.c_float),
+                ("pmax", C.c_float), ("n0", C.c_int32)]
+
+
+_vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); every symbol include/pysdr_hip.h declares
@@ -162,6 +167,15 @@ PROTOTYPES = {
                                C.POINTER(C.c_int32)]),
     "pysdr_psk_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
     "pysdr_psk_state": (_i, [_vp, _pf, _pf, C.POINTER(C.c_int32)]),
+    "pysdr_fsk_plan": (_i, [_i, _i, _i, C.POINTER(FskCfg), C.POINTER(C.c_int32)]),
+    "pysdr_fsk_create": (_i, [_vp, _i, C.POINTER(FskCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_fsk_destroy": (None, [_vp]),
+    "pysdr_fsk_reset": (_i, [_vp]),
+    "pysdr_fsk_sync": (_i, [_vp]),
+    "pysdr_fsk_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong, _pf,
+                               C.POINTER(C.c_int32)]),
+    "pysdr_fsk_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
+    "pysdr_fsk_state": (_i, [_vp, _pf, C.POINTER(C.c_int32)]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -188,4 +188,8 @@ int launch_cw_decode(const CwArgs& a, hipStream_t st);
 struct PskArgs;
 int launch_psk_decode(int S, const PskArgs& a, hipStream_t st);
 
+// ---- RTTY raster skimmer (fsk.hip, host half api_fsk.hip; plan, steps and kernel arguments: fsk_plan.h) ----------------
+struct FskArgs;
+int launch_fsk_decode(int S, const FskArgs& a, hipStream_t st);
+
 }  // namespace pysdr

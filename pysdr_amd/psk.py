@@ -139,9 +139,9 @@ def plan(nk, S, max_out, cfg):
     return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6]}
 
 
-def owners(qn, is_open, circular, prev=None, keep=KEEP):
-    """The finder: fine row F owns its neighbourhood if it is open and beats every G with 0 < |F - G| <= 9 -- qn[F] >
-    qn[G], or equal and F < G.  The distance is circular where the rows cover the whole band, clipped otherwise.  The
+def owners(qn, is_open, circular, prev=None, keep=KEEP, reach=NEIGHBOURHOOD):
+    """The finder: fine row F owns its neighbourhood if it is open and beats every G with 0 < |F - G| <= ``reach`` (9) --
+    qn[F] > qn[G], or equal and F < G.  The distance is circular where the rows cover the whole band, clipped otherwise.  The
     owners of the last call (``prev``, bool [NF]) compete with ``keep`` times their qn (float32 product): a station that
     sits between two decoders stays with the one that had it.  -> bool [NF]"""
     qn = np.asarray(qn, np.float32)
@@ -150,7 +150,7 @@ def owners(qn, is_open, circular, prev=None, keep=KEEP):
     own = np.asarray(is_open).astype(bool).copy()
     NF = len(qn)
     F = np.arange(NF)
-    for d in range(1, min(NEIGHBOURHOOD, NF - 1 if circular else NF) + 1):
+    for d in range(1, min(int(reach), NF - 1 if circular else NF) + 1):
         for sgn in (-1, 1):
             G = F + sgn * d
             if circular:

@@ -1,6 +1,6 @@
-"""What the CW and the PSK31 skimmer share on the host: a bank of decoders on a borrowed channelizer, and the object that
-owns both and turns the bank's event words into text.  The event-word layouts, the settings and the tables stay with
-``cw.py`` and ``psk.py``."""
+"""What the CW, the PSK31 and the RTTY raster skimmer share on the host: a bank of decoders on a borrowed channelizer, and
+the object that owns both and turns the bank's event words into text.  The event-word layouts, the settings and the
+tables stay with ``cw.py``, ``psk.py`` and ``fsk.py``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -84,6 +84,7 @@ class Skimmer:
     """Owns a channelizer ``chan`` of either kind and the decoder bank ``dec`` on it; ``text[row]`` gains what ``push``
     returns.  A kind builds the two, and says in ``_events`` which of a call's events come off the device."""
     chan = dec = None
+    SILENT = ()                                                          # event texts that ``text`` does not gain
 
     def close(self):
         if self.dec is not None:
@@ -108,5 +109,6 @@ class Skimmer:
             i += n
         ev.sort(key=lambda e: (e[0], e[1]))
         for _, row, ch in ev:
-            self.text[row] += ch
+            if ch not in self.SILENT:
+                self.text[row] += ch
         return ev
