@@ -556,6 +556,51 @@ int  pysdr_fsk_process(pysdr_fsk* fsk, const void* iq, int n, int on_device, int
 int  pysdr_fsk_fetch(pysdr_fsk* fsk, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_fsk_state(pysdr_fsk* fsk, float* f, int32_t* ints);
 
+/* ---- FT8 skimmer: Costas sync and soft bits on a fine raster of the band --------------------
+ * The fourth client of a channelizer (either kind, M / D = 4, rows at S = 64 or 96 samples per symbol of 6.25 baud).
+ * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 14 bins baud / 2 apart whose powers are
+ * taken four times per symbol (a step: QS = S / 4 row outputs) into a device ring [nk][TR][NB].  Fine row F = a NSUB + j.
+ * Step t is complete with row output QS t + S - 1.  An event is a frame start t0 whose Costas score is a peak over four
+ * steps to either side, at least smin, with at least hmin of the 21 sync symbols strongest on their own tone; it is
+ * emitted at step t0 + 316.  Every float operation is float32 and rounded on its own; any cut of a stream into calls
+ * gives the same events, state bits and soft bits; a call that completes no output launches nothing and changes no
+ * state; one that completes outputs but no step only rolls the rows' history.
+ * pysdr_ft8_plan needs no device: PYSDR_ERR_ARG for S not 64 or 96, nk < 1, nk S / 2 > 2^18, max_out outside [1, 2^20], a
+ * ring above 2^30 bytes or a cfg outside its rules (smin >= 0, hmin in [0, 21], pmax in (0, 1e18], all finite), else out =
+ * {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, NSUB, TR}; cap = (max_out / QS + 1) / 5 + 1
+ * (two events of a decoder are at least 5 steps apart), TR = 321 + 2 (max_out / QS + 1) steps.
+ * create: tw [4 S][2] = (cos, -sin)(2 pi i / (4 S)).  The skimmer borrows ch, resets it, and ch must be fed only through it.
+ * process: as pysdr_fsk_process.  An event is two int32 words: (index within the call of the step at which it was
+ * emitted) << 5 | hits, then the score's float32 bits; t0 = steps[0] + index - 316.  events[F * ev_pitch + 2 i], i <
+ * counts[F]; ev_pitch counts words and is at least 2 cap.  steps (NULL or [2]) receives the steps complete before the
+ * call and the steps the call completed.  Refusals as pysdr_fsk_process (PYSDR_ERR_STATE: n > max_in, more than max_out
+ * outputs, ev_pitch too small; the stream does not advance).
+ * fetch: the last call's event words of the named fine rows, events[i * pitch + w], pitch >= 2 cap.
+ * llr: the 174 soft bits, in transmission order, of n <= 4096 candidates (F[i], t0[i]) to out[i * 174 + b]: for data
+ * symbol d (frame symbol 7 + d, or 43 + (d - 29) from d = 29 on) and the powers p[v] of its eight values v (sent on tone
+ * GRAY[v]), bit 4, 2, 1 of v in that order gives max over the values with the bit minus max over those without.  Before
+ * any launch and changing nothing it refuses every call in which some F is outside [0, nk NSUB) (PYSDR_ERR_ARG) or some
+ * frame is not yet complete (t0 + 312 >= steps done) or has left the ring (steps done - t0 > TR, or t0 < 0):
+ * PYSDR_ERR_STATE.  A frame is in the ring for at least one whole call of max_out outputs behind the call that emitted it.
+ * state: sc [9][nk NSUB] and hits [9][nk NSUB], the score and hit count of frame start t at index t mod 9; ring
+ * [nk][TR][NB], step t at index t mod TR; t_done, the steps complete.  NULL skips. */
+typedef struct pysdr_ft8_cfg {
+  float smin;               /* least score of an event */
+  int32_t hmin;             /* least hit count of an event, of 21 */
+  float pmax;               /* bin powers above this (or not finite) are blanked */
+} pysdr_ft8_cfg;
+typedef struct pysdr_ft8 pysdr_ft8;
+int  pysdr_ft8_plan(int nk, int S, int max_out, const pysdr_ft8_cfg* cfg, int32_t out[8]);
+int  pysdr_ft8_create(pysdr_chan* ch, int S, const pysdr_ft8_cfg* cfg, const float* tw, int max_out, pysdr_ft8** out);
+void pysdr_ft8_destroy(pysdr_ft8* ft8);
+int  pysdr_ft8_reset(pysdr_ft8* ft8);
+int  pysdr_ft8_sync(pysdr_ft8* ft8);
+int  pysdr_ft8_process(pysdr_ft8* ft8, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch, long long* steps);
+int  pysdr_ft8_fetch(pysdr_ft8* ft8, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_ft8_llr(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, float* out);
+int  pysdr_ft8_state(pysdr_ft8* ft8, float* sc, int32_t* hits, float* ring, long long* t_done);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -192,4 +192,10 @@ int launch_psk_decode(int S, const PskArgs& a, hipStream_t st);
 struct FskArgs;
 int launch_fsk_decode(int S, const FskArgs& a, hipStream_t st);
 
+// ---- FT8 skimmer (ft8.hip, host half api_ft8.hip; plan, steps and kernel arguments: ft8_plan.h) ------------------------
+struct Ft8Args;
+struct Ft8LlrArgs;
+int launch_ft8_steps(int S, const Ft8Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
+int launch_ft8_llr(const Ft8LlrArgs& a, hipStream_t st);
+
 }  // namespace pysdr

@@ -1,0 +1,334 @@
+"""FT8 skimmer: Costas sync and soft bits on a fine raster of the band (kernels ``ft8.hip``, host half
+``api_ft8.hip``).  8-FSK at 6.25 baud, tones 6.25 Hz apart, 79 symbols of which 21 are three Costas arrays.  A channelizer
+with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders run on the device, one
+every 3.125 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The device finds every
+frame by its sync score and hands out its 174 soft bits in transmission order, ready for any LDPC(174,91) decoder; LDPC,
+CRC and message text are not here.  The tables and settings are derived here, once, and handed to the library already
+derived."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from . import channelizer as _chan
+from . import psk as _psk
+from ._lib import Ft8Cfg
+from .channelizer import Channelizer
+from .skimmer import DecoderBank, Skimmer
+
+BAUD = 6.25
+COSTAS = (3, 1, 4, 0, 6, 5, 2)
+GRAY = (0, 1, 3, 2, 5, 6, 4, 7)                  # value v is sent on tone GRAY[v]
+SYMBOLS, DATA, BITS = 79, 58, 174
+SYNC_AT = (0, 36, 72)                            # first symbol of the three Costas arrays
+FRAME_SECONDS, SLOT_SECONDS, NOMINAL_START = SYMBOLS / BAUD, 15.0, 0.5
+STEPS_PER_SYMBOL = 4
+EMIT_LAG = 316                                   # an event t0 is emitted at step t0 + 316 ...
+HOLD = 321                                       # ... and released once step t0 + 320 is complete: every rival has arrived
+KEEP = 9
+SHAPES = (64, 96)                                # row samples per symbol
+LLR_MAX = 4096
+
+
+def shape(fs):
+    """-> (S, D, M): S = 64 row samples per symbol if fs / (64 baud) is an integer D and the channelizer accepts M = 4 D,
+    otherwise S = 96 likewise, otherwise ValueError."""
+    for S in SHAPES:
+        d = float(fs) / (S * BAUD)
+        D = int(round(d))
+        if D < 1 or abs(d - D) > 1e-9 * max(d, 1.0):
+            continue
+        try:
+            _chan.plan(4 * D, D, 16 * D)
+        except _lib.PysdrError:
+            continue
+        return S, D, 4 * D
+    raise ValueError(f"no FT8 raster for fs = {fs}: fs / 400 or fs / 600 must be an integer D with M = 4 D a channelizer size")
+
+
+def prototype(fs, M, S):
+    """The channelizer's prototype for the FT8 raster, ``psk.prototype``'s form: Kaiser(8.0) windowed sinc of 4 M taps cut
+    at fs_out / 2 = S baud / 2, sum 1.  A row's outer bin is (NB - 1) baud / 4 from its centre, a station up to a raster
+    step beyond it, plus its own baud-wide tone: the response is flat within 0.1 dB out to fp = (NB + 1) baud / 4 + baud
+    and at least 70 dB down from fs_out - fp on, where the aliases of that band begin."""
+    return _psk.prototype(fs, M, BAUD, S)
+
+
+def fine_channelizer(fs, band, device=0, max_in=1 << 22):
+    """A ``fine.FineChannelizer`` for ``FT8_Skimmer(fs, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4 apart whose
+    centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 64 where ``fine.shape`` finds a shape, else 96; M2 / D2 =
+    4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
+    from . import fine
+    err = None
+    for S in SHAPES:
+        try:
+            M1, D1, M2, D2 = fine.shape(fs, S * BAUD, 4)
+        except ValueError as e:
+            err = e
+            continue
+        h2 = prototype(float(fs) / D1, M2, S)
+        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
+                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
+    raise ValueError(f"no FT8 raster in two stages for fs = {fs}: {err}")
+
+
+def tables(S):
+    """-> tw float32 [4 S][2] = (cos, -sin)(2 pi i / NT): derived in float64, rounded once"""
+    t = 2 * np.pi * np.arange(4 * S) / (4 * S)
+    return np.ascontiguousarray(np.stack((np.cos(t), -np.sin(t)), axis=1), np.float32)
+
+
+def params(smin=3.0, hmin=13, pmax=1e18):
+    """The settings of DESIGN.md 3 item 22 as the ``_lib.Ft8Cfg`` the C ABI takes."""
+    return Ft8Cfg(smin=float(np.float32(smin)), hmin=int(hmin), pmax=float(np.float32(pmax)))
+
+
+def cfg_dict(cfg):
+    return {k: getattr(cfg, k) for k, _ in Ft8Cfg._fields_}
+
+
+def plan(nk, S, max_out, cfg):
+    """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
+    samples, event cap per decoder and call, workgroups, decoders per row, ring depth in steps.  Raises PysdrError
+    outside the rules."""
+    v = _lib.plan_call("pysdr_ft8_plan", 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
+    return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6], "tr": v[7]}
+
+
+def steps_done(n_out, S):
+    """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1"""
+    return (int(n_out) - S) // (S // 4) + 1 if n_out >= S else 0
+
+
+def unpack(words):
+    """the two event words -> (index within the call of the emitting step, hits, score)"""
+    w = int(words[0]) & 0xFFFFFFFF
+    return w >> 5, w & 31, float(np.array([int(words[1]) & 0xFFFFFFFF], np.uint32).view(np.float32)[0])
+
+
+def owners(events, reach_f=2, reach_t=4, nfine=None):
+    """The finder.  ``events``: sequence of (t0, F, score, ...).  An event owns itself unless another event within
+    ``reach_t`` steps and ``reach_f`` fine rows has a greater score; ties go to the lower (t0, F).  With ``nfine`` (the
+    raster covers the whole circle, nk == M) the distance in F is circular.  -> bool [len(events)]"""
+    n = len(events)
+    own = np.ones(n, bool)
+    if n < 2:
+        return own
+    t = np.array([e[0] for e in events], np.int64)
+    F = np.array([e[1] for e in events], np.int64)
+    s = np.array([e[2] for e in events], np.float64)
+    order = np.argsort(t, kind="stable")
+    lo = np.searchsorted(t[order], t - reach_t, "left")
+    hi = np.searchsorted(t[order], t + reach_t, "right")
+    for i in range(n):
+        for k in order[lo[i]:hi[i]]:
+            if k == i:
+                continue
+            d = abs(int(F[k] - F[i]))
+            if nfine is not None:
+                d = min(d, nfine - d)
+            if d > reach_f:
+                continue
+            if s[k] > s[i] or (s[k] == s[i] and (t[k], F[k]) < (t[i], F[i])):
+                own[i] = False
+                break
+    return own
+
+
+def unit_llr(llr):
+    """soft bits scaled to unit variance (what a decoder's channel model expects); zeros stay zeros"""
+    llr = np.asarray(llr, np.float32)
+    sd = float(np.std(llr.astype(np.float64)))
+    return llr if sd == 0 else (llr / np.float32(sd)).astype(np.float32)
+
+
+def hard_bits(llr):
+    return (np.asarray(llr) > 0).astype(np.uint8)
+
+
+def tones(bits):
+    """174 bits in transmission order -> the frame's 79 tones: Costas arrays at symbols 0, 36 and 72, 2 x 29 data symbols
+    of 3 bits, MSB first, Gray-mapped"""
+    bits = np.asarray(bits, np.int64).reshape(DATA, 3)
+    v = 4 * bits[:, 0] + 2 * bits[:, 1] + bits[:, 2]
+    g = np.array(GRAY)[v]
+    return np.concatenate((COSTAS, g[:29], COSTAS, g[29:], COSTAS)).astype(np.int64)
+
+
+def waveform(tones, f0, fs, gfsk=True, phase=0.0):
+    """complex128 frame of power 1 at ``fs``: tone 0 at ``f0`` Hz from the centre, continuous phase.  ``gfsk``: the
+    frequency pulse of a symbol is (erf(k (t + 1/2)) - erf(k (t - 1/2))) / 2, k = 2 pi sqrt(2 / ln 2), t in symbols from the
+    symbol's middle (BT = 2), the first and the last tone held beyond the frame; otherwise rectangular."""
+    from scipy.special import erf
+    tones = np.asarray(tones, np.float64)
+    sps = float(fs) / BAUD
+    n = int(round(len(tones) * sps))
+    t = (np.arange(n) + 0.5) / sps                                       # symbols
+    k0 = np.minimum(np.floor(t).astype(np.int64), len(tones) - 1)
+    if gfsk:
+        kk = 2 * np.pi * np.sqrt(2 / np.log(2))
+        ext = np.concatenate((tones[:1], tones, tones[-1:]))
+        dev = np.zeros(n)
+        for d in (-1, 0, 1):                                             # the pulse is 0 to 1e-50 beyond a symbol and a half
+            tau = t - (k0 + d) - 0.5
+            dev += ext[k0 + d + 1] * 0.5 * (erf(kk * (tau + 0.5)) - erf(kk * (tau - 0.5)))
+    else:
+        dev = tones[k0]
+    ph = np.cumsum(float(f0) + BAUD * dev)
+    return np.exp(1j * (2 * np.pi / float(fs) * ph + phase))
+
+
+class FT8_Decoders(DecoderBank):
+    """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
+    KIND, DESTROY = "ft8", "pysdr_ft8_destroy"
+
+    def __init__(self, chan, S, max_out=256, cfg=None):
+        super().__init__(chan, max_out)
+        self.S, self.nsub, self.nb, self.qs = int(S), int(S) // 2, int(S) // 2 + 14, int(S) // 4
+        self.nfine = self.nk * self.nsub
+        self.cfg = params() if cfg is None else cfg
+        self.plan = plan(self.nk, self.S, self.max_out, self.cfg)         # a bad shape fails here
+        self.tr = self.plan["tr"]
+        self.tw = tables(self.S)
+        self._open(self.nfine, self.S, C.byref(self.cfg), _lib.as_pf(self.tw))
+        self.slots = self.cap                                             # events per fine row and call
+        self.cap = 2 * self.slots                                         # int32 words per fine row: what fetch and process move
+        self.t_done = 0
+
+    def reset(self):
+        super().reset()
+        self.t_done = 0
+
+    def decode_raw(self, x, n=None, on_device=False, events="all"):
+        """One call of the C ABI: host samples (complex64 [n]) or a device pointer.  -> dict of n_out, m0, counts [nfine]
+        and events [nfine][2 slots] int32 words (``DecoderBank._decode``'s rules), and t_first, n_steps: the steps complete
+        before the call and those it completed.  An event's t0 is ``t_first + unpack(words)[0] - 316``."""
+        steps = (C.c_longlong * 2)()
+        r = self._decode(x, n, on_device, events, steps)
+        self.t_done = steps[0] + steps[1]
+        return dict(r, t_first=int(steps[0]), n_steps=int(steps[1]))
+
+    def events_of(self, r, rows=None, words=None):
+        """the events of a call as (t0, F, score, hits), from ``decode_raw``'s answer (events="all") or from fetched rows"""
+        if rows is None:
+            rows, words = np.flatnonzero(r["counts"]), r["events"][np.flatnonzero(r["counts"])]
+        out = []
+        for k, F in enumerate(rows):
+            for i in range(int(r["counts"][F])):
+                u, hits, score = unpack(words[k, 2 * i:2 * i + 2])
+                out.append((r["t_first"] + u - EMIT_LAG, int(F), score, hits))
+        return out
+
+    def llr(self, F, t0):
+        """float32 [n][174]: the soft bits of the candidates (F[i], t0[i]); PysdrError for a frame that is not complete yet
+        or has left the ring, or an F outside the raster"""
+        F = np.ascontiguousarray(F, np.int32)
+        t0 = np.ascontiguousarray(t0, np.int64)
+        out = np.zeros((len(F), BITS), np.float32)
+        for i in range(0, len(F), LLR_MAX):
+            f, t, o = F[i:i + LLR_MAX], t0[i:i + LLR_MAX], out[i:i + LLR_MAX]
+            self._call("llr", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), _lib.as_pf(o))
+        return out
+
+    def state(self, ring=False):
+        """dict of sc float32 [9][nfine] and hits int32 [9][nfine] (frame start t at index t mod 9), t_done, and with
+        ``ring`` the spectrum ring float32 [nk][TR][NB] (step t at index t mod TR)"""
+        sc = np.empty((KEEP, self.nfine), np.float32)
+        hits = np.empty((KEEP, self.nfine), np.int32)
+        rg = np.empty((self.nk, self.tr, self.nb), np.float32) if ring else None
+        done = C.c_longlong(0)
+        self._call("state", _lib.as_pf(sc), hits.ctypes.data_as(C.POINTER(C.c_int32)), None if rg is None else _lib.as_pf(rg), C.byref(done))
+        out = dict(sc=sc, hits=hits, t_done=int(done.value))
+        if ring:
+            out["ring"] = rg
+        return out
+
+
+class FT8_Skimmer(Skimmer):
+    """Wideband IQ at ``fs`` -> a channelizer of M = 4 D rows S baud / 4 apart at S baud samples per second -> NSUB = S / 2
+    sync decoders inside every row, fine row F with tone 0 at ``freqs_fine[F]`` Hz (signed) -> a record for every frame
+    found: ``t0`` (steps of a quarter symbol since create / reset), ``F``, ``freq``, ``time`` (seconds into the stream),
+    ``score``, ``hits`` and ``llr`` float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` and ``dt``."""
+
+    def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None):
+        self.fs, self.baud, self.t_first = float(fs), BAUD, t_first
+        if chan is None:
+            self.S, self.D, self.M = shape(fs)
+            nk = self.M if channels is None else int(channels[1])
+            plan(nk, self.S, max_out, params())                          # a bad shape fails here, with or without a device
+            self.h = prototype(fs, self.M, self.S)
+            self.chan = Channelizer(fs, self.M, self.D, self.h, channels, device, max_in)
+        else:
+            # a ready channelizer of either kind, adopted and owned: rows S baud / 4 apart at S baud samples per second
+            self.chan = chan
+            s = chan.fs_out / BAUD
+            self.S, self.D, self.M = int(round(s)), chan.D, chan.M
+            if abs(s - self.S) > 1e-9 * s or self.S not in SHAPES or chan.M != 4 * chan.D or float(fs) != chan.fs:
+                raise ValueError(f"FT8_Skimmer: the channelizer's rows (fs {chan.fs}, fs_out {chan.fs_out}, M / D = "
+                                 f"{chan.M / chan.D}) are not at 64 or 96 samples per symbol of 6.25 baud with M / D = 4 at fs = {fs}")
+            self.h = chan.prototypes
+        self.nsub, self.qs = self.S // 2, self.S // 4
+        self.dec = FT8_Decoders(self.chan, self.S, max_out)
+        self.nk, self.nfine, self.fs_out = self.chan.nk, self.dec.nfine, self.chan.fs_out
+        self.freqs = self.chan.freqs
+        q = 2 * np.arange(self.nsub) - (self.nsub + 13)
+        self.freqs_fine = (self.freqs[:, None] + q[None, :] * (BAUD / 4)).reshape(-1)
+        self.circular = self.nk == self.M
+        self.records = []
+        self._pending, self._recent = [], []
+
+    def reset(self):
+        self.dec.reset()
+        self.records = []
+        self._pending, self._recent = [], []
+
+    def _events(self, x):
+        """one call: the counts come off the device first, then only the rows that have events"""
+        r = self.dec.decode_raw(x, events="counts")
+        if r["n_out"] == 0 or r["n_steps"] == 0:
+            return []
+        rows = np.flatnonzero(r["counts"])
+        if not len(rows):
+            return []
+        return self.dec.events_of(r, rows, self.dec.fetch(rows))
+
+    def _release(self):
+        """the events whose rivals have all arrived: the owners among them, with their soft bits"""
+        done = self.dec.t_done
+        ripe = [e for e in self._pending if e[0] + HOLD <= done]
+        if not ripe:
+            return []
+        pool = self._recent + self._pending
+        own = owners(pool, nfine=self.nfine if self.circular else None)
+        out = [e for e, o in zip(pool, own) if o and e in ripe and e[0] + HOLD <= done]
+        first = min(e[0] for e in ripe)
+        self._recent = [e for e in self._recent if e[0] >= first - 16] + ripe
+        self._pending = [e for e in self._pending if e[0] + HOLD > done]
+        out.sort(key=lambda e: (e[0], e[1]))
+        if not out:
+            return []
+        llr = self.dec.llr([e[1] for e in out], [e[0] for e in out])
+        recs = []
+        for (t0, F, score, hits), soft in zip(out, llr):
+            rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits, llr=soft)
+            if self.t_first is not None:
+                T = float(self.t_first) + rec["time"]
+                rec["slot"] = int(np.floor(T / SLOT_SECONDS))
+                rec["dt"] = T - SLOT_SECONDS * rec["slot"] - NOMINAL_START
+            recs.append(rec)
+        return recs
+
+    def push(self, x):
+        """complex64 [n] -> the records of the frames whose step t0 + 320 this input completes, owners only, sorted by
+        (t0, F).  ``records`` gains them.  The input goes through in calls of at most ``dec.max_samples()``."""
+        x = np.ascontiguousarray(x, np.complex64)
+        out, i = [], 0
+        while i < len(x):
+            n = min(len(x) - i, self.dec.max_samples())
+            self._pending += self._events(x[i:i + n])
+            out += self._release()
+            i += n
+        self.records += out
+        return out
