@@ -241,7 +241,7 @@ struct pysdr_ctx {
 
 struct pysdr_spectrum {
   int device = 0, chunk = 0, nfft = 0, max_frames = 0;
-  int num_cus = 256;          // read once at create: the grid of the columns loop (host_plan.h plan_psd_cols)
+  int num_cus = 256;          // read once at create: the grids of the columns and rows loops (host_plan.h plan_psd_cols / plan_psd_rows)
   Stream stream;
   DevBuf<float> d_win;
   DevBuf<float2> d_work;      // [frames][nfft], grown on demand
@@ -1570,6 +1570,8 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
     // host_plan.h from the CU count read at create: 240 frames on 256 CUs = 60 rows of 4 frames each; a single frame = 16
     // workgroups of one iteration); PYSDR_PSD_PATH=unit / loop:<G> for A/B.  Same bits either way.  Measured (LABNOTES 15):
     // the columns kernel alone 134.3 -> 129.5 ns per frame, the C3 step 2.945 -> 2.893 ms (medians of 15 + 15 runs: 1.8 %).
+    // The rows pass is the same kind of loop on 8 x R resident workgroups (psd_rows_form / plan_psd_rows; LABNOTES 25);
+    // PYSDR_PSD_PATH=rows=unit / rows=loop:<R> for A/B, `unit` alone for the unit form of both passes.  Same bits either way.
     const int group = sp->tune.frames_per_group();
     if (sp->tune.nstreams > 1 && nframes > group) {
       // The groups are dealt out over `nstreams` streams, each with its own intermediate of group / nstreams
@@ -1600,7 +1602,7 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
         const int w = k % ns;
         rc = launch_psd64k(d_x + (size_t)f0 * hop, hop, nf, sp->d_win.get(), w ? sp->xwork[w].get() : sp->d_work.get(),
                            d_out + (size_t)f0 * sp->nfft, db, w ? sp->xstream[w].get() : sp->stream.get(),
-                           psd_form(sp->tune, nf, sp->num_cus));
+                           psd_launch_form(sp->tune, nf, sp->num_cus));
         if (rc) break;             // a failed launch still joins the side streams below: what was forked keeps writing
       }                            // d_out / xwork until it is done, and the caller reacts to the error right away
       for (int i = 1; i < ns; ++i) {
@@ -1616,7 +1618,7 @@ static int spectrum_run(pysdr_spectrum* sp, const float2* d_x, size_t hop, int n
     for (int f0 = 0; f0 < nframes; f0 += group) {
       const int nf = (nframes - f0 < group) ? nframes - f0 : group;
       rc = launch_psd64k(d_x + (size_t)f0 * hop, hop, nf, sp->d_win.get(), sp->d_work.get(),
-                         d_out + (size_t)f0 * sp->nfft, db, sp->stream, psd_form(sp->tune, nf, sp->num_cus));
+                         d_out + (size_t)f0 * sp->nfft, db, sp->stream, psd_launch_form(sp->tune, nf, sp->num_cus));
       if (rc) return rc;
     }
     PYSDR_HIP_CHECK(hipEventRecord(sp->ev[1], sp->stream));

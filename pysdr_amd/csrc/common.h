@@ -347,8 +347,9 @@ int launch_psd_post(const float2* work, int nframes, int nfft, int half, int db,
                     hipStream_t st);
 
 // fused 32768 -> 65536 PSD path (psdfft.hip): two kernels, `work` = nframes x 65536 complex
-// form (host_plan.h psd_form): 0 = float2 intermediate; >= 1 = the intermediate as block-scaled 24-bit fixed point (6 bytes
-// per complex), 1 with one columns unit per workgroup, 1 + G with the columns as a loop over frames on 16 x G workgroups
+// form (host_plan.h psd_launch_form): 0 = float2 intermediate; otherwise the intermediate as block-scaled 24-bit fixed point
+// (6 bytes per complex): in the low 16 bits 1 with one columns unit per workgroup, 1 + G with the columns as a loop over frames
+// on 16 x G workgroups; above them 0 with one rows unit per workgroup, R with the rows as a loop over frames on 8 x R
 int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work,
                   float* out, int db, hipStream_t st, int form);
 

@@ -124,6 +124,7 @@ struct Tuning {
 
 // Tuning values of a spectrum object (pysdr_spectrum_create)
 constexpr int kPsdColsMaxG = 4096;   // most grid rows PYSDR_PSD_PATH=loop:<G> can ask for (far above any residency)
+constexpr int kPsdRowsMaxR = 4096;   // the same for rows=loop:<R>
 struct SpectrumTuning {
   bool force_rocfft = false;  // PYSDR_PSD_ROCFFT: rocFFT even for the 32768 -> 65536 size
   int group = 0;              // frames per launch pair of the four-step path (PYSDR_PSD_GROUP); 0 = 480 with the 24-bit intermediate, 448 with float2
@@ -133,10 +134,13 @@ struct SpectrumTuning {
   // the rows of the other and the kernel boundaries of one stream hide behind the other's kernels
   static constexpr int kMaxStreams = 4;
   int nstreams = 2;
-  // PYSDR_PSD_PATH: the columns pass of the 24-bit path.  "unit": one unit (16 columns of one frame) per workgroup, grid
-  // 16 x frames; "loop:<G>": psd_cols_pk_kernel's loop over frames on 16 x G workgroups; unset: the loop with the G of
-  // plan_psd_cols.  (cols_g: -1 = default, 0 = unit, > 0 = forced G)
-  int cols_g = -1;
+  // PYSDR_PSD_PATH: the two passes of the 24-bit path, as comma-separated parts.  The columns part -- "unit": one unit (16
+  // columns of one frame) per workgroup, grid 16 x frames; "loop:<G>": psd_cols_pk_kernel's loop over frames on 16 x G
+  // workgroups; absent: the loop with the G of plan_psd_cols.  (cols_g: -1 = default, 0 = unit, > 0 = forced G)
+  // The rows part -- "rows=unit": one unit (32 rows of one frame) per workgroup, grid 8 x frames; "rows=loop:<R>":
+  // psd_rows_pk_kernel's loop on 8 x R workgroups; absent: the loop with the R of plan_psd_rows.  (rows_r: as cols_g)
+  // "unit" with no rows part is the unit form of BOTH passes: the pair of every round before the loops.
+  int cols_g = -1, rows_r = -1;
   int frames_per_group() const { return group > 0 ? group : (packed ? 480 : 448); }
 
   static SpectrumTuning from_env() {
@@ -146,8 +150,20 @@ struct SpectrumTuning {
     { const char* e = tuning_env("PYSDR_PSD_PACKED"); if (e && *e) t.packed = atoi(e) ? 1 : 0; }
     { const char* e = tuning_env("PYSDR_PSD_STREAMS"); if (e && atoi(e) >= 1 && atoi(e) <= kMaxStreams) t.nstreams = atoi(e); }
     { const char* e = tuning_env("PYSDR_PSD_PATH");
-      if (e && !strcmp(e, "unit")) t.cols_g = 0;
-      else if (e && !strncmp(e, "loop:", 5) && atoi(e + 5) > 0) t.cols_g = std::min(atoi(e + 5), kPsdColsMaxG); }
+      bool rows_given = false;
+      while (e && *e) {
+        const char* end = strchr(e, ',');
+        const size_t len = end ? (size_t)(end - e) : strlen(e);
+        const bool rows = len >= 5 && !strncmp(e, "rows=", 5);
+        const char* p = rows ? e + 5 : e;
+        const size_t plen = rows ? len - 5 : len;
+        int v = -1;                                                      // a malformed part leaves its default
+        if (plen == 4 && !strncmp(p, "unit", 4)) v = 0;
+        else if (plen > 5 && !strncmp(p, "loop:", 5) && atoi(p + 5) > 0) v = std::min(atoi(p + 5), rows ? kPsdRowsMaxR : kPsdColsMaxG);
+        if (rows) { t.rows_r = v; rows_given = true; } else t.cols_g = v;
+        e = end ? end + 1 : nullptr;
+      }
+      if (!rows_given && t.cols_g == 0) t.rows_r = 0; }
     return t;
   }
 };
@@ -168,10 +184,37 @@ inline int plan_psd_cols(int nframes, int num_cus, int forced) {
   const int rounds = (nframes + gmax - 1) / gmax;
   return (nframes + rounds - 1) / rounds;
 }
-// launch_psd64k's `form`: 0 = float2 intermediate, 1 = 24-bit with one columns unit per workgroup, 1 + G = 24-bit, loop on 16 x G
+// launch_psd64k's columns form: 0 = float2 intermediate, 1 = 24-bit with one columns unit per workgroup, 1 + G = 24-bit, loop on 16 x G
 inline int psd_form(const SpectrumTuning& t, int nframes, int num_cus) {
   if (!t.packed) return 0;
   return t.cols_g == 0 ? 1 : 1 + plan_psd_cols(nframes, num_cus, t.cols_g);
+}
+
+// The grid of the rows pass as a loop over frames (psdfft.hip psd_rows_pk_kernel): 8 row blocks x R workgroups, of which
+// workgroup (rb, r) walks over the frames r, r + R, r + 2 R, ... < nframes, the next one's intermediate and block scales in
+// flight while one is transformed.  The 72 KB of LDS of a workgroup allow kPsdRowsWgPerCu of them on a CU, and all 8 R are
+// resident at once; among the R with the fewest rounds the smallest, R <= nframes, `forced` (rows=loop:<R>) as it is --
+// plan_psd_cols' rules, and on every CU count the same rhythm (2 CUs / 8 = 4 CUs / 16: 240 frames on 256 CUs = R 60 x 4).
+constexpr int kPsdRowBlocks = 8, kPsdRowsWgPerCu = 2;
+inline int psd_rows_max_r(int num_cus) { return std::max(1, std::min(kPsdRowsMaxR, num_cus * kPsdRowsWgPerCu / kPsdRowBlocks)); }
+inline int plan_psd_rows(int nframes, int num_cus, int forced) {
+  if (nframes < 1) return 1;
+  if (forced > 0) return std::min(forced, nframes);
+  const int rmax = psd_rows_max_r(num_cus);
+  const int rounds = (nframes + rmax - 1) / rmax;
+  return (nframes + rounds - 1) / rounds;
+}
+// launch_psd64k's rows form (24-bit path only): 0 = one rows unit per workgroup, R = the loop on 8 x R
+inline int psd_rows_form(const SpectrumTuning& t, int nframes, int num_cus) {
+  if (!t.packed || t.rows_r == 0) return 0;
+  return plan_psd_rows(nframes, num_cus, t.rows_r);
+}
+// launch_psd64k's `form`: the columns form (psd_form: below kPsdRowsFormShift bits, kPsdColsMaxG + 1 at most) and the rows
+// form above it.  (psd_form itself stays the columns' value: tests/psd_cols_plan pins it.)
+constexpr int kPsdRowsFormShift = 16;
+static_assert(kPsdColsMaxG + 1 < (1 << kPsdRowsFormShift) && kPsdRowsMaxR < (1 << (31 - kPsdRowsFormShift)), "the two forms share an int");
+inline int psd_launch_form(const SpectrumTuning& t, int nframes, int num_cus) {
+  return psd_form(t, nframes, num_cus) | (psd_rows_form(t, nframes, num_cus) << kPsdRowsFormShift);
 }
 
 inline int round_up64(int v) { return (v + 63) & ~63; }

@@ -20,11 +20,13 @@
 // The shipped pair keeps the intermediate as block-scaled 24-bit fixed point (psd_cols_pk / psd_rows_pk below), and its
 // columns pass is a LOOP OVER FRAMES: 16 x G resident workgroups, each keeping its column block -- table, window and
 // four-step twiddles set up once -- and loading its next frame while it transforms one (psd_cols_pk_kernel; the grid is
-// host_plan.h plan_psd_cols; LABNOTES 15).  One unit per workgroup (psd_cols_pk_unit_kernel, PYSDR_PSD_PATH=unit) is the A/B form.
+// host_plan.h plan_psd_cols; LABNOTES 15).  The rows pass is the same kind of loop on 8 x R workgroups (psd_rows_pk_kernel,
+// plan_psd_rows).  One unit per workgroup (psd_cols_pk_unit_kernel / psd_rows_pk_unit_kernel, PYSDR_PSD_PATH=unit) is the A/B form.
 #include <algorithm>
 
 #include "common.h"
 #include "psd_cols_geom.h"
+#include "psd_rows_geom.h"
 
 namespace pysdr {
 
@@ -534,7 +536,7 @@ __device__ __forceinline__ void rows_unit_pk(const char* __restrict__ wf, float*
   }
 }
 
-__global__ __launch_bounds__(512) void psd_rows_pk_kernel(const char* __restrict__ work, float* __restrict__ out, int db) {
+__global__ __launch_bounds__(512) void psd_rows_pk_unit_kernel(const char* __restrict__ work, float* __restrict__ out, int db) {
   __shared__ __attribute__((aligned(16))) float2 lds[kRowLds];
   __shared__ __attribute__((aligned(16))) float2 tw[16 * kTwRow];
   const int f = blockIdx.y;
@@ -542,22 +544,142 @@ __global__ __launch_bounds__(512) void psd_rows_pk_kernel(const char* __restrict
   rows_unit_pk(work + (size_t)f * kN * sizeof(float2), out + (size_t)f * kN, blockIdx.x, db, threadIdx.x, lds, tw);
 }
 
+
+// ---- the same rows pass as a LOOP OVER FRAMES, the columns loop's counterpart: grid = 8 x R, workgroup (rb, r) keeps row
+// block rb and walks over the frames r, r + R, r + 2 R, ... of the launch (R = gridDim.y <= nframes: host_plan.h
+// plan_psd_rows; all 8 R workgroups are resident at once, none gets more than one frame more than another).  Nothing happens
+// across workgroups.  Set up ONCE in front of the loop: the W_256 table (256 v_sin / v_cos pairs and the barrier behind
+// them) and every index that depends on (tid, rb) only.  The arithmetic of a frame is the unit's, operation by operation on
+// the same values in the same order, so every bit of the PSD is what psd_rows_pk_unit_kernel writes
+// (tests/test_gpu_psd_rows_loop.py).
+// A unit is a strict chain -- 48 vector loads, wait, DFT16, barrier, LDS, barrier, DFT16, log, 16 stores -- that only the
+// CU's one other workgroup hides.  Here the 16 HI dwords and 16 LO halfwords of the workgroup's NEXT frame are loaded while
+// this one is transformed, the way cols_prefetch does it (inline asm, "+v" ties, waited for by hand in front of the frame's
+// stores, taken at the top of the next iteration).  The 16 block scales a wave needs, ss[4 c1 + wave], are the same for all
+// its lanes: they come over the scalar path (16 scalar loads from a base that holds the wave's slot; the unit spends 16
+// vector loads per thread on them) into scalar registers, prefetched with the frame and waited for with it.  The intermediate
+// was written by the columns kernel, a launch earlier on the same stream: nothing this kernel reads changes while it runs.
+//   (saddr form: one 32-bit lane offset per plane; the frame's base + 16 KB c1 (HI) / + 256 KB + 8 KB c1 (LO) in scalar registers)
+#define PYSDR_ROWS_SLOAD(c1, off) asm volatile("s_load_dword %0, %1, " #off : "+s"(ns[c1]) : "s"(sbase))
+__device__ __forceinline__ void rows_prefetch(unsigned (&nh)[16], unsigned (&nl)[16], float (&ns)[16], unsigned voh, unsigned vol,
+                                              const char* wf, int wave4) {
+  const PYSDR_AS1 char* base = (const PYSDR_AS1 char*)wf;
+#pragma unroll
+  for (int c1 = 0; c1 < 16; ++c1)
+    asm volatile("global_load_dword %0, %1, %2" : "+v"(nh[c1]) : "v"(voh), "s"(base + 16384 * c1));
+#pragma unroll
+  for (int c1 = 0; c1 < 16; ++c1)
+    asm volatile("global_load_ushort %0, %1, %2" : "+v"(nl[c1]) : "v"(vol), "s"(base + kPkLoOff + 8192 * c1));
+  const PYSDR_AS1 char* sbase = base + kPkScaleOff + wave4;              // slot 4 c1 + wave of the 16 x 4 scales
+  PYSDR_ROWS_SLOAD(0, 0x00); PYSDR_ROWS_SLOAD(1, 0x10); PYSDR_ROWS_SLOAD(2, 0x20); PYSDR_ROWS_SLOAD(3, 0x30);
+  PYSDR_ROWS_SLOAD(4, 0x40); PYSDR_ROWS_SLOAD(5, 0x50); PYSDR_ROWS_SLOAD(6, 0x60); PYSDR_ROWS_SLOAD(7, 0x70);
+  PYSDR_ROWS_SLOAD(8, 0x80); PYSDR_ROWS_SLOAD(9, 0x90); PYSDR_ROWS_SLOAD(10, 0xa0); PYSDR_ROWS_SLOAD(11, 0xb0);
+  PYSDR_ROWS_SLOAD(12, 0xc0); PYSDR_ROWS_SLOAD(13, 0xd0); PYSDR_ROWS_SLOAD(14, 0xe0); PYSDR_ROWS_SLOAD(15, 0xf0);
+}
+#undef PYSDR_ROWS_SLOAD
+// one wait for both counters (the scalar loads count on lgkmcnt beside the LDS traffic, which hipcc counts without them:
+// its own waits can only come out stricter); an asm statement takes 30 operands, so the LO plane and the scales are tied by
+// two empty statements behind it -- volatile statements keep their order
+__device__ __forceinline__ void rows_prefetch_wait(unsigned (&nh)[16], unsigned (&nl)[16], float (&ns)[16]) {
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
+               : "+v"(nh[0]), "+v"(nh[1]), "+v"(nh[2]), "+v"(nh[3]), "+v"(nh[4]), "+v"(nh[5]), "+v"(nh[6]), "+v"(nh[7]),
+                 "+v"(nh[8]), "+v"(nh[9]), "+v"(nh[10]), "+v"(nh[11]), "+v"(nh[12]), "+v"(nh[13]), "+v"(nh[14]), "+v"(nh[15]));
+  asm volatile(""
+               : "+v"(nl[0]), "+v"(nl[1]), "+v"(nl[2]), "+v"(nl[3]), "+v"(nl[4]), "+v"(nl[5]), "+v"(nl[6]), "+v"(nl[7]),
+                 "+v"(nl[8]), "+v"(nl[9]), "+v"(nl[10]), "+v"(nl[11]), "+v"(nl[12]), "+v"(nl[13]), "+v"(nl[14]), "+v"(nl[15]));
+  asm volatile(""
+               : "+s"(ns[0]), "+s"(ns[1]), "+s"(ns[2]), "+s"(ns[3]), "+s"(ns[4]), "+s"(ns[5]), "+s"(ns[6]), "+s"(ns[7]),
+                 "+s"(ns[8]), "+s"(ns[9]), "+s"(ns[10]), "+s"(ns[11]), "+s"(ns[12]), "+s"(ns[13]), "+s"(ns[14]), "+s"(ns[15]));
+}
+
+// (512 threads and 72 KB of LDS: two workgroups per CU = four waves per SIMD, so up to 128 registers cost nothing)
+__global__ __launch_bounds__(512, 4) void psd_rows_pk_kernel(const char* __restrict__ work, float* __restrict__ out, int db,
+                                                             int nframes) {
+  __shared__ __attribute__((aligned(16))) float2 lds[kRowLds];
+  __shared__ __attribute__((aligned(16))) float2 tw[16 * kTwRow];
+  const int tid = threadIdx.x, rb = blockIdx.x;
+  PsdRowsWalk fr((int)blockIdx.y, (int)gridDim.y, nframes);             // fr.f < nframes: the grid has at most nframes rows
+  // pass 1 thread (c0, pl): element (rb 32 + pl) 16 + c0 = 512 rb + tid of plane block c1
+  const unsigned idx = 512u * (unsigned)rb + (unsigned)tid;
+  const unsigned voh = idx * 4u, vol = idx * 2u;
+  const int wave4 = 4 * __builtin_amdgcn_readfirstlane((tid >> 6) & 3);  // the wave's 4 rows p share (p % 16) >> 2
+  unsigned nh[16] = {}, nl[16] = {};
+  float ns[16] = {};
+  rows_prefetch(nh, nl, ns, voh, vol, work + (size_t)fr.f * kN * sizeof(float2), wave4);   // the first frame, behind which the set-up hides
+  tw256_build(tw, tid);
+  const int c0 = tid & 15;
+  float2* const p1w = lds + 17 * (tid >> 4) + c0;                        // pass 1 writes slot(q1, pl = tid >> 4, c0)
+  const int pl = tid & 31, q1 = tid >> 5;
+  const float2* const p2r = lds + 544 * q1 + 17 * pl;                    // pass 2 reads slot(q1, pl, c0 = 0 .. 15)
+  // bin k = kb + 4096 q0 with kb < 4096, so its fftshifted place (k + 32768) & 65535 is kb + 4096 ((q0 + 8) & 15)
+  const unsigned kbo = (unsigned)(rb * kRowsPerWg + pl + 256 * q1) * (unsigned)sizeof(float);
+  rows_prefetch_wait(nh, nl, ns);
+  __syncthreads();                                                      // the table
+  for (;;) {
+    float2 u[16];
+#pragma unroll
+    for (int c1 = 0; c1 < 16; ++c1) {
+      const float inv = ns[c1];                                          // block scale / 256
+      const int xr = (int)pk_perm(nl[c1], nh[c1], 0x0100040cu);          // [0, l.b0, h.b0, h.b1] = Re * 256
+      const int xi = (int)pk_perm(nl[c1], nh[c1], 0x0302050cu);          // [0, l.b1, h.b2, h.b3] = Im * 256
+      u[c1] = make_float2((float)xr * inv, (float)xi * inv);
+      // formed HERE, in front of the loads that overwrite nh / nl / ns (see psd_cols_pk_kernel)
+      asm volatile("" : "+v"(u[c1].x), "+v"(u[c1].y));
+    }
+    if (fr.has_next()) rows_prefetch(nh, nl, ns, voh, vol, work + (size_t)fr.fn * kN * sizeof(float2), wave4);   // never a frame the launch does not have
+    dft16(u);
+    twiddle_tab(u, tw, c0);                                              // W_256^(c0 q1)
+    // No barrier in front of these writes: (C) of the last iteration lies behind every thread's pass-2 reads of it.
+#pragma unroll
+    for (int k = 0; k < 16; ++k) p1w[544 * k] = u[k];
+    __syncthreads();                                                    // (B) pass 1 -> pass 2
+    float2 v[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = p2r[k];
+    __syncthreads();                                                    // (C) pass 2 has read: the next frame's pass 1 may write
+    dft16(v);
+    float pw[16];
+#pragma unroll
+    for (int q0 = 0; q0 < 16; ++q0) {
+      pw[q0] = v[q0].x * v[q0].x + v[q0].y * v[q0].y;
+      if (db) pw[q0] = 3.0102999566398120f * __builtin_amdgcn_logf(pw[q0] + 1.0e-30f);
+    }
+    rows_prefetch_wait(nh, nl, ns);        // the next frame: in flight since the top of this iteration
+    // (the frame's base + 16 KB ((q0 + 8) & 15) in scalar registers, one 32-bit lane offset)
+    PYSDR_AS1 char* const o = (PYSDR_AS1 char*)(out + (size_t)fr.f * kN);
+#pragma unroll
+    for (int q0 = 0; q0 < 16; ++q0) {
+      PYSDR_AS1 char* oq = o + 16384 * ((q0 + 8) & 15);
+      asm("" : "+s"(oq));                  // kept a scalar base: reassociated with kbo it becomes a 64-bit vector sum per store
+      __builtin_nontemporal_store(pw[q0], (PYSDR_AS1 float*)(oq + kbo));
+    }
+    if (!fr.has_next()) break;
+    fr.advance();
+  }
+}
+
 }  // namespace
 
 // nframes frames; `work` holds nframes x 65536 complex of intermediate.
-// form (host_plan.h psd_form): 0 = float2 intermediate; 1 = 24-bit intermediate, one columns unit per workgroup;
-// 1 + G = 24-bit intermediate, columns as a loop over frames on a grid of 16 x min(G, nframes) workgroups
+// form (host_plan.h psd_launch_form): 0 = float2 intermediate; otherwise the 24-bit intermediate, with the columns form in the
+// low 16 bits (psd_form: 1 = one columns unit per workgroup, 1 + G = the loop over frames on 16 x min(G, nframes) workgroups)
+// and the rows form above them (psd_rows_form: 0 = one rows unit per workgroup, R = the loop on 8 x min(R, nframes))
 int launch_psd64k(const float2* x, size_t hop, int nframes, const float* win, float2* work,
                   float* out, int db, hipStream_t st, int form) {
-  if (form >= 1) {
-    if (form > 1) {
-      const int rows = std::min(form - 1, nframes);
+  const int cform = form & 0xffff, rform = form >> 16;
+  if (cform >= 1) {
+    if (cform > 1) {
+      const int rows = std::min(cform - 1, nframes);
       hipLaunchKernelGGL(psd_cols_pk_kernel, dim3(256 / kColsPerWg, rows), dim3(256), 0, st, x, hop, win, (char*)work, nframes);
     } else {
       hipLaunchKernelGGL(psd_cols_pk_unit_kernel, dim3(256 / kColsPerWg, nframes), dim3(256), 0, st, x, hop, win, (char*)work);
     }
     PYSDR_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(psd_rows_pk_kernel, dim3(256 / kRowsPerWg, nframes), dim3(512), 0, st, (const char*)work, out, db);
+    if (rform > 0) {
+      hipLaunchKernelGGL(psd_rows_pk_kernel, dim3(256 / kRowsPerWg, std::min(rform, nframes)), dim3(512), 0, st, (const char*)work, out, db, nframes);
+    } else {
+      hipLaunchKernelGGL(psd_rows_pk_unit_kernel, dim3(256 / kRowsPerWg, nframes), dim3(512), 0, st, (const char*)work, out, db);
+    }
     PYSDR_HIP_CHECK(hipGetLastError());
     return PYSDR_OK;
   }
