@@ -601,6 +601,36 @@ int  pysdr_ft8_fetch(pysdr_ft8* ft8, const int* rows, int nrows, int32_t* events
 int  pysdr_ft8_llr(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, float* out);
 int  pysdr_ft8_state(pysdr_ft8* ft8, float* sc, int32_t* hits, float* ring, long long* t_done);
 
+/* ---- FT4 skimmer: four Costas arrays and soft bits on a fine raster of the band --------------
+ * The fifth client of a channelizer (either kind, M / D = 4, rows at S = 48 or 72 samples per symbol of 125 / 6 baud).
+ * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 6 bins baud / 2 apart whose powers are
+ * taken four times per symbol (a step: QS = S / 4 row outputs) into a device ring [nk][TR][NB].  Fine row F = a NSUB + j.
+ * A frame is 103 symbols of 4 tones with four different 4-symbol Costas arrays at symbols 0, 33, 66 and 99.  An event is
+ * a frame start t0 whose Costas score is a peak over four steps to either side, at least smin, with at least hmin of the
+ * 16 sync symbols strongest on their own tone; it is emitted at step t0 + 412.  Steps, calls, event words, fetch, state
+ * and every refusal are pysdr_ft8_*'s with these numbers: S 48 or 72, nk S / 2 <= 2^18, hmin in [0, 16], t0 = steps[0] +
+ * index - 412, cap = (max_out / QS + 1) / 5 + 1, TR = 417 + 2 (max_out / QS + 1) steps.
+ * llr: the 174 soft bits, in transmission order, of n <= 4096 candidates: for data symbol d (frame symbol 4 + d, 37 +
+ * (d - 29) from d = 29 on, 70 + (d - 58) from d = 58 on) and the powers p[v] of its four values v (sent on tone GRAY4[v],
+ * GRAY4 = [0,1,3,2]), bit 2, 1 of v in that order gives max over the values with the bit minus max over those without.
+ * A frame is not yet complete while t0 + 408 >= steps done. */
+typedef struct pysdr_ft4_cfg {
+  float smin;               /* least score of an event */
+  int32_t hmin;             /* least hit count of an event, of 16 */
+  float pmax;               /* bin powers above this (or not finite) are blanked */
+} pysdr_ft4_cfg;
+typedef struct pysdr_ft4 pysdr_ft4;
+int  pysdr_ft4_plan(int nk, int S, int max_out, const pysdr_ft4_cfg* cfg, int32_t out[8]);
+int  pysdr_ft4_create(pysdr_chan* ch, int S, const pysdr_ft4_cfg* cfg, const float* tw, int max_out, pysdr_ft4** out);
+void pysdr_ft4_destroy(pysdr_ft4* ft4);
+int  pysdr_ft4_reset(pysdr_ft4* ft4);
+int  pysdr_ft4_sync(pysdr_ft4* ft4);
+int  pysdr_ft4_process(pysdr_ft4* ft4, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch, long long* steps);
+int  pysdr_ft4_fetch(pysdr_ft4* ft4, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_ft4_llr(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, float* out);
+int  pysdr_ft4_state(pysdr_ft4* ft4, float* sc, int32_t* hits, float* ring, long long* t_done);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -1,0 +1,220 @@
+// C ABI of the FT4 skimmer (include/pysdr_hip.h).  Host-side only, like api_ft8.hip, whose call rules
+// and refusals these are: the kernels and their launch functions live in ft4.hip, what both sides share in ft4_plan.h.
+// The skimmer borrows a channelizer as the other skimmers do (chan_client.h: what the channelizer's clients share) and
+// queues its kernels behind the channelizer's launch on the channelizer's stream.  Every device resource is an owner
+// (host_res.h): deleting the object frees it.
+#include "chan_client.h"
+#include "ft4_plan.h"
+
+using namespace pysdr;
+
+struct pysdr_ft4 : ChanClient {
+  int max_out = 0;
+  pysdr_ft4_cfg cfg{};
+  Ft4Plan plan;
+  unsigned long long t_done = 0;    // steps complete since create / reset
+  DevBuf<Ft8C> d_y;                 // [nk][ypitch]: kFt4Hpad of history room, then the call's outputs
+  DevBuf<Ft8C> d_tw;                // [NT]
+  DevBuf<float> d_ring;             // [nk][tr][NB]
+  DevBuf<float> d_sc;               // [9][nfine]
+  DevBuf<int32_t> d_hi;             // [9][nfine]
+  DevBuf<int32_t> d_events;         // [nfine][cap][2]
+  DevBuf<int32_t> d_counts;         // [nfine]
+  DevBuf<int32_t> d_cand;           // [kFt4LlrMax][2]
+  DevBuf<float> d_llr;              // [kFt4LlrMax][174]
+  std::vector<float> h_tw;
+  std::vector<int32_t> h_cand;
+};
+
+namespace {
+
+int ft4_alloc(pysdr_ft4* w) {
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine, S = (size_t)w->plan.S;
+  PYSDR_HIP_CHECK(w->d_y.alloc(nk * (size_t)w->plan.ypitch));
+  PYSDR_HIP_CHECK(w->d_tw.alloc(4 * S));
+  PYSDR_HIP_CHECK(w->d_ring.alloc(nk * (size_t)w->plan.tr * (size_t)w->plan.nb));
+  PYSDR_HIP_CHECK(w->d_sc.alloc((size_t)kFt8Keep * nf));
+  PYSDR_HIP_CHECK(w->d_hi.alloc((size_t)kFt8Keep * nf));
+  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap * kFt8EventWords));
+  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
+  PYSDR_HIP_CHECK(w->d_cand.alloc((size_t)kFt4LlrMax * 2));
+  PYSDR_HIP_CHECK(w->d_llr.alloc((size_t)kFt4LlrMax * kFt4Bits));
+  return PYSDR_OK;
+}
+
+int ft4_reset_locked(pysdr_ft4* w) {
+  const int rc = pysdr_chan_reset(w->ch);
+  if (rc != PYSDR_OK) return rc;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // the host arrays may still feed an earlier copy
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_tw.get(), w->h_tw.data(), w->h_tw.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_y.get(), 0, nk * (size_t)w->plan.ypitch * sizeof(Ft8C), st));   // y[k] = 0 for k < 0
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_ring.get(), 0, nk * (size_t)w->plan.tr * (size_t)w->plan.nb * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sc.get(), 0, (size_t)kFt8Keep * nf * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_hi.get(), 0, (size_t)kFt8Keep * nf * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * kFt8EventWords * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  w->last_n_out = 0;
+  w->t_done = 0;
+  return PYSDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pysdr_ft4_plan(int nk, int S, int max_out, const pysdr_ft4_cfg* cfg, int32_t out[8]) {
+  if (!out) { set_last_error("pysdr_ft4_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  Ft4Plan p;
+  if (!ft4_plan(nk, S, max_out, cfg, &p)) {
+    set_last_error("pysdr_ft4_plan: S %d is neither 48 nor 72, nk %d < 1 or nk S / 2 > %d, max_out %d outside [1, %d], a spectrum ring "
+                   "above %lld bytes, or a cfg outside the rules (NULL; smin >= 0, 0 <= hmin <= 16, 0 < pmax <= 1e18, all finite)", S, nk,
+                   kFt4FineMax, max_out, kFt4MaxOutMax, kFt4RingBytesMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = 1; out[1] = ft4_threads(S); out[2] = ft4_lds_bytes(S); out[3] = S; out[4] = p.cap; out[5] = p.groups;
+  out[6] = p.nsub; out[7] = p.tr;
+  return PYSDR_OK;
+}
+
+int pysdr_ft4_create(pysdr_chan* ch, int S, const pysdr_ft4_cfg* cfg, const float* tw, int max_out, pysdr_ft4** out) {
+  if (!out) { set_last_error("pysdr_ft4_create: out is NULL"); return PYSDR_ERR_ARG; }
+  *out = nullptr;
+  if (!ch || !cfg || !tw) { set_last_error("pysdr_ft4_create: NULL channelizer, cfg or tw"); return PYSDR_ERR_ARG; }
+  pysdr_ft4* w = new pysdr_ft4();
+  int32_t pl[8];
+  int rc = client_bind(w, ch);
+  if (rc == PYSDR_OK) rc = pysdr_ft4_plan(w->nk, S, max_out, cfg, pl);
+  if (rc != PYSDR_OK) { delete w; return rc; }
+  w->max_out = max_out; w->cfg = *cfg;
+  ft4_plan(w->nk, S, max_out, cfg, &w->plan);
+  w->h_tw.assign(tw, tw + 2 * 4 * (size_t)S);
+  w->h_cand.reserve((size_t)kFt4LlrMax * 2);
+  return client_create(w, "pysdr_ft4_create", ft4_alloc, ft4_reset_locked, out);
+}
+
+void pysdr_ft4_destroy(pysdr_ft4* w) { client_destroy(w); }
+
+int pysdr_ft4_reset(pysdr_ft4* w) {
+  if (!w) { set_last_error("pysdr_ft4_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  return ft4_reset_locked(w);
+}
+
+int pysdr_ft4_sync(pysdr_ft4* w) {
+  if (!w) { set_last_error("pysdr_ft4_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
+  return client_sync(w);
+}
+
+int pysdr_ft4_process(pysdr_ft4* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                      long long ev_pitch, long long* steps) {
+  if (!w || !n_out) { set_last_error("pysdr_ft4_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
+  *n_out = 0;
+  std::lock_guard<std::mutex> lk(w->mu);
+  ClientStep step;
+  int rc = client_begin(w, "pysdr_ft4_process", iq, n, &step);
+  if (rc != PYSDR_OK) return rc;
+  const int words = w->plan.cap * kFt8EventWords;
+  if (events && ev_pitch < words) {
+    set_last_error("pysdr_ft4_process: ev_pitch %lld < the event cap's %d words", ev_pitch, words);
+    return PYSDR_ERR_STATE;
+  }
+  if (step.nf_want > (unsigned long long)w->max_out) {
+    set_last_error("pysdr_ft4_process: the call would complete %llu outputs, max_out is %d", step.nf_want, w->max_out);
+    return PYSDR_ERR_STATE;
+  }
+  int nf = 0;
+  rc = client_feed(w, "pysdr_ft4_process", "skimmer", iq, n, on_device, w->d_y.get() + kFt4Hpad, w->plan.ypitch, step, &nf);
+  if (rc != PYSDR_OK) return rc;
+  const size_t nfine = (size_t)w->plan.nfine;
+  const int S = w->plan.S;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  if (steps) { steps[0] = (long long)w->t_done; steps[1] = 0; }
+  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
+    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
+  } else {
+    const unsigned long long t1 = ft8_steps_done(step.m0 + (unsigned long long)nf, S);
+    Ft4Args a{};
+    a.y = w->d_y.get() + kFt4Hpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.ns = (int)(t1 - w->t_done);
+    a.e_first = a.ns > 0 ? (int)((unsigned long long)(S / 4) * w->t_done + (unsigned long long)(S - 1) - step.m0) : 0;
+    a.tr = w->plan.tr; a.t_first = (long long)w->t_done;
+    a.cfg = w->cfg; a.tw = w->d_tw.get(); a.ring = w->d_ring.get(); a.sc = w->d_sc.get(); a.hi = w->d_hi.get();
+    a.events = w->d_events.get(); a.counts = w->d_counts.get();
+    if (a.ns < 0 || a.ns > ft4_steps_per_call(w->max_out, S) || a.e_first < 0 || a.e_first >= (w->t_done ? S / 4 : S)) {
+      set_last_error("pysdr_ft4_process: the step count lost its place (%d steps, first at output %d)", a.ns, a.e_first);
+      return PYSDR_ERR_STATE;
+    }
+    if (a.ns == 0) PYSDR_HIP_CHECK(hipMemsetAsync(a.counts, 0, nfine * sizeof(int32_t), st));   // outputs but no step: only the history rolls
+    rc = launch_ft4_steps(S, a, st);
+    if (rc) return rc;
+    w->t_done = t1;
+    *n_out = nf;
+    if (steps) steps[1] = a.ns;
+    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (events)
+      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)words * sizeof(int32_t),
+                                       (size_t)words * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
+  }
+  if (counts || events || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
+  return PYSDR_OK;
+}
+
+int pysdr_ft4_fetch(pysdr_ft4* w, const int* rows, int nrows, int32_t* events, long long pitch) {
+  if (!w) { set_last_error("pysdr_ft4_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
+  return client_fetch_events(w, "pysdr_ft4_fetch", "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap * kFt8EventWords, rows, nrows,
+                             events, pitch);
+}
+
+int pysdr_ft4_llr(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, float* out) {
+  if (!w) { set_last_error("pysdr_ft4_llr: NULL skimmer"); return PYSDR_ERR_ARG; }
+  if (n < 0 || n > kFt4LlrMax || (n > 0 && (!F || !t0 || !out))) {
+    set_last_error("pysdr_ft4_llr: n %d outside [0, %d] / NULL F, t0 or out", n, kFt4LlrMax);
+    return PYSDR_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(w->mu);
+  const long long done = (long long)w->t_done;
+  for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
+    if (!ft4_llr_ok(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+      set_last_error("pysdr_ft4_llr: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the "
+                     "ring (%lld steps done, its last is %lld, the ring holds %d)", i, (int)F[i], t0[i], w->plan.nfine, done,
+                     t0[i] + kFt4Lag, w->plan.tr);
+      return F[i] < 0 || F[i] >= w->plan.nfine ? PYSDR_ERR_ARG : PYSDR_ERR_STATE;
+    }
+  if (n == 0) return PYSDR_OK;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // h_cand may still feed an earlier copy
+  w->h_cand.resize((size_t)n * 2);
+  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % w->plan.tr); }
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  Ft4LlrArgs a{};
+  a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.n = n; a.cand = w->d_cand.get(); a.out = w->d_llr.get();
+  const int rc = launch_ft4_llr(a, st);
+  if (rc) return rc;
+  PYSDR_HIP_CHECK(hipMemcpyAsync(out, a.out, (size_t)n * kFt4Bits * sizeof(float), hipMemcpyDeviceToHost, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  return PYSDR_OK;
+}
+
+int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
+  if (!w) { set_last_error("pysdr_ft4_state: NULL skimmer"); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nf = (size_t)w->plan.nfine;
+  if (sc) PYSDR_HIP_CHECK(hipMemcpyAsync(sc, w->d_sc.get(), (size_t)kFt8Keep * nf * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (hits) PYSDR_HIP_CHECK(hipMemcpyAsync(hits, w->d_hi.get(), (size_t)kFt8Keep * nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (ring)
+    PYSDR_HIP_CHECK(hipMemcpyAsync(ring, w->d_ring.get(), (size_t)w->nk * (size_t)w->plan.tr * (size_t)w->plan.nb * sizeof(float),
+                                   hipMemcpyDeviceToHost, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  if (t_done) *t_done = (long long)w->t_done;
+  return PYSDR_OK;
+}
+
+}  // extern "C"

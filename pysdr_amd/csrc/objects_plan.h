@@ -198,4 +198,10 @@ struct Ft8LlrArgs;
 int launch_ft8_steps(int S, const Ft8Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
 int launch_ft8_llr(const Ft8LlrArgs& a, hipStream_t st);
 
+// ---- FT4 skimmer (ft4.hip, host half api_ft4.hip; plan, steps and kernel arguments: ft4_plan.h) ------------------------
+struct Ft4Args;
+struct Ft4LlrArgs;
+int launch_ft4_steps(int S, const Ft4Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
+int launch_ft4_llr(const Ft4LlrArgs& a, hipStream_t st);
+
 }  // namespace pysdr

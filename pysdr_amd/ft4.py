@@ -1,0 +1,159 @@
+"""FT4 skimmer: four Costas arrays and soft bits on a fine raster of the band (kernels ``ft4.hip``, host
+half ``api_ft4.hip``).  4-GFSK at 125 / 6 baud, tones one baud apart, 103 symbols of which 16 are four different Costas
+arrays.  A channelizer with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders
+run on the device, one every 10.4 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The
+device finds every frame by its sync score and hands out its 174 soft bits in transmission order; LDPC, CRC, the bit
+scrambler and message text are not here.  The decoder bank and the skimmer are ``ft8.py``'s, told this mode's constants,
+settings, plan and tables; the finder and the soft bits' helpers are ``ft8.py``'s as they are."""
+from __future__ import annotations
+
+import ctypes as C
+import sys
+
+import numpy as np
+
+from . import _lib
+from . import channelizer as _chan
+from . import psk as _psk
+from ._lib import Ft4Cfg
+from .ft8 import FT8_Decoders, FT8_Skimmer, hard_bits, owners, unit_llr, unpack  # noqa: F401  (this mode's too)
+
+BAUD = 125.0 / 6.0
+COSTAS = ((0, 1, 3, 2), (1, 0, 2, 3), (2, 3, 1, 0), (3, 2, 0, 1))   # at symbols 0, 33, 66 and 99
+GRAY4 = (0, 1, 3, 2)                             # value v is sent on tone GRAY4[v]
+SYMBOLS, DATA, BITS = 103, 87, 174
+SYNC_AT = (0, 33, 66, 99)                        # first symbol of the four Costas arrays
+FRAME_SECONDS, SLOT_SECONDS, NOMINAL_START = SYMBOLS / BAUD, 7.5, 0.5
+STEPS_PER_SYMBOL = 4
+EMIT_LAG = 412                                   # an event t0 is emitted at step t0 + 412 ...
+HOLD = 417                                       # ... and released once step t0 + 416 is complete: every rival has arrived
+KEEP = 9
+SHAPES = (48, 72)                                # row samples per symbol
+NB_EXTRA = 6                                     # NB = NSUB + 6: decoder j uses bins j + 2 tone, tone 0 to 3
+LLR_MAX = 4096
+
+
+def shape(fs):
+    """-> (S, D, M): S = 48 row samples per symbol if fs / (48 baud) is an integer D and the channelizer accepts M = 4 D,
+    otherwise S = 72 likewise, otherwise ValueError (``ft8.shape``'s rules)."""
+    for S in SHAPES:
+        d = float(fs) / (S * BAUD)
+        D = int(round(d))
+        if D < 1 or abs(d - D) > 1e-9 * max(d, 1.0):
+            continue
+        try:
+            _chan.plan(4 * D, D, 16 * D)
+        except _lib.PysdrError:
+            continue
+        return S, D, 4 * D
+    raise ValueError(f"no FT4 raster for fs = {fs}: fs / 1000 or fs / 1500 must be an integer D with M = 4 D a channelizer size")
+
+
+def prototype(fs, M, S):
+    """The channelizer's prototype for the FT4 raster, ``psk.prototype``'s form: cut at fs_out / 2 = S baud / 2, sum 1; flat
+    within 0.1 dB out to fp = (NB + 1) baud / 4 + baud and at least 70 dB down from fs_out - fp on."""
+    return _psk.prototype(fs, M, BAUD, S)
+
+
+def fine_channelizer(fs, band, device=0, max_in=1 << 22):
+    """A ``fine.FineChannelizer`` for ``FT4_Skimmer(fs, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4 apart whose
+    centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 48 where ``fine.shape`` finds a shape, else 72; M2 / D2 =
+    4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
+    from . import fine
+    err = None
+    for S in SHAPES:
+        try:
+            M1, D1, M2, D2 = fine.shape(fs, S * BAUD, 4)
+        except ValueError as e:
+            err = e
+            continue
+        h2 = prototype(float(fs) / D1, M2, S)
+        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
+                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
+    raise ValueError(f"no FT4 raster in two stages for fs = {fs}: {err}")
+
+
+def tables(S):
+    """-> tw float32 [4 S][2] = (cos, -sin)(2 pi i / NT): derived in float64, rounded once"""
+    t = 2 * np.pi * np.arange(4 * S) / (4 * S)
+    return np.ascontiguousarray(np.stack((np.cos(t), -np.sin(t)), axis=1), np.float32)
+
+
+def params(smin=4.0, hmin=12, pmax=1e18):
+    """The settings of DESIGN.md 3 item 23 as the ``_lib.Ft4Cfg`` the C ABI takes."""
+    return Ft4Cfg(smin=float(np.float32(smin)), hmin=int(hmin), pmax=float(np.float32(pmax)))
+
+
+def cfg_dict(cfg):
+    return {k: getattr(cfg, k) for k, _ in Ft4Cfg._fields_}
+
+
+def plan(nk, S, max_out, cfg):
+    """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
+    samples, event cap per decoder and call, workgroups, decoders per row, ring depth in steps.  Raises PysdrError
+    outside the rules."""
+    v = _lib.plan_call("pysdr_ft4_plan", 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
+    return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6], "tr": v[7]}
+
+
+def steps_done(n_out, S):
+    """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1"""
+    return (int(n_out) - S) // (S // 4) + 1 if n_out >= S else 0
+
+
+def tones(bits):
+    """174 bits in transmission order -> the frame's 103 tones: the four Costas arrays at symbols 0, 33, 66 and 99, 3 x 29
+    data symbols of 2 bits, MSB first, Gray-mapped"""
+    bits = np.asarray(bits, np.int64).reshape(DATA, 2)
+    g = np.array(GRAY4)[2 * bits[:, 0] + bits[:, 1]]
+    return np.concatenate((COSTAS[0], g[:29], COSTAS[1], g[29:58], COSTAS[2], g[58:], COSTAS[3])).astype(np.int64)
+
+
+def waveform(tones, f0, fs, gfsk=True, ramps=True, phase=0.0):
+    """complex128 frame at ``fs``: tone 0 at ``f0`` Hz from the centre, continuous phase, amplitude 1 over the frame's
+    symbols.  ``gfsk``: the frequency pulse of a symbol is (erf(k (t + 1/2)) - erf(k (t - 1/2))) / 2, k = pi sqrt(2 / ln 2), t
+    in symbols from the symbol's middle (BT = 1; it reaches two symbols to either side), the first and the last tone held
+    beyond the frame; otherwise rectangular.  With ``ramps`` one more symbol before and one after the frame hold the first
+    and the last tone under a raised-cosine amplitude, as on the air (105 symbols, 5.04 s): THE RETURNED ARRAY THEN STARTS
+    AT THE RAMP, and the frame's first Costas symbol -- the skimmer's t0 -- begins one symbol (fs / baud samples) later."""
+    from scipy.special import erf
+    tones = np.asarray(tones, np.float64)
+    if ramps:
+        tones = np.concatenate((tones[:1], tones, tones[-1:]))
+    sps = float(fs) / BAUD
+    n = int(round(len(tones) * sps))
+    t = (np.arange(n) + 0.5) / sps                                       # symbols
+    k0 = np.minimum(np.floor(t).astype(np.int64), len(tones) - 1)
+    if gfsk:
+        kk = np.pi * np.sqrt(2 / np.log(2))
+        ext = np.concatenate((tones[:1], tones[:1], tones, tones[-1:], tones[-1:]))
+        dev = np.zeros(n)
+        for d in (-2, -1, 0, 1, 2):                                      # the pulse is below 1e-13 beyond two symbols and a half
+            tau = t - (k0 + d) - 0.5
+            dev += ext[k0 + d + 2] * 0.5 * (erf(kk * (tau + 0.5)) - erf(kk * (tau - 0.5)))
+    else:
+        dev = tones[k0]
+    ph = np.cumsum(float(f0) + BAUD * dev)
+    w = np.exp(1j * (2 * np.pi / float(fs) * ph + phase))
+    if ramps:
+        first, last = t < 1, t >= len(tones) - 1
+        w[first] *= 0.5 * (1 - np.cos(np.pi * t[first]))
+        w[last] *= 0.5 * (1 + np.cos(np.pi * (t[last] - (len(tones) - 1))))
+    return w
+
+
+class FT4_Decoders(FT8_Decoders):
+    """The decoder bank on a borrowed ``Channelizer``: ``FT8_Decoders``' calls on ``pysdr_ft4_*`` with this module's
+    constants (an event's t0 is ``t_first + unpack(words)[0] - 412``)."""
+    KIND, DESTROY = "ft4", "pysdr_ft4_destroy"
+    MODE = sys.modules[__name__]
+
+
+class FT4_Skimmer(FT8_Skimmer):
+    """Wideband IQ at ``fs`` -> a channelizer of M = 4 D rows S baud / 4 apart at S baud = 1000 or 1500 samples per second ->
+    NSUB = S / 2 sync decoders inside every row, fine row F with tone 0 at ``freqs_fine[F]`` Hz (signed) -> a record for
+    every frame found, ``FT8_Skimmer``'s: ``t0`` (steps of a quarter symbol since create / reset; the first Costas symbol,
+    one symbol behind the start of the transmission's ramp), ``F``, ``freq``, ``time``, ``score``, ``hits`` and ``llr``
+    float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` (7.5 s) and ``dt`` (against 0.5 s).  The hold,
+    the finder and the release are ``FT8_Skimmer``'s code."""
+    DECODERS = FT4_Decoders

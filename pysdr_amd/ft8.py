@@ -8,6 +8,7 @@ derived."""
 from __future__ import annotations
 
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -29,6 +30,7 @@ EMIT_LAG = 316                                   # an event t0 is emitted at ste
 HOLD = 321                                       # ... and released once step t0 + 320 is complete: every rival has arrived
 KEEP = 9
 SHAPES = (64, 96)                                # row samples per symbol
+NB_EXTRA = 14                                    # NB = NSUB + 14: decoder j uses bins j + 2 tone, tone 0 to 7
 LLR_MAX = 4096
 
 
@@ -183,15 +185,16 @@ def waveform(tones, f0, fs, gfsk=True, phase=0.0):
 class FT8_Decoders(DecoderBank):
     """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
     KIND, DESTROY = "ft8", "pysdr_ft8_destroy"
+    MODE = sys.modules[__name__]                                         # the mode's constants, settings, plan and tables (``ft4.py`` has its own)
 
     def __init__(self, chan, S, max_out=256, cfg=None):
         super().__init__(chan, max_out)
-        self.S, self.nsub, self.nb, self.qs = int(S), int(S) // 2, int(S) // 2 + 14, int(S) // 4
+        self.S, self.nsub, self.nb, self.qs = int(S), int(S) // 2, int(S) // 2 + self.MODE.NB_EXTRA, int(S) // 4
         self.nfine = self.nk * self.nsub
-        self.cfg = params() if cfg is None else cfg
-        self.plan = plan(self.nk, self.S, self.max_out, self.cfg)         # a bad shape fails here
+        self.cfg = self.MODE.params() if cfg is None else cfg
+        self.plan = self.MODE.plan(self.nk, self.S, self.max_out, self.cfg)         # a bad shape fails here
         self.tr = self.plan["tr"]
-        self.tw = tables(self.S)
+        self.tw = self.MODE.tables(self.S)
         self._open(self.nfine, self.S, C.byref(self.cfg), _lib.as_pf(self.tw))
         self.slots = self.cap                                             # events per fine row and call
         self.cap = 2 * self.slots                                         # int32 words per fine row: what fetch and process move
@@ -204,7 +207,7 @@ class FT8_Decoders(DecoderBank):
     def decode_raw(self, x, n=None, on_device=False, events="all"):
         """One call of the C ABI: host samples (complex64 [n]) or a device pointer.  -> dict of n_out, m0, counts [nfine]
         and events [nfine][2 slots] int32 words (``DecoderBank._decode``'s rules), and t_first, n_steps: the steps complete
-        before the call and those it completed.  An event's t0 is ``t_first + unpack(words)[0] - 316``."""
+        before the call and those it completed.  An event's t0 is ``t_first + unpack(words)[0] - EMIT_LAG``."""
         steps = (C.c_longlong * 2)()
         r = self._decode(x, n, on_device, events, steps)
         self.t_done = steps[0] + steps[1]
@@ -218,7 +221,7 @@ class FT8_Decoders(DecoderBank):
         for k, F in enumerate(rows):
             for i in range(int(r["counts"][F])):
                 u, hits, score = unpack(words[k, 2 * i:2 * i + 2])
-                out.append((r["t_first"] + u - EMIT_LAG, int(F), score, hits))
+                out.append((r["t_first"] + u - self.MODE.EMIT_LAG, int(F), score, hits))
         return out
 
     def llr(self, F, t0):
@@ -226,7 +229,7 @@ class FT8_Decoders(DecoderBank):
         or has left the ring, or an F outside the raster"""
         F = np.ascontiguousarray(F, np.int32)
         t0 = np.ascontiguousarray(t0, np.int64)
-        out = np.zeros((len(F), BITS), np.float32)
+        out = np.zeros((len(F), self.MODE.BITS), np.float32)
         for i in range(0, len(F), LLR_MAX):
             f, t, o = F[i:i + LLR_MAX], t0[i:i + LLR_MAX], out[i:i + LLR_MAX]
             self._call("llr", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), _lib.as_pf(o))
@@ -252,29 +255,33 @@ class FT8_Skimmer(Skimmer):
     found: ``t0`` (steps of a quarter symbol since create / reset), ``F``, ``freq``, ``time`` (seconds into the stream),
     ``score``, ``hits`` and ``llr`` float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` and ``dt``."""
 
+    DECODERS = FT8_Decoders                                              # the bank; its MODE is the skimmer's too
+
     def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None):
-        self.fs, self.baud, self.t_first = float(fs), BAUD, t_first
+        m = self.DECODERS.MODE
+        self.fs, self.baud, self.t_first = float(fs), m.BAUD, t_first
         if chan is None:
-            self.S, self.D, self.M = shape(fs)
+            self.S, self.D, self.M = m.shape(fs)
             nk = self.M if channels is None else int(channels[1])
-            plan(nk, self.S, max_out, params())                          # a bad shape fails here, with or without a device
-            self.h = prototype(fs, self.M, self.S)
+            m.plan(nk, self.S, max_out, m.params())                      # a bad shape fails here, with or without a device
+            self.h = m.prototype(fs, self.M, self.S)
             self.chan = Channelizer(fs, self.M, self.D, self.h, channels, device, max_in)
         else:
             # a ready channelizer of either kind, adopted and owned: rows S baud / 4 apart at S baud samples per second
             self.chan = chan
-            s = chan.fs_out / BAUD
+            s = chan.fs_out / m.BAUD
             self.S, self.D, self.M = int(round(s)), chan.D, chan.M
-            if abs(s - self.S) > 1e-9 * s or self.S not in SHAPES or chan.M != 4 * chan.D or float(fs) != chan.fs:
-                raise ValueError(f"FT8_Skimmer: the channelizer's rows (fs {chan.fs}, fs_out {chan.fs_out}, M / D = "
-                                 f"{chan.M / chan.D}) are not at 64 or 96 samples per symbol of 6.25 baud with M / D = 4 at fs = {fs}")
+            if abs(s - self.S) > 1e-9 * s or self.S not in m.SHAPES or chan.M != 4 * chan.D or float(fs) != chan.fs:
+                raise ValueError(f"{type(self).__name__}: the channelizer's rows (fs {chan.fs}, fs_out {chan.fs_out}, M / D = "
+                                 f"{chan.M / chan.D}) are not at {m.SHAPES[0]} or {m.SHAPES[1]} samples per symbol of {m.BAUD:.6g} baud "
+                                 f"with M / D = 4 at fs = {fs}")
             self.h = chan.prototypes
         self.nsub, self.qs = self.S // 2, self.S // 4
-        self.dec = FT8_Decoders(self.chan, self.S, max_out)
+        self.dec = self.DECODERS(self.chan, self.S, max_out)
         self.nk, self.nfine, self.fs_out = self.chan.nk, self.dec.nfine, self.chan.fs_out
         self.freqs = self.chan.freqs
-        q = 2 * np.arange(self.nsub) - (self.nsub + 13)
-        self.freqs_fine = (self.freqs[:, None] + q[None, :] * (BAUD / 4)).reshape(-1)
+        q = 2 * np.arange(self.nsub) - (self.dec.nb - 1)
+        self.freqs_fine = (self.freqs[:, None] + q[None, :] * (m.BAUD / 4)).reshape(-1)
         self.circular = self.nk == self.M
         self.records = []
         self._pending, self._recent = [], []
@@ -296,16 +303,17 @@ class FT8_Skimmer(Skimmer):
 
     def _release(self):
         """the events whose rivals have all arrived: the owners among them, with their soft bits"""
-        done = self.dec.t_done
-        ripe = [e for e in self._pending if e[0] + HOLD <= done]
+        m = self.DECODERS.MODE
+        done, hold = self.dec.t_done, m.HOLD
+        ripe = [e for e in self._pending if e[0] + hold <= done]
         if not ripe:
             return []
         pool = self._recent + self._pending
         own = owners(pool, nfine=self.nfine if self.circular else None)
-        out = [e for e, o in zip(pool, own) if o and e in ripe and e[0] + HOLD <= done]
+        out = [e for e, o in zip(pool, own) if o and e in ripe and e[0] + hold <= done]
         first = min(e[0] for e in ripe)
         self._recent = [e for e in self._recent if e[0] >= first - 16] + ripe
-        self._pending = [e for e in self._pending if e[0] + HOLD > done]
+        self._pending = [e for e in self._pending if e[0] + hold > done]
         out.sort(key=lambda e: (e[0], e[1]))
         if not out:
             return []
@@ -315,13 +323,13 @@ class FT8_Skimmer(Skimmer):
             rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits, llr=soft)
             if self.t_first is not None:
                 T = float(self.t_first) + rec["time"]
-                rec["slot"] = int(np.floor(T / SLOT_SECONDS))
-                rec["dt"] = T - SLOT_SECONDS * rec["slot"] - NOMINAL_START
+                rec["slot"] = int(np.floor(T / m.SLOT_SECONDS))
+                rec["dt"] = T - m.SLOT_SECONDS * rec["slot"] - m.NOMINAL_START
             recs.append(rec)
         return recs
 
     def push(self, x):
-        """complex64 [n] -> the records of the frames whose step t0 + 320 this input completes, owners only, sorted by
+        """complex64 [n] -> the records of the frames whose step t0 + HOLD - 1 this input completes, owners only, sorted by
         (t0, F).  ``records`` gains them.  The input goes through in calls of at most ``dec.max_samples()``."""
         x = np.ascontiguousarray(x, np.complex64)
         out, i = [], 0
