@@ -631,6 +631,40 @@ int  pysdr_ft4_fetch(pysdr_ft4* ft4, const int* rows, int nrows, int32_t* events
 int  pysdr_ft4_llr(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, float* out);
 int  pysdr_ft4_state(pysdr_ft4* ft4, float* sc, int32_t* hits, float* ring, long long* t_done);
 
+/* ---- LDPC(174,91), CRC-14: the back half of the FT8 and FT4 skimmers ---------------------------
+ * Normalised min-sum on a flooding schedule over the 83 sparse checks (degree 6 or 7, every column in 3), one workgroup
+ * of 192 threads per candidate, float32 with every operation rounded on its own.  Soft bits are positive for bit 1 and
+ * need no scaling: the decoder works on L = -llr, messages c start at +0, and for k = 0, 1, ..: tot[n] = ((L[n] + c[e0]) +
+ * c[e1]) + c[e2] over the column's edges in ascending check order; hard[n] = tot[n] < 0; every check even: stop, a
+ * codeword after `iterations` = k; k == iters: stop, no codeword; else v[e] = L[n] + the two other messages into n in
+ * ascending check order and c[e] = s * (alpha * min |v| over the check's other edges), s the product of the other edges'
+ * signs (v < 0 is negative, +0 and -0 positive) applied by negation (a zero minimum under a negative sign is -0).
+ * Per candidate: status[4] = {status, iterations, nerr, 0} -- status 2: a codeword whose 14 CRC bits match (polynomial
+ * 0x2757 over the 77 message bits and five zeros, zero start, no reflection, no final XOR) and whose message is not all
+ * zero; 1: any other codeword; 0: none; nerr: positions where llr > 0 differs from the final hard bit -- bits[12]: the
+ * first 91 final hard bits, MSB first, 5 zero bits of padding, filled for every status; post (or NULL) [174]: the final tot.
+ * pysdr_ldpc_plan needs no device: PYSDR_ERR_ARG for a NULL cfg, iters outside [1, 200] or alpha not in (0, 1] (a NaN
+ * is not), else out = {threads per candidate, LDS bytes, candidates per call (4096), iters}.
+ * pysdr_ft8_decode / pysdr_ft4_decode: the candidates (F[i], t0[i]) of pysdr_ft8_llr / pysdr_ft4_llr, under its rules
+ * and refusals, decoded from the spectrum ring: the soft bits never reach memory.  status [n][4], bits [n][12], post
+ * [n][174] or NULL are host arrays.  A bad candidate, n outside [0, 4096], a bad cfg or a NULL array: nothing is launched,
+ * no output changes.
+ * pysdr_ft8_decode_llr / pysdr_ft4_decode_llr: host soft bits llr [n][174]; a value that is not finite is refused
+ * (PYSDR_ERR_ARG) before any launch.  Runs on the skimmer's stream through its soft-bit buffer. */
+typedef struct pysdr_ldpc_cfg {
+  int32_t iters;            /* most iterations, [1, 200] */
+  float alpha;              /* the normalisation, (0, 1] */
+} pysdr_ldpc_cfg;
+int  pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]);
+int  pysdr_ft8_decode(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                      uint8_t* bits, float* post);
+int  pysdr_ft8_decode_llr(pysdr_ft8* ft8, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                          float* post);
+int  pysdr_ft4_decode(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                      uint8_t* bits, float* post);
+int  pysdr_ft4_decode_llr(pysdr_ft4* ft4, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                          float* post);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -60,6 +60,10 @@ class Ft4Cfg(C.Structure):
     _fields_ = [("smin", C.c_float), ("hmin", C.c_int32), ("pmax", C.c_float)]
 
 
+class LdpcCfg(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("alpha", C.c_float)]
+
+
 class FskCfg(C.Structure):
     _fields_ = [("a_q", C.c_float), ("a_b", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("bal", C.c_float),
                 ("pmax", C.c_float), ("n0", C.c_int32)]
@@ -194,6 +198,9 @@ PROTOTYPES = {
     "pysdr_ft8_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
     "pysdr_ft8_llr": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
     "pysdr_ft8_state": (_i, [_vp, _pf, C.POINTER(C.c_int32), _pf, C.POINTER(C.c_longlong)]),
+    "pysdr_ft8_decode": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_uint8), _pf]),
+    "pysdr_ft8_decode_llr": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf]),
     "pysdr_ft4_plan": (_i, [_i, _i, _i, C.POINTER(Ft4Cfg), C.POINTER(C.c_int32)]),
     "pysdr_ft4_create": (_i, [_vp, _i, C.POINTER(Ft4Cfg), _pf, _i, C.POINTER(_vp)]),
     "pysdr_ft4_destroy": (None, [_vp]),
@@ -204,6 +211,10 @@ PROTOTYPES = {
     "pysdr_ft4_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
     "pysdr_ft4_llr": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
     "pysdr_ft4_state": (_i, [_vp, _pf, C.POINTER(C.c_int32), _pf, C.POINTER(C.c_longlong)]),
+    "pysdr_ft4_decode": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_uint8), _pf]),
+    "pysdr_ft4_decode_llr": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf]),
+    "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), C.POINTER(C.c_int32)]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

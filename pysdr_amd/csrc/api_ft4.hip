@@ -5,6 +5,7 @@
 // (host_res.h): deleting the object frees it.
 #include "chan_client.h"
 #include "ft4_plan.h"
+#include "ldpc_host.h"
 
 using namespace pysdr;
 
@@ -24,6 +25,7 @@ struct pysdr_ft4 : ChanClient {
   DevBuf<float> d_llr;              // [kFt4LlrMax][174]
   std::vector<float> h_tw;
   std::vector<int32_t> h_cand;
+  LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
 };
 
 namespace {
@@ -199,6 +201,15 @@ int pysdr_ft4_llr(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, fl
   PYSDR_HIP_CHECK(hipMemcpyAsync(out, a.out, (size_t)n * kFt4Bits * sizeof(float), hipMemcpyDeviceToHost, st));
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   return PYSDR_OK;
+}
+
+int pysdr_ft4_decode(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                     float* post) {
+  return ldpc_decode_ring(w, "pysdr_ft4_decode", kLdpcFromFt4Ring, ft4_llr_ok, kFt4Lag, F, t0, n, cfg, status, bits, post);
+}
+
+int pysdr_ft4_decode_llr(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+  return ldpc_decode_llr(w, "pysdr_ft4_decode_llr", llr, n, cfg, status, bits, post);
 }
 
 int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {

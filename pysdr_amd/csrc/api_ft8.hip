@@ -5,6 +5,7 @@
 // frees it.
 #include "chan_client.h"
 #include "ft8_plan.h"
+#include "ldpc_host.h"
 
 using namespace pysdr;
 
@@ -24,6 +25,7 @@ struct pysdr_ft8 : ChanClient {
   DevBuf<float> d_llr;              // [kFt8LlrMax][174]
   std::vector<float> h_tw;
   std::vector<int32_t> h_cand;
+  LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
 };
 
 namespace {
@@ -198,6 +200,25 @@ int pysdr_ft8_llr(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, fl
   if (rc) return rc;
   PYSDR_HIP_CHECK(hipMemcpyAsync(out, a.out, (size_t)n * kFt8Bits * sizeof(float), hipMemcpyDeviceToHost, st));
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  return PYSDR_OK;
+}
+
+int pysdr_ft8_decode(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                     float* post) {
+  return ldpc_decode_ring(w, "pysdr_ft8_decode", kLdpcFromFt8Ring, ft8_llr_ok, kFt8Lag, F, t0, n, cfg, status, bits, post);
+}
+
+int pysdr_ft8_decode_llr(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+  return ldpc_decode_llr(w, "pysdr_ft8_decode_llr", llr, n, cfg, status, bits, post);
+}
+
+int pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_ldpc_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!ldpc_cfg_ok(cfg)) {
+    set_last_error("pysdr_ldpc_plan: a cfg outside the rules (NULL; iters in [1, %d]; alpha finite and in (0, 1])", kLdpcItersMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kLdpcThreads; out[1] = kLdpcLdsBytes; out[2] = kLdpcMax; out[3] = cfg->iters;
   return PYSDR_OK;
 }
 

@@ -204,4 +204,8 @@ struct Ft4LlrArgs;
 int launch_ft4_steps(int S, const Ft4Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
 int launch_ft4_llr(const Ft4LlrArgs& a, hipStream_t st);
 
+// ---- LDPC(174,91) decoder (ldpc.hip, host half ldpc_host.h; tables, steps and kernel arguments: ldpc_plan.h) -----------
+struct LdpcArgs;
+int launch_ldpc_decode(int source, const LdpcArgs& a, hipStream_t st);   // source: LdpcSource
+
 }  // namespace pysdr

@@ -2,8 +2,9 @@
 half ``api_ft4.hip``).  4-GFSK at 125 / 6 baud, tones one baud apart, 103 symbols of which 16 are four different Costas
 arrays.  A channelizer with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders
 run on the device, one every 10.4 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The
-device finds every frame by its sync score and hands out its 174 soft bits in transmission order; LDPC, CRC, the bit
-scrambler and message text are not here.  The decoder bank and the skimmer are ``ft8.py``'s, told this mode's constants,
+device finds every frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` it
+also runs the LDPC(174,91) decoder and the CRC-14 on them and a record carries ``ok`` and the 77
+bits as decoded; the bit scrambler FT4 applies before the CRC is not here, so ``text`` is None.  The decoder bank and the skimmer are ``ft8.py``'s, told this mode's constants,
 settings, plan and tables; the finder and the soft bits' helpers are ``ft8.py``'s as they are."""
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ KEEP = 9
 SHAPES = (48, 72)                                # row samples per symbol
 NB_EXTRA = 6                                     # NB = NSUB + 6: decoder j uses bins j + 2 tone, tone 0 to 3
 LLR_MAX = 4096
+UNPACK = None                                    # FT4 XORs its 77 bits with a fixed scrambler before the CRC; that vector is not here
 
 
 def shape(fs):

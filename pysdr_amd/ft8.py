@@ -2,9 +2,10 @@
 ``api_ft8.hip``).  8-FSK at 6.25 baud, tones 6.25 Hz apart, 79 symbols of which 21 are three Costas arrays.  A channelizer
 with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders run on the device, one
 every 3.125 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The device finds every
-frame by its sync score and hands out its 174 soft bits in transmission order, ready for any LDPC(174,91) decoder; LDPC,
-CRC and message text are not here.  The tables and settings are derived here, once, and handed to the library already
-derived."""
+frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` the device also runs
+the LDPC(174,91) decoder on them, straight from the spectrum ring, checks the CRC-14, and the record carries the message's
+77 bits and its text (``ldpc.py``, ``ft8msg.py``).  The tables and settings are derived here, once, and
+handed to the library already derived."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +15,8 @@ import numpy as np
 
 from . import _lib
 from . import channelizer as _chan
+from . import ft8msg as _msg
+from . import ldpc as _ldpc
 from . import psk as _psk
 from ._lib import Ft8Cfg
 from .channelizer import Channelizer
@@ -32,6 +35,7 @@ KEEP = 9
 SHAPES = (64, 96)                                # row samples per symbol
 NB_EXTRA = 14                                    # NB = NSUB + 14: decoder j uses bins j + 2 tone, tone 0 to 7
 LLR_MAX = 4096
+UNPACK = _msg.unpack77                           # the 77 decoded bits -> text (``ft4.py``: None, its scrambler is not here)
 
 
 def shape(fs):
@@ -235,6 +239,45 @@ class FT8_Decoders(DecoderBank):
             self._call("llr", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), _lib.as_pf(o))
         return out
 
+    def _decoded(self, n, post):
+        return (np.zeros((n, 4), np.int32), np.zeros((n, 12), np.uint8), np.zeros((n, self.MODE.BITS), np.float32) if post else None)
+
+    @staticmethod
+    def _answer(st, bits, post):
+        out = dict(status=st[:, 0].copy(), iterations=st[:, 1].copy(), nerr=st[:, 2].copy(), bits=_ldpc.unpack_bits(bits))
+        if post is not None:
+            out["post"] = post
+        return out
+
+    def decode(self, F, t0, cfg=None, post=False):
+        """The candidates (F[i], t0[i]) of ``llr``, under its rules, through the LDPC decoder on the device, straight from
+        the spectrum ring (``cfg``: ``ldpc.params()``).  -> dict of status int32 [n] (2: a codeword with
+        a good CRC and a message that is not all zero, 1: any other codeword, 0: none), iterations, nerr (hard bits the
+        decoder changed), bits uint8 [n][91] (the message's 77 and the CRC's 14, whatever the status) and, with ``post``,
+        post float32 [n][174], the decoder's final sums."""
+        F = np.ascontiguousarray(F, np.int32)
+        t0 = np.ascontiguousarray(t0, np.int64)
+        cfg = _ldpc.params() if cfg is None else cfg
+        st, bits, po = self._decoded(len(F), post)
+        for i in range(0, len(F), LLR_MAX):
+            f, t = F[i:i + LLR_MAX], t0[i:i + LLR_MAX]
+            self._call("decode", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), C.byref(cfg),
+                       st[i:].ctypes.data_as(C.POINTER(C.c_int32)), bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)),
+                       None if po is None else _lib.as_pf(po[i:]))
+        return self._answer(st, bits, po)
+
+    def decode_llr(self, llr, cfg=None, post=False):
+        """Soft bits from the host, float32 [n][174], positive for bit 1, any scale -> ``decode``'s answer.  In calls of
+        4096; a value that is not finite is refused."""
+        llr = np.ascontiguousarray(llr, np.float32).reshape(-1, self.MODE.BITS)
+        cfg = _ldpc.params() if cfg is None else cfg
+        st, bits, po = self._decoded(len(llr), post)
+        for i in range(0, len(llr), LLR_MAX):
+            v = llr[i:i + LLR_MAX]
+            self._call("decode_llr", _lib.as_pf(v), len(v), C.byref(cfg), st[i:].ctypes.data_as(C.POINTER(C.c_int32)),
+                       bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)), None if po is None else _lib.as_pf(po[i:]))
+        return self._answer(st, bits, po)
+
     def state(self, ring=False):
         """dict of sc float32 [9][nfine] and hits int32 [9][nfine] (frame start t at index t mod 9), t_done, and with
         ``ring`` the spectrum ring float32 [nk][TR][NB] (step t at index t mod TR)"""
@@ -253,13 +296,22 @@ class FT8_Skimmer(Skimmer):
     """Wideband IQ at ``fs`` -> a channelizer of M = 4 D rows S baud / 4 apart at S baud samples per second -> NSUB = S / 2
     sync decoders inside every row, fine row F with tone 0 at ``freqs_fine[F]`` Hz (signed) -> a record for every frame
     found: ``t0`` (steps of a quarter symbol since create / reset), ``F``, ``freq``, ``time`` (seconds into the stream),
-    ``score``, ``hits`` and ``llr`` float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` and ``dt``."""
+    ``score``, ``hits`` and ``llr`` float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` and ``dt``.
+    With ``decode=True`` the owners go through the LDPC decoder on the device (``ldpc``: ``ldpc.params()``) and a record
+    gains ``status``, ``ok`` (status 2), ``iterations``, ``nerr``, ``bits77``, ``i3``, ``n3`` and ``text`` (None where the
+    frame did not decode or its message type is not unpacked); ``keep_llr=False`` then skips the soft bits' download and
+    the records carry no ``llr``."""
 
     DECODERS = FT8_Decoders                                              # the bank; its MODE is the skimmer's too
 
-    def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None):
+    def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None, decode=False, ldpc=None,
+                 keep_llr=True):
         m = self.DECODERS.MODE
         self.fs, self.baud, self.t_first = float(fs), m.BAUD, t_first
+        self.decode, self.keep_llr = bool(decode), bool(keep_llr) or not decode
+        self.ldpc = (_ldpc.params() if ldpc is None else ldpc) if decode else None
+        if decode:
+            _ldpc.plan(self.ldpc)                                        # a bad setting fails here, with or without a device
         if chan is None:
             self.S, self.D, self.M = m.shape(fs)
             nk = self.M if channels is None else int(channels[1])
@@ -317,10 +369,20 @@ class FT8_Skimmer(Skimmer):
         out.sort(key=lambda e: (e[0], e[1]))
         if not out:
             return []
-        llr = self.dec.llr([e[1] for e in out], [e[0] for e in out])
+        Fs, ts = [e[1] for e in out], [e[0] for e in out]
+        llr = self.dec.llr(Fs, ts) if self.keep_llr else None
+        dec = self.dec.decode(Fs, ts, self.ldpc) if self.decode else None
         recs = []
-        for (t0, F, score, hits), soft in zip(out, llr):
-            rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits, llr=soft)
+        for k, (t0, F, score, hits) in enumerate(out):
+            rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits)
+            if llr is not None:
+                rec["llr"] = llr[k]
+            if dec is not None:
+                b77 = dec["bits"][k, :77].copy()
+                i3, n3 = _msg.types(b77)
+                ok = int(dec["status"][k]) == _ldpc.STATUS_OK
+                rec.update(status=int(dec["status"][k]), ok=ok, iterations=int(dec["iterations"][k]), nerr=int(dec["nerr"][k]), bits77=b77,
+                           i3=i3, n3=n3, text=m.UNPACK(b77) if ok and m.UNPACK is not None else None)
             if self.t_first is not None:
                 T = float(self.t_first) + rec["time"]
                 rec["slot"] = int(np.floor(T / m.SLOT_SECONDS))
