@@ -665,6 +665,36 @@ int  pysdr_ft4_decode(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int
 int  pysdr_ft4_decode_llr(pysdr_ft4* ft4, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                           float* post);
 
+/* ---- Ordered-statistics decoding behind min-sum -------------------------------------------------
+ * A second stage for the candidates min-sum left without a message (status != 2), on the same channel soft bits x:
+ * r = |x|, h = x > 0; the positions ranked by descending r, ties by ascending position; the most reliable basis (the
+ * first 91 ranks whose generator columns are independent, `last` the 91st); G', the generator whose columns at those
+ * ranks are the identity; e0 = (the re-encoding of h on the basis) xor h; the patterns k = 0: e0; 1 + i: e0 xor G'[i];
+ * 92 + the place of (i, j), i < j, in lexicographic order: e0 xor G'[i] xor G'[j] -- 1, 92 or 4187 of them for order 0,
+ * 1, 2; a pattern's distance is the float32 sum, in rank order, of r where its bit is set; the least (distance, k) wins.
+ * If the winner's word h xor pattern has a matching CRC-14 and a message that is not all zero, the candidate becomes
+ * status 2 with the word's first 91 bits and nerr = the pattern's weight; iterations and post stay min-sum's.  THE CRC IS
+ * THE ONLY GUARD: a candidate that reaches this stage comes out as a false message with probability about 2^-14.
+ * status[3] is 0 where the stage did not run, else 1, 2, 3 for a winner k = 0, k in 1..91, k >= 92, accepted or not.
+ * detail (or NULL) [n][4]: {k, last, the pattern's weight, the bits of the float32 distance}, or {-1, -1, -1, 0} where
+ * the stage did not run.  One wavefront per candidate, launched behind min-sum on the skimmer's stream.
+ * pysdr_osd_plan needs no device: PYSDR_ERR_ARG for a NULL cfg or out or an order outside [0, 2], else out = {threads
+ * per candidate, LDS bytes, patterns, candidates per call}.  The four calls are pysdr_*_decode / pysdr_*_decode_llr with
+ * their rules and refusals, plus PYSDR_ERR_ARG for a NULL or bad osd cfg; a refusal launches nothing and changes no
+ * output. */
+typedef struct pysdr_osd_cfg {
+  int32_t order;            /* rows of G' flipped at once, [0, 2] */
+} pysdr_osd_cfg;
+int  pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]);
+int  pysdr_ft8_decode_osd(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+int  pysdr_ft8_decode_llr_osd(pysdr_ft8* ft8, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                              float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+int  pysdr_ft4_decode_osd(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+int  pysdr_ft4_decode_llr_osd(pysdr_ft4* ft4, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                              float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -64,6 +64,10 @@ class LdpcCfg(C.Structure):
     _fields_ = [("iters", C.c_int32), ("alpha", C.c_float)]
 
 
+class OsdCfg(C.Structure):
+    _fields_ = [("order", C.c_int32)]
+
+
 class FskCfg(C.Structure):
     _fields_ = [("a_q", C.c_float), ("a_b", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("bal", C.c_float),
                 ("pmax", C.c_float), ("n0", C.c_int32)]
@@ -215,6 +219,15 @@ PROTOTYPES = {
                               C.POINTER(C.c_uint8), _pf]),
     "pysdr_ft4_decode_llr": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), C.POINTER(C.c_int32)]),
+    "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
+    "pysdr_ft8_decode_osd": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
+    "pysdr_ft8_decode_llr_osd": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg),
+                                      C.POINTER(C.c_int32)]),
+    "pysdr_ft4_decode_osd": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
+                                  C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
+    "pysdr_ft4_decode_llr_osd": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg),
+                                      C.POINTER(C.c_int32)]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -212,6 +212,17 @@ int pysdr_ft4_decode_llr(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc
   return ldpc_decode_llr(w, "pysdr_ft4_decode_llr", llr, n, cfg, status, bits, post);
 }
 
+int pysdr_ft4_decode_osd(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                         uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_ring(w, "pysdr_ft4_decode_osd", kLdpcFromFt4Ring, ft4_llr_ok, kFt4Lag, F, t0, n, cfg, status, bits, post,
+                          OsdCall{true, osd, detail});
+}
+
+int pysdr_ft4_decode_llr_osd(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                             float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_llr(w, "pysdr_ft4_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+
 int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
   if (!w) { set_last_error("pysdr_ft4_state: NULL skimmer"); return PYSDR_ERR_ARG; }
   std::lock_guard<std::mutex> lk(w->mu);

@@ -212,6 +212,17 @@ int pysdr_ft8_decode_llr(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc
   return ldpc_decode_llr(w, "pysdr_ft8_decode_llr", llr, n, cfg, status, bits, post);
 }
 
+int pysdr_ft8_decode_osd(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                         uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_ring(w, "pysdr_ft8_decode_osd", kLdpcFromFt8Ring, ft8_llr_ok, kFt8Lag, F, t0, n, cfg, status, bits, post,
+                          OsdCall{true, osd, detail});
+}
+
+int pysdr_ft8_decode_llr_osd(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                             float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_llr(w, "pysdr_ft8_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+
 int pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]) {
   if (!out) { set_last_error("pysdr_ldpc_plan: out is NULL"); return PYSDR_ERR_ARG; }
   if (!ldpc_cfg_ok(cfg)) {
@@ -219,6 +230,16 @@ int pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]) {
     return PYSDR_ERR_ARG;
   }
   out[0] = kLdpcThreads; out[1] = kLdpcLdsBytes; out[2] = kLdpcMax; out[3] = cfg->iters;
+  return PYSDR_OK;
+}
+
+int pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_osd_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!osd_cfg_ok(cfg)) {
+    set_last_error("pysdr_osd_plan: a cfg outside the rule (NULL; order in [0, %d])", kOsdOrderMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kOsdThreads; out[1] = kOsdLdsBytes; out[2] = osd_patterns(cfg->order); out[3] = kLdpcMax;
   return PYSDR_OK;
 }
 

@@ -1,11 +1,13 @@
 // The host half of the LDPC decoder, shared by the FT8 and the FT4 skimmer (api_ft8.hip, api_ft4.hip) over chan_client.h:
 // the result buffers a skimmer owns, and the two calls -- candidates from the spectrum ring, soft bits from the host --
-// written once for both objects, which name their fields alike (plan, t_done, d_ring, d_cand, h_cand, d_llr).  Every
+// written once for both objects, which name their fields alike (plan, t_done, d_ring, d_cand, h_cand, d_llr).  A call may
+// ask for the second stage, ordered-statistics decoding (osd.hip), launched behind min-sum on the same stream.  Every
 // check comes before any launch: a refusal changes nothing.  Host only; not part of the public ABI.
 #pragma once
 
 #include "chan_client.h"
 #include "ldpc_plan.h"
+#include "osd_plan.h"
 
 namespace pysdr {
 
@@ -13,6 +15,7 @@ struct LdpcBufs {                   // allocated by the first decode call of a s
   DevBuf<int32_t> d_status;         // [kLdpcMax][4]
   DevBuf<uint8_t> d_bits;           // [kLdpcMax][12]
   DevBuf<float> d_post;             // [kLdpcMax][174]
+  DevBuf<int32_t> d_detail;         // [kLdpcMax][4]: the second stage's (osd_plan.h)
   bool ready = false;
 };
 
@@ -21,6 +24,7 @@ inline int ldpc_bufs_ready(LdpcBufs* b) {
   PYSDR_HIP_CHECK(b->d_status.alloc((size_t)kLdpcMax * kLdpcStatusWords));
   PYSDR_HIP_CHECK(b->d_bits.alloc((size_t)kLdpcMax * kLdpcBitsBytes));
   PYSDR_HIP_CHECK(b->d_post.alloc((size_t)kLdpcMax * kLdpcN));
+  PYSDR_HIP_CHECK(b->d_detail.alloc((size_t)kLdpcMax * kOsdDetailWords));
   b->ready = true;
   return PYSDR_OK;
 }
@@ -38,15 +42,38 @@ inline bool ldpc_call_ok(const char* who, int n, const pysdr_ldpc_cfg* cfg, cons
   return true;
 }
 
+// The second stage of a call: none for the calls without it; the *_osd calls need a cfg inside the rule.
+struct OsdCall {
+  bool wanted;
+  const pysdr_osd_cfg* cfg;
+  int32_t* detail;                  // host [n][4] or NULL
+};
+constexpr OsdCall kNoOsd{false, nullptr, nullptr};
+
+inline bool osd_call_ok(const char* who, const OsdCall& osd) {
+  if (!osd.wanted || osd_cfg_ok(osd.cfg)) return true;
+  set_last_error("%s: an osd cfg outside the rule (NULL; order in [0, %d])", who, kOsdOrderMax);
+  return false;
+}
+
 // the launch and the way back, under the skimmer's lock, its device set
 template <class W>
-int ldpc_run(W* w, int source, LdpcArgs& a, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+int ldpc_run(W* w, int source, LdpcArgs& a, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post, const OsdCall& osd) {
   hipStream_t st = w->stream;
   a.iters = cfg->iters; a.alpha = cfg->alpha;
   a.status = w->ldpc.d_status.get(); a.bits = w->ldpc.d_bits.get(); a.post = post ? w->ldpc.d_post.get() : nullptr;
   const int rc = launch_ldpc_decode(source, a, st);
   if (rc) return rc;
   const size_t n = (size_t)a.n;
+  if (osd.wanted) {                                                    // behind min-sum on the same stream, before the copies back
+    OsdArgs o{};
+    o.llr = a.llr; o.ring = a.ring; o.tr = a.tr; o.nb = a.nb; o.nsub = a.nsub; o.cand = a.cand; o.n = a.n; o.order = osd.cfg->order;
+    o.status = a.status; o.bits = a.bits; o.detail = osd.detail ? w->ldpc.d_detail.get() : nullptr;
+    const int rc2 = launch_osd_decode(source, o, st);
+    if (rc2) return rc2;
+    if (osd.detail)
+      PYSDR_HIP_CHECK(hipMemcpyAsync(osd.detail, o.detail, n * kOsdDetailWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  }
   PYSDR_HIP_CHECK(hipMemcpyAsync(status, a.status, n * kLdpcStatusWords * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   PYSDR_HIP_CHECK(hipMemcpyAsync(bits, a.bits, n * kLdpcBitsBytes, hipMemcpyDeviceToHost, st));
   if (post) PYSDR_HIP_CHECK(hipMemcpyAsync(post, a.post, n * kLdpcN * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -58,9 +85,9 @@ int ldpc_run(W* w, int source, LdpcArgs& a, const pysdr_ldpc_cfg* cfg, int32_t* 
 // last step of a frame behind its first, for the message.
 template <class W, class Ok>
 int ldpc_decode_ring(W* w, const char* who, int source, Ok ok, int lag, const int32_t* F, const long long* t0, int n,
-                     const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+                     const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post, const OsdCall& osd = kNoOsd) {
   if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
-  if (!ldpc_call_ok(who, n, cfg, F, t0, status, bits)) return PYSDR_ERR_ARG;
+  if (!ldpc_call_ok(who, n, cfg, F, t0, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   std::lock_guard<std::mutex> lk(w->mu);
   const long long done = (long long)w->t_done;
   for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
@@ -81,15 +108,15 @@ int ldpc_decode_ring(W* w, const char* who, int source, Ok ok, int lag, const in
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   LdpcArgs a{};
   a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.cand = w->d_cand.get(); a.n = n;
-  return ldpc_run(w, source, a, cfg, status, bits, post);
+  return ldpc_run(w, source, a, cfg, status, bits, post, osd);
 }
 
 // Soft bits from the host, through the skimmer's soft-bit buffer.
 template <class W>
 int ldpc_decode_llr(W* w, const char* who, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
-                    float* post) {
+                    float* post, const OsdCall& osd = kNoOsd) {
   if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
-  if (!ldpc_call_ok(who, n, cfg, llr, llr, status, bits)) return PYSDR_ERR_ARG;
+  if (!ldpc_call_ok(who, n, cfg, llr, llr, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   const long long bad = ldpc_first_nonfinite(llr, (size_t)n * kLdpcN);
   if (bad >= 0) {
     set_last_error("%s: soft bit %lld of candidate %lld is not finite", who, bad % kLdpcN, bad / kLdpcN);
@@ -104,7 +131,7 @@ int ldpc_decode_llr(W* w, const char* who, const float* llr, int n, const pysdr_
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_llr.get(), llr, (size_t)n * kLdpcN * sizeof(float), hipMemcpyHostToDevice, st));
   LdpcArgs a{};
   a.llr = w->d_llr.get(); a.n = n;
-  return ldpc_run(w, kLdpcFromBuffer, a, cfg, status, bits, post);
+  return ldpc_run(w, kLdpcFromBuffer, a, cfg, status, bits, post, osd);
 }
 
 }  // namespace pysdr

@@ -208,4 +208,8 @@ int launch_ft4_llr(const Ft4LlrArgs& a, hipStream_t st);
 struct LdpcArgs;
 int launch_ldpc_decode(int source, const LdpcArgs& a, hipStream_t st);   // source: LdpcSource
 
+// ---- ordered-statistics decoding behind it (osd.hip; steps and kernel arguments: osd_plan.h) -----------------------------
+struct OsdArgs;
+int launch_osd_decode(int source, const OsdArgs& a, hipStream_t st);     // source: LdpcSource, the min-sum launch's
+
 }  // namespace pysdr

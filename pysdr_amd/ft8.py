@@ -243,40 +243,65 @@ class FT8_Decoders(DecoderBank):
         return (np.zeros((n, 4), np.int32), np.zeros((n, 12), np.uint8), np.zeros((n, self.MODE.BITS), np.float32) if post else None)
 
     @staticmethod
-    def _answer(st, bits, post):
+    def _answer(st, bits, post, osd=None, detail=None):
         out = dict(status=st[:, 0].copy(), iterations=st[:, 1].copy(), nerr=st[:, 2].copy(), bits=_ldpc.unpack_bits(bits))
         if post is not None:
             out["post"] = post
+        if osd is not None:
+            out["osd"] = st[:, 3].copy()
+        if detail is not None:
+            out["detail"] = detail
         return out
 
-    def decode(self, F, t0, cfg=None, post=False):
+    @staticmethod
+    def _osd(osd, detail, n):
+        """-> (the OsdCfg or None, the detail array or None)"""
+        osd = _ldpc.osd_cfg(osd)
+        if osd is None and detail:
+            raise ValueError("detail is the second stage's: it needs osd")
+        return osd, np.zeros((n, 4), np.int32) if detail else None
+
+    def decode(self, F, t0, cfg=None, post=False, osd=None, detail=False):
         """The candidates (F[i], t0[i]) of ``llr``, under its rules, through the LDPC decoder on the device, straight from
         the spectrum ring (``cfg``: ``ldpc.params()``).  -> dict of status int32 [n] (2: a codeword with
         a good CRC and a message that is not all zero, 1: any other codeword, 0: none), iterations, nerr (hard bits the
         decoder changed), bits uint8 [n][91] (the message's 77 and the CRC's 14, whatever the status) and, with ``post``,
-        post float32 [n][174], the decoder's final sums."""
+        post float32 [n][174], the decoder's final sums.  With ``osd`` (an order 0 to 2 or ``ldpc.osd_params()``) the
+        candidates min-sum left without a message go through ordered-statistics decoding in a second launch (DESIGN.md 3
+        item 25) and the answer gains osd int32 [n] (0: the stage did not run; 1, 2, 3: it did and no, one or two rows of
+        the basis were flipped) and, with ``detail``, detail int32 [n][4] (k, last, weight, the distance's bits)."""
         F = np.ascontiguousarray(F, np.int32)
         t0 = np.ascontiguousarray(t0, np.int64)
         cfg = _ldpc.params() if cfg is None else cfg
+        osd, de = self._osd(osd, detail, len(F))
         st, bits, po = self._decoded(len(F), post)
         for i in range(0, len(F), LLR_MAX):
             f, t = F[i:i + LLR_MAX], t0[i:i + LLR_MAX]
-            self._call("decode", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), C.byref(cfg),
-                       st[i:].ctypes.data_as(C.POINTER(C.c_int32)), bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)),
-                       None if po is None else _lib.as_pf(po[i:]))
-        return self._answer(st, bits, po)
+            args = (f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), C.byref(cfg),
+                    st[i:].ctypes.data_as(C.POINTER(C.c_int32)), bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)),
+                    None if po is None else _lib.as_pf(po[i:]))
+            if osd is None:
+                self._call("decode", *args)
+            else:
+                self._call("decode_osd", *args, C.byref(osd), None if de is None else de[i:].ctypes.data_as(C.POINTER(C.c_int32)))
+        return self._answer(st, bits, po, osd, de)
 
-    def decode_llr(self, llr, cfg=None, post=False):
+    def decode_llr(self, llr, cfg=None, post=False, osd=None, detail=False):
         """Soft bits from the host, float32 [n][174], positive for bit 1, any scale -> ``decode``'s answer.  In calls of
         4096; a value that is not finite is refused."""
         llr = np.ascontiguousarray(llr, np.float32).reshape(-1, self.MODE.BITS)
         cfg = _ldpc.params() if cfg is None else cfg
+        osd, de = self._osd(osd, detail, len(llr))
         st, bits, po = self._decoded(len(llr), post)
         for i in range(0, len(llr), LLR_MAX):
             v = llr[i:i + LLR_MAX]
-            self._call("decode_llr", _lib.as_pf(v), len(v), C.byref(cfg), st[i:].ctypes.data_as(C.POINTER(C.c_int32)),
-                       bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)), None if po is None else _lib.as_pf(po[i:]))
-        return self._answer(st, bits, po)
+            args = (_lib.as_pf(v), len(v), C.byref(cfg), st[i:].ctypes.data_as(C.POINTER(C.c_int32)),
+                    bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)), None if po is None else _lib.as_pf(po[i:]))
+            if osd is None:
+                self._call("decode_llr", *args)
+            else:
+                self._call("decode_llr_osd", *args, C.byref(osd), None if de is None else de[i:].ctypes.data_as(C.POINTER(C.c_int32)))
+        return self._answer(st, bits, po, osd, de)
 
     def state(self, ring=False):
         """dict of sc float32 [9][nfine] and hits int32 [9][nfine] (frame start t at index t mod 9), t_done, and with
@@ -300,18 +325,26 @@ class FT8_Skimmer(Skimmer):
     With ``decode=True`` the owners go through the LDPC decoder on the device (``ldpc``: ``ldpc.params()``) and a record
     gains ``status``, ``ok`` (status 2), ``iterations``, ``nerr``, ``bits77``, ``i3``, ``n3`` and ``text`` (None where the
     frame did not decode or its message type is not unpacked); ``keep_llr=False`` then skips the soft bits' download and
-    the records carry no ``llr``."""
+    the records carry no ``llr``.  ``osd=2`` (an order 0 to 2, or ``ldpc.osd_params()``) sends the frames min-sum could not
+    decode through ordered-statistics decoding and a record gains ``osd``: 0, the stage did not
+    run; 1, 2, 3, it did.  Off by default: the CRC-14 is that stage's only guard, and a frame that reaches it comes out as
+    a false message with probability about 2^-14."""
 
     DECODERS = FT8_Decoders                                              # the bank; its MODE is the skimmer's too
 
     def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None, decode=False, ldpc=None,
-                 keep_llr=True):
+                 keep_llr=True, osd=None):
         m = self.DECODERS.MODE
         self.fs, self.baud, self.t_first = float(fs), m.BAUD, t_first
         self.decode, self.keep_llr = bool(decode), bool(keep_llr) or not decode
         self.ldpc = (_ldpc.params() if ldpc is None else ldpc) if decode else None
+        self.osd = _ldpc.osd_cfg(osd)
+        if self.osd is not None and not decode:
+            raise ValueError(f"{type(self).__name__}: osd is a stage of the decoder: it needs decode=True")
         if decode:
             _ldpc.plan(self.ldpc)                                        # a bad setting fails here, with or without a device
+        if self.osd is not None:
+            _ldpc.osd_plan(self.osd)
         if chan is None:
             self.S, self.D, self.M = m.shape(fs)
             nk = self.M if channels is None else int(channels[1])
@@ -371,7 +404,7 @@ class FT8_Skimmer(Skimmer):
             return []
         Fs, ts = [e[1] for e in out], [e[0] for e in out]
         llr = self.dec.llr(Fs, ts) if self.keep_llr else None
-        dec = self.dec.decode(Fs, ts, self.ldpc) if self.decode else None
+        dec = self.dec.decode(Fs, ts, self.ldpc, osd=self.osd) if self.decode else None
         recs = []
         for k, (t0, F, score, hits) in enumerate(out):
             rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits)
@@ -383,6 +416,8 @@ class FT8_Skimmer(Skimmer):
                 ok = int(dec["status"][k]) == _ldpc.STATUS_OK
                 rec.update(status=int(dec["status"][k]), ok=ok, iterations=int(dec["iterations"][k]), nerr=int(dec["nerr"][k]), bits77=b77,
                            i3=i3, n3=n3, text=m.UNPACK(b77) if ok and m.UNPACK is not None else None)
+                if self.osd is not None:
+                    rec["osd"] = int(dec["osd"][k])
             if self.t_first is not None:
                 T = float(self.t_first) + rec["time"]
                 rec["slot"] = int(np.floor(T / m.SLOT_SECONDS))

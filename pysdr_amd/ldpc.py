@@ -10,9 +10,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import LdpcCfg
+from ._lib import LdpcCfg, OsdCfg
 
 N, K, M, MSG, CRC_BITS, EDGES = 174, 91, 83, 77, 14, 522
+OSD_PATTERNS = (1, 92, 4187)                     # error patterns the second stage scores at order 0, 1, 2
 CRC_POLY = 0x2757                                # x^14 + these terms; zero initial value, no reflection, no final XOR
 ITERS_MAX, DECODE_MAX = 200, 4096
 STATUS_NONE, STATUS_CODEWORD, STATUS_OK = 0, 1, 2   # no codeword; a codeword with a wrong CRC or an all-zero message; a message
@@ -158,3 +159,26 @@ def plan(cfg):
     iterations.  Raises PysdrError for a cfg outside the rules (iters in [1, 200], alpha finite and in (0, 1])."""
     v = _lib.plan_call("pysdr_ldpc_plan", 4, C.byref(cfg) if cfg is not None else None)
     return {"threads": v[0], "lds_bytes": v[1], "max_candidates": v[2], "iters": v[3]}
+
+
+def osd_params(order=2):
+    """The setting of ordered-statistics decoding behind min-sum as the ``_lib.OsdCfg`` the C ABI
+    takes: ``order`` rows of the most reliable basis' generator are flipped at once, 0 to 2.  The CRC-14 is the stage's
+    only guard: a candidate that reaches it comes out as a false message with probability about 2^-14."""
+    return OsdCfg(order=int(order))
+
+
+def osd_cfg(osd):
+    """None, an order or an ``OsdCfg`` -> None or the ``OsdCfg``"""
+    if osd is None or isinstance(osd, OsdCfg):
+        return osd
+    if isinstance(osd, bool) or not isinstance(osd, (int, np.integer)):
+        raise ValueError(f"osd: None, an order 0 to 2 or an OsdCfg, not {osd!r}")
+    return osd_params(osd)
+
+
+def osd_plan(cfg):
+    """What the second launch of a decode call with ``osd`` is (no device needed): dict of threads per candidate, LDS
+    bytes, patterns scored, candidates per call.  Raises PysdrError for an order outside [0, 2]."""
+    v = _lib.plan_call("pysdr_osd_plan", 4, C.byref(cfg) if cfg is not None else None)
+    return {"threads": v[0], "lds_bytes": v[1], "patterns": v[2], "max_candidates": v[3]}
