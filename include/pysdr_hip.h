@@ -695,6 +695,32 @@ int  pysdr_ft4_decode_osd(pysdr_ft4* ft4, const int32_t* F, const long long* t0,
 int  pysdr_ft4_decode_llr_osd(pysdr_ft4* ft4, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                               float* post, const pysdr_osd_cfg* osd, int32_t* detail);
 
+/* ---- Frame report and row floor ------------------------------------------------------------------
+ * What the spectrum ring says about a frame whose 91 bits are known.  float32, every operation rounded on its own.
+ * pysdr_ft8_report / pysdr_ft4_report: n <= 4096 candidates (F[i], t0[i]) under pysdr_*_llr's rules and refusals, and
+ * bits [n][12], the 91 bits MSB first as pysdr_*_decode packs them (the CRC is not checked).  Per candidate the bits are
+ * encoded again to the 174-bit codeword, the codeword gives the frame's tones tone[k], k < 79 (FT4: 103) -- the Costas
+ * arrays in their places, the data symbols' bits MSB first through the Gray map -- and
+ *   power[0 .. 8] = sig9[dt][dF], dt in -1, 0, 1 outer, dF in -1, 0, 1 inner: the sum over k ascending, from the first
+ *     term, of P[a'][t0 + dt + 4 k][j' + 2 tone[k]], (a', j') = divmod(F + dF, NSUB); F + dF wraps modulo the raster where
+ *     the raster is the whole circle (nk == M).  A place is missing -- exactly -1 -- where its fine row is outside the
+ *     raster, or where the frame from t0 + dt is not whole yet, begins before step 0 or has left the ring;
+ *   power[9] = tot: the sum over k ascending of (the symbol's 8 (4) tones at the candidate's own place, added ascending);
+ *   errs[0] = nhard, errs[1] = nsync: the data and the Costas symbols whose sent tone is not strictly greater than
+ *     every other tone of the symbol at the candidate's own place.
+ * pysdr_ft8_floor / pysdr_ft4_floor: out [nk][NB], out[a][b] = the sum over i < nsym ascending, from the first term, of
+ * P[a][t_end - 4 (nsym - 1 - i)][b].  PYSDR_ERR_ARG unless 1 <= nsym <= 128; PYSDR_ERR_STATE unless every one of those
+ * steps is complete and still in the ring.
+ * A refused call launches nothing and changes no output.  pysdr_report_plan needs no device: PYSDR_ERR_ARG for a mode
+ * that is neither or a NULL out, else out = {threads per candidate, LDS bytes, symbols, candidates per call}. */
+#define PYSDR_REPORT_FT8 0
+#define PYSDR_REPORT_FT4 1
+int  pysdr_report_plan(int mode, int32_t out[4]);
+int  pysdr_ft8_report(pysdr_ft8* ft8, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs);
+int  pysdr_ft4_report(pysdr_ft4* ft4, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs);
+int  pysdr_ft8_floor(pysdr_ft8* ft8, long long t_end, int nsym, float* out);
+int  pysdr_ft4_floor(pysdr_ft4* ft4, long long t_end, int nsym, float* out);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

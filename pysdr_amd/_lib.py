@@ -228,6 +228,11 @@ PROTOTYPES = {
                                   C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
     "pysdr_ft4_decode_llr_osd": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg),
                                       C.POINTER(C.c_int32)]),
+    "pysdr_report_plan": (_i, [_i, C.POINTER(C.c_int32)]),
+    "pysdr_ft8_report": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), _i, _pf, C.POINTER(C.c_int32)]),
+    "pysdr_ft4_report": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), _i, _pf, C.POINTER(C.c_int32)]),
+    "pysdr_ft8_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
+    "pysdr_ft4_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

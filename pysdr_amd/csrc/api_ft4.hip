@@ -6,6 +6,7 @@
 #include "chan_client.h"
 #include "ft4_plan.h"
 #include "ldpc_host.h"
+#include "report_host.h"
 
 using namespace pysdr;
 
@@ -26,6 +27,7 @@ struct pysdr_ft4 : ChanClient {
   std::vector<float> h_tw;
   std::vector<int32_t> h_cand;
   LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
+  ReportBufs report;                // the frame report's and the row floor's (report_host.h)
 };
 
 namespace {
@@ -222,6 +224,12 @@ int pysdr_ft4_decode_llr_osd(pysdr_ft4* w, const float* llr, int n, const pysdr_
                              float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
   return ldpc_decode_llr(w, "pysdr_ft4_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
 }
+
+int pysdr_ft4_report(pysdr_ft4* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
+  return report_frames(w, "pysdr_ft4_report", kReportFt4, ft4_llr_ok, kFt4Lag, F, t0, bits, n, power, errs);
+}
+
+int pysdr_ft4_floor(pysdr_ft4* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft4_floor", t_end, nsym, out); }
 
 int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
   if (!w) { set_last_error("pysdr_ft4_state: NULL skimmer"); return PYSDR_ERR_ARG; }

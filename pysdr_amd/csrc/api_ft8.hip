@@ -2,10 +2,12 @@
 // their launch functions live in ft8.hip, what both sides share in ft8_plan.h.  The skimmer borrows a channelizer as the
 // other skimmers do (chan_client.h: what the channelizer's clients share) and queues its kernels behind the
 // channelizer's launch on the channelizer's stream.  Every device resource is an owner (host_res.h): deleting the object
-// frees it.
+// frees it.  The decoder's calls are ldpc_host.h's, the frame report's and the row floor's report_host.h's, both shared
+// with api_ft4.hip.
 #include "chan_client.h"
 #include "ft8_plan.h"
 #include "ldpc_host.h"
+#include "report_host.h"
 
 using namespace pysdr;
 
@@ -26,6 +28,7 @@ struct pysdr_ft8 : ChanClient {
   std::vector<float> h_tw;
   std::vector<int32_t> h_cand;
   LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
+  ReportBufs report;                // the frame report's and the row floor's (report_host.h)
 };
 
 namespace {
@@ -240,6 +243,21 @@ int pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]) {
     return PYSDR_ERR_ARG;
   }
   out[0] = kOsdThreads; out[1] = kOsdLdsBytes; out[2] = osd_patterns(cfg->order); out[3] = kLdpcMax;
+  return PYSDR_OK;
+}
+
+int pysdr_ft8_report(pysdr_ft8* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
+  return report_frames(w, "pysdr_ft8_report", kReportFt8, ft8_llr_ok, kFt8Lag, F, t0, bits, n, power, errs);
+}
+
+int pysdr_ft8_floor(pysdr_ft8* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft8_floor", t_end, nsym, out); }
+
+int pysdr_report_plan(int mode, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_report_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!report_plan(mode, out)) {
+    set_last_error("pysdr_report_plan: mode %d is neither PYSDR_REPORT_FT8 nor PYSDR_REPORT_FT4", mode);
+    return PYSDR_ERR_ARG;
+  }
   return PYSDR_OK;
 }
 

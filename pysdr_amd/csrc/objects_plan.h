@@ -212,4 +212,10 @@ int launch_ldpc_decode(int source, const LdpcArgs& a, hipStream_t st);   // sour
 struct OsdArgs;
 int launch_osd_decode(int source, const OsdArgs& a, hipStream_t st);     // source: LdpcSource, the min-sum launch's
 
+// ---- frame report and row floor (report.hip, host half report_host.h; steps and kernel arguments: report_plan.h) ---------
+struct ReportArgs;
+struct FloorArgs;
+int launch_frame_report(int mode, const ReportArgs& a, hipStream_t st);  // mode: ReportMode
+int launch_ring_floor(const FloorArgs& a, hipStream_t st);
+
 }  // namespace pysdr

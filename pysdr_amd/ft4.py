@@ -17,7 +17,9 @@ from . import _lib
 from . import channelizer as _chan
 from . import psk as _psk
 from ._lib import Ft4Cfg
+from . import ft8 as _ft8
 from .ft8 import FT8_Decoders, FT8_Skimmer, hard_bits, owners, unit_llr, unpack  # noqa: F401  (this mode's too)
+from .ft8 import delta, noise_floor, noise_of, refine, snr_db, spots  # noqa: F401  (the frame report's host half)
 
 BAUD = 125.0 / 6.0
 COSTAS = ((0, 1, 3, 2), (1, 0, 2, 3), (2, 3, 1, 0), (3, 2, 0, 1))   # at symbols 0, 33, 66 and 99
@@ -33,6 +35,21 @@ SHAPES = (48, 72)                                # row samples per symbol
 NB_EXTRA = 6                                     # NB = NSUB + 6: decoder j uses bins j + 2 tone, tone 0 to 3
 LLR_MAX = 4096
 UNPACK = None                                    # FT4 XORs its 77 bits with a fixed scrambler before the CRC; that vector is not here
+REPORT_MODE = 1                                  # PYSDR_REPORT_FT4
+TONES = 4
+FLOOR_QUANTILE = 0.02                            # a row's floor: this quantile of its NB bin means, all but the least of them
+FLOOR_ROWS = (4, 8)                              # a candidate's noise: the median floor of the rows this far away: behind the prototype's stop band
+CAL = -0.7                                       # dB: the bias of so low a quantile, measured (tests/test_report_oracle.py)
+
+
+def report_plan():
+    """``ft8.report_plan`` for this mode: 103 symbols"""
+    return _ft8.report_plan(REPORT_MODE)
+
+
+def spot_line(rec, f_centre=0.0):
+    """``ft8.spot_line`` on this mode's 7.5 s slots"""
+    return _ft8.spot_line(rec, f_centre, SLOT_SECONDS)
 
 
 def shape(fs):

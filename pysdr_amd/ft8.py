@@ -4,8 +4,9 @@ with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSU
 every 3.125 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The device finds every
 frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` the device also runs
 the LDPC(174,91) decoder on them, straight from the spectrum ring, checks the CRC-14, and the record carries the message's
-77 bits and its text (``ldpc.py``, ``ft8msg.py``).  The tables and settings are derived here, once, and
-handed to the library already derived."""
+77 bits and its text (``ldpc.py``, ``ft8msg.py``); with ``report=True`` it measures every decoded frame
+in the spectrum ring and the record carries its SNR, fine frequency and fine time (kernels ``report.hip``; DESIGN.md 3 item
+26).  The tables and settings are derived here, once, and handed to the library already derived."""
 from __future__ import annotations
 
 import ctypes as C
@@ -186,6 +187,119 @@ def waveform(tones, f0, fs, gfsk=True, phase=0.0):
     return np.exp(1j * (2 * np.pi / float(fs) * ph + phase))
 
 
+# ---- the frame report on the host: float64, from the device's exact float32 numbers -----------------
+REPORT_MODE = 0                                  # PYSDR_REPORT_FT8
+REPORT_MAX = 4096
+TONES = 8
+SNR_BW = 2500.0                                  # the bandwidth an SNR is quoted in
+FLOOR_QUANTILE = 0.02                            # a row's floor: this quantile of its NB bin means, all but the least of them
+FLOOR_ROWS = (4, 8)                              # a candidate's noise: the median floor of the rows this far away, either side
+CAL = -0.7                                       # dB: the bias of so low a quantile, measured (tests/test_report_oracle.py)
+
+
+def report_plan(mode=None):
+    """What a frame report launches (no device needed): dict of threads per candidate, LDS bytes, symbols of a frame and
+    candidates per call.  Raises PysdrError for a mode that is neither."""
+    v = _lib.plan_call("pysdr_report_plan", 4, int(REPORT_MODE if mode is None else mode))
+    return {"threads": v[0], "lds_bytes": v[1], "symbols": v[2], "max_candidates": v[3]}
+
+
+def delta(a, b, c):
+    """Offset of a three-point parabola's peak from the middle point, in points, within +-0.5: 0 where ``a`` or ``c`` is
+    missing (negative); with d = a - 2 b + c, clip(0.5 (a - c) / d) where d < 0, else half a point towards the greater
+    neighbour.  ``b`` need not be the maximum."""
+    a, b, c = float(a), float(b), float(c)
+    if a < 0 or c < 0:
+        return 0.0
+    d = a - 2 * b + c
+    if d < 0:
+        return float(min(0.5, max(-0.5, 0.5 * (a - c) / d)))
+    return 0.5 * float(np.sign(c - a))
+
+
+def refine(sig9):
+    """sig9 [3][3] (time outer, fine row inner) -> (delta_f in raster steps, delta_t in steps, peak): ``delta`` across the
+    fine rows and across the steps through the candidate's own place; peak = b - 0.25 (a - c) delta_f, the parabola's
+    height across the fine rows (b itself where a neighbour is missing)."""
+    s = np.asarray(sig9, np.float64).reshape(3, 3)
+    a, b, c = s[1, 0], s[1, 1], s[1, 2]
+    df, dt = delta(a, b, c), delta(s[0, 1], b, s[2, 1])
+    return df, dt, float(b - 0.25 * (a - c) * df)
+
+
+def noise_floor(floor, nsym, quantile=None):
+    """``FT8_Decoders.floor``'s sums [nk][NB] over ``nsym`` steps -> float64 [nk]: per row the lower quartile of its bins'
+    mean powers"""
+    q = FLOOR_QUANTILE if quantile is None else quantile
+    return np.quantile(np.asarray(floor, np.float64) / float(nsym), q, axis=1)
+
+
+def noise_of(floor, nsym, F, nsub, circular, tones=TONES, rows=None, quantile=None):
+    """The noise power per bin for a candidate on fine row ``F``: the median of the floors of the rows 4 to 8 rows away
+    on either side (circular where the raster is); of all other rows if there are none; and on a raster of one row the
+    lower quartile of that row's own bins outside j - 2 .. j + 2 tones + 2."""
+    floor = np.asarray(floor, np.float64)
+    nk = floor.shape[0]
+    lo, hi = FLOOR_ROWS if rows is None else rows
+    q = FLOOR_QUANTILE if quantile is None else quantile
+    a, j = divmod(int(F), int(nsub))
+    if nk == 1:
+        b = np.arange(floor.shape[1])
+        out = floor[0, (b < j - 2) | (b > j + 2 * tones + 2)]
+        return float(np.quantile((out if len(out) else floor[0]) / float(nsym), q))
+    fl = noise_floor(floor, nsym, q)
+    far = set()
+    for d in range(lo, hi + 1):
+        for r in (a - d, a + d):
+            if circular:
+                far.add(r % nk)
+            elif 0 <= r < nk:
+                far.add(r)
+    far.discard(a)
+    if not far:
+        far = set(range(nk)) - {a}
+    return float(np.median(fl[sorted(far)]))
+
+
+def snr_db(peak, noise, nsym, baud=BAUD, cal=None):
+    """10 log10(max(peak / nsym - noise, 1e-3 noise) / noise) - 10 log10(2500 / baud) + CAL: dB in 2500 Hz"""
+    cal = CAL if cal is None else cal
+    s = max(float(peak) / float(nsym) - float(noise), 1e-3 * float(noise))
+    return 10 * np.log10(s / float(noise)) - 10 * np.log10(SNR_BW / baud) + cal
+
+
+def spots(records, reach=8):
+    """Among the ``ok`` records with equal ``bits77`` whose ``t0`` differ by at most ``reach`` steps keep the one of
+    greatest ``sig`` (ties: the lower (t0, F)): one message seen on two fine rows, or a step apart, is one spot.  -> the
+    records kept, in their order; records without ``ok`` are not spots."""
+    ok = [r for r in records if r.get("ok")]
+    keys = [bytes(np.asarray(r["bits77"], np.uint8)) for r in ok]
+    out = []
+    for i, r in enumerate(ok):
+        beaten = False
+        for k, o in enumerate(ok):
+            if k == i or keys[k] != keys[i] or abs(o["t0"] - r["t0"]) > reach:
+                continue
+            if o["sig"] > r["sig"] or (o["sig"] == r["sig"] and (o["t0"], o["F"]) < (r["t0"], r["F"])):
+                beaten = True
+                break
+        if not beaten:
+            out.append(r)
+    return out
+
+
+def spot_line(rec, f_centre=0.0, slot_seconds=SLOT_SECONDS):
+    """A reported record as the usual line ``HHMMSS snr dt freq ~ text``: the slot's UTC start, dB in 2500 Hz, seconds
+    against the nominal start, Hz (``f_centre`` is the band centre's dial offset).  Without ``t_first`` the time is empty
+    and dt is the frame's time into the stream."""
+    if "slot" in rec:
+        s = int(rec["slot"] * slot_seconds) % 86400
+        when, dt = f"{s // 3600:02d}{s // 60 % 60:02d}{s % 60:02d}", rec["dt_fine"]
+    else:
+        when, dt = "", rec["t_fine"]
+    return f"{when:6s} {int(round(rec['snr'])):3d} {dt:4.1f} {int(round(f_centre + rec['f_fine'])):4d} ~  {rec['text'] or ''}".rstrip()
+
+
 class FT8_Decoders(DecoderBank):
     """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
     KIND, DESTROY = "ft8", "pysdr_ft8_destroy"
@@ -303,6 +417,34 @@ class FT8_Decoders(DecoderBank):
                 self._call("decode_llr_osd", *args, C.byref(osd), None if de is None else de[i:].ctypes.data_as(C.POINTER(C.c_int32)))
         return self._answer(st, bits, po, osd, de)
 
+    def report(self, F, t0, bits91):
+        """The candidates (F[i], t0[i]) of ``llr``, under its rules, with the 91 bits of each as ``decode`` returns them
+        (uint8 [n][91]; the CRC is not checked) -> dict of sig9 float32 [n][3][3] (the sum of the frame's sent tones at
+        t0 - 1, t0, t0 + 1 outer and F - 1, F, F + 1 inner; -1 where a place is outside the raster or the ring), tot float32
+        [n] (all tones at the candidate's own place), nhard and nsync int32 [n] (data and Costas symbols whose sent tone is
+        not the strongest).  DESIGN.md 3 item 26; in calls of 4096."""
+        F = np.ascontiguousarray(F, np.int32)
+        t0 = np.ascontiguousarray(t0, np.int64)
+        b = np.ascontiguousarray(bits91, np.uint8).reshape(len(F), _ldpc.K) & 1
+        packed = np.ascontiguousarray(np.packbits(np.concatenate((b, np.zeros((len(F), 5), np.uint8)), axis=1), axis=1))
+        power = np.zeros((len(F), 10), np.float32)
+        errs = np.zeros((len(F), 2), np.int32)
+        for i in range(0, len(F), REPORT_MAX):
+            f, t, p = F[i:i + REPORT_MAX], t0[i:i + REPORT_MAX], packed[i:i + REPORT_MAX]
+            self._call("report", f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)),
+                       p.ctypes.data_as(C.POINTER(C.c_uint8)), len(f), _lib.as_pf(power[i:]), errs[i:].ctypes.data_as(C.POINTER(C.c_int32)))
+        return dict(sig9=power[:, :9].reshape(-1, 3, 3).copy(), tot=power[:, 9].copy(), nhard=errs[:, 0].copy(), nsync=errs[:, 1].copy())
+
+    def floor(self, t_end=None, nsym=None):
+        """float32 [nk][NB]: every bin of every row summed over the ``nsym`` steps, four apart, that end at step ``t_end``
+        (defaults: the newest complete step, the mode's symbol count); PysdrError unless 1 <= nsym <= 128 and every one of
+        those steps is complete and still in the ring."""
+        t_end = self.t_done - 1 if t_end is None else int(t_end)
+        nsym = self.MODE.SYMBOLS if nsym is None else int(nsym)
+        out = np.zeros((self.nk, self.nb), np.float32)
+        self._call("floor", C.c_longlong(t_end), nsym, _lib.as_pf(out))
+        return out
+
     def state(self, ring=False):
         """dict of sc float32 [9][nfine] and hits int32 [9][nfine] (frame start t at index t mod 9), t_done, and with
         ``ring`` the spectrum ring float32 [nk][TR][NB] (step t at index t mod TR)"""
@@ -328,12 +470,16 @@ class FT8_Skimmer(Skimmer):
     the records carry no ``llr``.  ``osd=2`` (an order 0 to 2, or ``ldpc.osd_params()``) sends the frames min-sum could not
     decode through ordered-statistics decoding and a record gains ``osd``: 0, the stage did not
     run; 1, 2, 3, it did.  Off by default: the CRC-14 is that stage's only guard, and a frame that reaches it comes out as
-    a false message with probability about 2^-14."""
+    a false message with probability about 2^-14.  ``report=True`` measures every decoded frame in the spectrum ring
+    (DESIGN.md 3 item 26): one row-floor call per release and one report call for the records with ``ok``, which gain
+    ``snr`` (dB in 2500 Hz), ``f_fine`` (Hz), ``t_fine`` (s), ``nhard``, ``nsync``, ``sig`` and ``noise`` (the mean power of
+    the sent tones at the refined peak and the noise power per bin) and, with ``t_first``, ``dt_fine``; the other records
+    carry the same keys as None.  ``spots`` then keeps one record per message and ``spot_line`` formats it."""
 
     DECODERS = FT8_Decoders                                              # the bank; its MODE is the skimmer's too
 
     def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None, decode=False, ldpc=None,
-                 keep_llr=True, osd=None):
+                 keep_llr=True, osd=None, report=False):
         m = self.DECODERS.MODE
         self.fs, self.baud, self.t_first = float(fs), m.BAUD, t_first
         self.decode, self.keep_llr = bool(decode), bool(keep_llr) or not decode
@@ -341,6 +487,9 @@ class FT8_Skimmer(Skimmer):
         self.osd = _ldpc.osd_cfg(osd)
         if self.osd is not None and not decode:
             raise ValueError(f"{type(self).__name__}: osd is a stage of the decoder: it needs decode=True")
+        self.report = bool(report)
+        if self.report and not decode:
+            raise ValueError(f"{type(self).__name__}: report measures decoded frames: it needs decode=True")
         if decode:
             _ldpc.plan(self.ldpc)                                        # a bad setting fails here, with or without a device
         if self.osd is not None:
@@ -423,7 +572,33 @@ class FT8_Skimmer(Skimmer):
                 rec["slot"] = int(np.floor(T / m.SLOT_SECONDS))
                 rec["dt"] = T - m.SLOT_SECONDS * rec["slot"] - m.NOMINAL_START
             recs.append(rec)
+        if self.report:
+            self._measure(recs, dec["bits"])
         return recs
+
+    REPORT_KEYS = ("snr", "f_fine", "t_fine", "nhard", "nsync", "sig", "noise")
+
+    def _measure(self, recs, bits):
+        """the frame report of a release: one floor over the newest frame's span, one report for the decoded records"""
+        m = self.DECODERS.MODE
+        keys = self.REPORT_KEYS + (("dt_fine",) if self.t_first is not None else ())
+        for r in recs:
+            r.update(dict.fromkeys(keys))
+        good = [k for k, r in enumerate(recs) if r["ok"]]
+        if not good:
+            return
+        lag = m.STEPS_PER_SYMBOL * (m.SYMBOLS - 1)
+        floor = self.dec.floor(max(r["t0"] for r in recs) + lag, m.SYMBOLS)
+        rep = self.dec.report([recs[k]["F"] for k in good], [recs[k]["t0"] for k in good], bits[good])
+        for i, k in enumerate(good):
+            r = recs[k]
+            df, dt, peak = refine(rep["sig9"][i])
+            noise = noise_of(floor, m.SYMBOLS, r["F"], self.nsub, self.circular, m.TONES, m.FLOOR_ROWS, m.FLOOR_QUANTILE)
+            r.update(snr=float(snr_db(peak, noise, m.SYMBOLS, m.BAUD, m.CAL)), f_fine=float(self.freqs_fine[r["F"]] + df * m.BAUD / 2),
+                     t_fine=(r["t0"] + dt) * self.qs / self.fs_out, nhard=int(rep["nhard"][i]), nsync=int(rep["nsync"][i]),
+                     sig=peak / m.SYMBOLS, noise=noise)
+            if self.t_first is not None:
+                r["dt_fine"] = float(self.t_first) + r["t_fine"] - m.SLOT_SECONDS * r["slot"] - m.NOMINAL_START
 
     def push(self, x):
         """complex64 [n] -> the records of the frames whose step t0 + HOLD - 1 this input completes, owners only, sorted by
