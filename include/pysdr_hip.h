@@ -138,7 +138,10 @@ int pysdr_squelch_get(pysdr_ctx* ctx, int irx, float* level, int* open);
  * alpha = 0.001 (:131-134), and the gate open while sq1 / sq2 >= min_ratio (:145) -- independent of the signal's level.  One
  * decision per chunk (the AGC block), on the envelopes behind its last sample.  min_ratio > 0 arms it for that sub-receiver
  * (NFM) and takes precedence over pysdr_set_squelch; 0 disarms.  pysdr_squelch_ratio_get: the two envelopes and the gate
- * behind the last call. */
+ * behind the last call.  The two FIRs read the detector output the AF stage stages and keeps for its own filter of ntaps_af
+ * taps: ntaps <= min(64, 12 ceil(ntaps_af / 12) + 3, history - 1), history = 16 ceil((8 ceil(ntaps_af / 8) + 5) / 16) -- 63 from
+ * 49 AF taps on, 64 from 61 on.  Longer ones are refused (PYSDR_ERR_ARG, pysdr_last_error names both lengths) and nothing of
+ * the context changes. */
 int pysdr_set_squelch_ratio(pysdr_ctx* ctx, int irx, float min_ratio, const float* lp, const float* hp, int ntaps);
 int pysdr_squelch_ratio_get(pysdr_ctx* ctx, int irx, float* sq_lp, float* sq_hp, int* open);
 /* AGC on/off and reference level */

@@ -50,6 +50,22 @@ SQ_RATIO_ALPHA = 0.001
 SQ_RATIO_TAPS = 63
 SQ_RATIO_LP_HZ = 3000.0
 SQ_RATIO_HP_HZ = 4000.0
+SQ_TAPS_MAX = 64               # the most taps either filter of the ratio squelch may have
+
+
+def af_history(ntaps_af):
+    """Outputs of history the AF stage keeps in front of a call: the taps rounded up to 8, the discriminator's reach, to whole
+    groups of 16 outputs."""
+    return ((((int(ntaps_af) + 7) & ~7) + 5) + 15) & ~15
+
+
+def sq_ratio_taps_bound(ntaps_af):
+    """The longest squelch filters the ratio squelch accepts beside an AF filter of ``ntaps_af`` taps.  The AF stage stages, per
+    tile, the detector output from taps_padded + 3 values in front of the tile's first output (taps_padded = the AF taps in
+    whole groups of 12), and real detector history reaches back af_history - 2 outputs: a squelch filter of K taps reads K values
+    back from an output (the last one fetched, not used) and uses K - 1 of them."""
+    taps_padded = (int(ntaps_af) + 11) // 12 * 12
+    return min(SQ_TAPS_MAX, taps_padded + 3, af_history(ntaps_af) - 1)
 
 
 def squelch_ratio_taps(fs_out, dtype=np.float32):
@@ -389,8 +405,11 @@ class Demodulator:
         self.filter_bank_real = af_filter_bank_real(fs_out, ntaps_af)
         self.filter_bank_cmpx = af_filter_bank_cmpx(fs_out, ntaps_af)
         self.am_pll = CarrierPLL(fs_out, dtype)
-        self.yhist = np.zeros(self.ntaps + 1, self.cd)     # y[m-(ntaps+1)] .. y[m-1]
-        self.vhist = np.zeros(self.ntaps - 1, self.cd)     # PLL outputs (AM-Synch only)
+        # detector outputs kept in front of a call: what the AF filter reaches back over, and never less than the squelch needs
+        # (two back for the noise squelch, its taps minus one for the ratio squelch) -- whatever the AF filter's length
+        self.dhist = max(self.ntaps - 1, SQ_TAPS_MAX - 1)
+        self.yhist = np.zeros(self.dhist + 2, self.cd)     # y[m-(dhist+2)] .. y[m-1]
+        self.vhist = np.zeros(self.dhist, self.cd)         # PLL outputs (AM-Synch only)
         self.m_abs = 0
         self.taps = None
 
@@ -402,12 +421,12 @@ class Demodulator:
         the kept y history, so a mode change takes effect on the whole AF-filter window
         (DESIGN.md 3.5); only the AM-Synch PLL output has a history of its own."""
         y = np.asarray(y, self.cd)
-        n, hl = len(y), self.ntaps - 1
-        ybuf = np.concatenate((self.yhist, y))            # ybuf[j] <-> output m_abs-(hl+2)+j
+        n, hl, dh = len(y), self.ntaps - 1, self.dhist
+        ybuf = np.concatenate((self.yhist, y))            # ybuf[j] <-> output m_abs-(dh+2)+j
         if mode == "AM-Synch":
             v = self.am_pll.process(y).astype(self.cd)
             d = np.concatenate((self.vhist, v))
-            self.vhist = d[len(d) - hl:]
+            self.vhist = d[len(d) - dh:]
         elif mode == "AM":
             d = np.abs(ybuf[2:]).astype(self.rd).astype(self.cd)
         elif mode == "NFM":
@@ -415,19 +434,21 @@ class Demodulator:
             d = (nfm_discriminator(ybuf, self.rd) * scale).astype(self.cd)
         elif mode == "CW":
             fw, _ = freq_word(bfo, self.fs_out)
-            idx = self.m_abs - hl + np.arange(hl + n, dtype=np.int64)
+            idx = self.m_abs - dh + np.arange(dh + n, dtype=np.int64)
             ph = ((idx % TWO32) * fw) % TWO32
             d = (ybuf[2:] * phase_to_cplx(ph.astype(np.uint32), self.cd)).astype(self.cd)
         else:                       # SSB/USB/LSB/IQ/RTTY: the AF filter does the work
             d = ybuf[2:]
-        a = np.convolve(d, self.taps, mode='valid') if n else d[:0]
+        a = np.convolve(d[dh - hl:], self.taps, mode='valid') if n else d[:0]      # d[j] <-> output m_abs-dh+j
         # out-of-band noise of the detector output (2nd difference = crude high-pass), for
         # the NFM noise squelch (sigs/squelch.m:92-145: HP envelope, one-pole smoothing)
         dr = d.real.astype(self.rd)
-        self.last_hp = np.abs(dr[hl:] - self.rd(2) * dr[hl - 1:-1] + dr[hl - 2:-2]).astype(self.rd) if n else dr[:0]
+        self.last_hp = np.abs(dr[dh:] - self.rd(2) * dr[dh - 1:-1] + dr[dh - 2:-2]).astype(self.rd) if n else dr[:0]
         # ... and for the ratio squelch the detector output itself, with the history its two FIRs reach back over
-        self.last_det = dr[hl - (SQ_RATIO_TAPS - 1):] if n else dr[:0]
-        self.yhist = ybuf[len(ybuf) - (hl + 2):]
+        # (last_det: for the designed SQ_RATIO_TAPS; last_det_all: everything kept, for filters of another length)
+        self.last_det = dr[dh - (SQ_RATIO_TAPS - 1):] if n else dr[:0]
+        self.last_det_all = dr if n else dr[:0]
+        self.yhist = ybuf[len(ybuf) - (dh + 2):]
         self.m_abs += n
         return a.astype(self.cd)
 
@@ -466,11 +487,23 @@ class Receiver:
         self.squelch = dtype(0)        # NFM noise-squelch threshold, 0 = off
         self.sq_level = dtype(0)
         self.sq_open = True
-        self.squelch_ratio = dtype(0)  # the ratio squelch: open while sq1 / sq2 >= this; 0 = off (takes precedence when armed)
+        self._squelch_ratio = dtype(0)
         self.sq_lp = dtype(0)          # sq1: envelope of the < 3 kHz part of the discriminator output
         self.sq_hp = dtype(0)          # sq2: envelope of the > 4 kHz part
         self._sq_taps = squelch_ratio_taps(self.fs_out, dtype)
         self.xhist = np.zeros(0, self.cd)
+
+    @property
+    def squelch_ratio(self):
+        """The ratio squelch: open while sq1 / sq2 >= this; 0 = off (takes precedence when armed)."""
+        return self._squelch_ratio
+
+    @squelch_ratio.setter
+    def squelch_ratio(self, min_ratio):
+        k, bound = len(self._sq_taps[0]), sq_ratio_taps_bound(self.demod.ntaps)
+        if min_ratio > 0 and k > bound:
+            raise ValueError(f"ratio squelch: filters of {k} taps beside an AF filter of {self.demod.ntaps} taps (at most {bound})")
+        self._squelch_ratio = self.rd(min_ratio)
 
     @staticmethod
     def _video_index(video_bw):
@@ -529,7 +562,8 @@ class Receiver:
             # the ratio behind the chunk's last sample (a chunk is the AGC block: one gain per chunk)
             al = self.rd(SQ_RATIO_ALPHA)
             b, aa = np.array([al], self.rd), np.array([1, al - 1], self.rd)
-            det = self.demod.last_det
+            det = self.demod.last_det_all
+            det = det[len(det) - (len(a) + len(self._sq_taps[0]) - 1):]
             for name, taps in (("sq_lp", self._sq_taps[0]), ("sq_hp", self._sq_taps[1])):
                 z = np.abs(np.convolve(det, taps, mode='valid').astype(self.rd))
                 env, _ = signal.lfilter(b, aa, z, zi=np.array([(self.rd(1) - al) * getattr(self, name)], self.rd))

@@ -790,10 +790,7 @@ int pysdr_create(const pysdr_cfg* cfg, pysdr_ctx** out) {
   if (rc) return rc;
   pysdr_ctx* c = new pysdr_ctx();
   c->cfg = *cfg;
-  // FIR history (taps padded to 8) + discriminator, rounded up to 16 outputs so that output 0 of a
-  // call sits on a 128-byte line: the mix+decimate kernel's 512-byte wave stores then cover whole
-  // lines (partial lines are written through as masked writes = read-modify-write at the DRAM)
-  c->hy = ((((cfg->ntaps_af + 7) & ~7) + 4 + 1) + 15) & ~15;
+  c->hy = fir_history(cfg->ntaps_af);
   c->cap_samples = (size_t)cfg->max_chunks * (size_t)cfg->in_chunk;
   c->tune = Tuning::from_env();
   c->mmax = (int)((c->cap_samples * (size_t)cfg->up) / (size_t)cfg->down) + 4;
@@ -924,6 +921,13 @@ int pysdr_set_squelch(pysdr_ctx* c, int irx, float thresh) {
 
 int pysdr_set_squelch_ratio(pysdr_ctx* c, int irx, float min_ratio, const float* lp, const float* hp, int ntaps) {
   if (!c || irx < 0 || irx >= c->nrx || (min_ratio > 0.f && (!lp || !hp || ntaps < 1 || ntaps > kSqTapsMax))) return PYSDR_ERR_ARG;
+  // (before anything is allocated, uploaded or changed: the taps are the context's, and a refused call for one sub-receiver
+  // leaves the armed squelch of another as it was)
+  if (min_ratio > 0.f && ntaps > sq_taps_bound(c->cfg.ntaps_af)) {
+    set_last_error("pysdr_set_squelch_ratio: squelch filters of %d taps beside an AF filter of %d taps: at most %d (the AF stage "
+                   "stages and keeps no more detector history)", ntaps, c->cfg.ntaps_af, sq_taps_bound(c->cfg.ntaps_af));
+    return PYSDR_ERR_ARG;
+  }
   std::lock_guard<std::recursive_mutex> run_lk(c->run_mu);     // allocates and uploads on the context's stream
   int rc = use_device(c->cfg.device);
   if (rc) return rc;

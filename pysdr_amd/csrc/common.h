@@ -197,6 +197,9 @@ int launch_mixdec_mfma(int shape, const MixMfmaArgs& a, int grid, hipStream_t st
 // 55.8 / 55.8 / 56.4 us at 64 / 32 / 16 / 8 / 4 / 1 words) -- but agc_scan_kernel, which gathers them, does: 21.7 / 22.6 /
 // 15.9-16.6 / 15.9 / 14.5 / 13.8 us.  16 words = 64 bytes: the pair costs 70 us where 64 words cost 77.
 constexpr int kBlkStride = PYSDR_BLK_STRIDE;
+// the squelch's block sums are 64-bit atomics on blknoise / blknoise2 + block * kBlkStride words (fir_epilogue): 8-byte aligned,
+// and no block's sum may reach into the next block's
+static_assert(kBlkStride >= 2 && kBlkStride % 2 == 0, "PYSDR_BLK_STRIDE: even and at least 2 (64-bit block sums)");
 
 struct RxDevState {       // one per RX, lives in device memory
   float env, gain, maxbuf, err, ref;
@@ -220,6 +223,23 @@ struct RxDevState {       // one per RX, lives in device memory
 };
 // ratio squelch: taps per filter (device layout [2][kSqTapsMax]: low-pass, high-pass, zero padded), the envelopes' pole
 constexpr int kSqTapsMax = 64;
+// The AF FIR's geometry as far as the host needs it (demod_fir_kernel): the taps zero padded to whole groups of 12, and the
+// history kept in front of a call's outputs -- FIR history (taps padded to 8) + discriminator, rounded up to 16 outputs so that
+// output 0 of a call sits on a 128-byte line: the mix+decimate kernel's 512-byte wave stores then cover whole lines (partial
+// lines are written through as masked writes = read-modify-write at the DRAM).
+constexpr int fir_taps_padded(int ntaps) { return (ntaps + 11) / 12 * 12; }
+constexpr int fir_history(int ntaps_af) { return ((((ntaps_af + 7) & ~7) + 4 + 1) + 15) & ~15; }
+// The most taps the ratio squelch's two FIRs may have beside an AF filter of ntaps_af taps.  The tile stages
+// S[e] = d[i0 - H + e - 3], H = fir_taps_padded; output i0 + 8 tid + j sits at e = 8 tid + H + 3 + j and fir_epilogue reads
+// S[8 tid + H + 3 - q - 1] for q < sq_ntaps (the last one fetched, not used): e >= 0 on lane 0 <=> sq_ntaps <= H + 3.  The taps
+// used reach d[i - (sq_ntaps - 1)], i >= 0, and d is real history only for i >= -hy + 2 (zeros in front): sq_ntaps <= hy - 1.
+constexpr int sq_taps_bound(int ntaps_af) {
+  const int h3 = fir_taps_padded(ntaps_af) + 3, hy1 = fir_history(ntaps_af) - 1;
+  const int b = h3 < hy1 ? h3 : hy1;
+  return b < kSqTapsMax ? b : kSqTapsMax;
+}
+static_assert(sq_taps_bound(48) == 51 && sq_taps_bound(49) == 63 && sq_taps_bound(40) == 47 && sq_taps_bound(1) == 15 &&
+              sq_taps_bound(255) == kSqTapsMax, "sq_taps_bound");
 constexpr float kSqAlpha = 0.001f;                 // sigs/squelch.m:131
 constexpr float kSqLog2Decay = -0.00144341686f;    // log2(1 - 0.001)
 

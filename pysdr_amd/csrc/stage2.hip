@@ -558,7 +558,7 @@ constexpr int kFirRealReal = 0;        // d real, c real    -> real
 constexpr int kFirRePart = 1;          // d cplx, c cplx    -> Re(c*d)
 constexpr int kFirCplx = 2;            // d cplx, c cplx    -> cplx (IQ)
 __host__ __device__ __forceinline__ constexpr int fir_pad(int e) { return e + 4 * (e >> 7); }
-__host__ __device__ __forceinline__ constexpr int fir_taps_padded(int ntaps) { return (ntaps + 11) / 12 * 12; }
+// (fir_taps_padded -- the taps in whole groups of 12 -- is in common.h, beside the history length and the squelch's bound)
 
 __device__ __forceinline__ float2 detect(const Stage2Args& a, int r, int det, const float2* y, int i) {
   float2 d = make_float2(0.f, 0.f);

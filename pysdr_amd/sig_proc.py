@@ -444,10 +444,10 @@ class Receiver:
     @squelch_ratio.setter
     def squelch_ratio(self, min_ratio):
         from . import design
-        self._squelch_ratio = float(min_ratio)
         lp, hp = design.squelch_ratio_taps(float(self._ctx.fs_out))
-        check(self._ctx.L.pysdr_set_squelch_ratio(self._ctx.h, self.irx, self._squelch_ratio, _lib.as_pf(lp), _lib.as_pf(hp), len(lp)),
+        check(self._ctx.L.pysdr_set_squelch_ratio(self._ctx.h, self.irx, float(min_ratio), _lib.as_pf(lp), _lib.as_pf(hp), len(lp)),
               "pysdr_set_squelch_ratio")
+        self._squelch_ratio = float(min_ratio)          # (only what the library accepted: a refused value leaves the old one)
 
     @property
     def squelch_ratio_state(self):

@@ -146,10 +146,10 @@ def relerr(got, want):
     return float(np.max(np.abs(got - want)) / max(np.max(np.abs(want)), 1e-30))
 
 
-def run_oracle(cfg, x, calls, dtype):
+def run_oracle(cfg, x, calls, dtype, ntaps_af=255):
     """-> per sub-receiver, per call: (iq, am) of the oracle in ``dtype`` (np.float64: the master)."""
     out = []
-    for o in so.make_receivers(cfg, dtype):
+    for o in so.make_receivers(cfg, dtype, ntaps_af=ntaps_af):
         pos, per = 0, []
         for c in calls:
             am = o.demod_data(x[pos:pos + c])

@@ -580,20 +580,25 @@ def test_multi_rx_1001_taps_with_tiles_too_small_to_hold_the_taps(name):
     run_both(cfg, [L, L, 1000, 7, L - 13, 2 * L + 5, 333], seed=43, tile=(12288, 1024))
 
 
-def check_does_not_depend_on_the_cut(cfg, B=10, x=None, want_iq=None):
+def check_does_not_depend_on_the_cut(cfg, B=10, x=None, want_iq=None, af_filt_len=None, am_bar=None, am_cut_rx=()):
     """Chunk by chunk == one batch == cut at random places, bit for bit, for every sub-receiver (baseband IQ, audio, chunk
     counts; the raw chunk peaks are NumPy's), and the baseband IQ equals the oracle (``want_iq[i]``: a reference of the caller's
-    for the B chunks of ``x``, else the float32 oracle).  -> (the chunked run's parameters, the worst IQ error)."""
+    for the B chunks of ``x``, else the float32 oracle).  -> (the chunked run's parameters, the worst IQ error).
+    ``af_filt_len``: the contexts' AF filter length (default: the parameters' own).  ``am_bar[i]``: sub-receiver i's batch audio
+    is held to that fraction of the chunked run's peak instead of its bits (AM-Synch: segments joined within a tolerance).
+    ``am_cut_rx``: sub-receivers without AGC (one gain per call would differ) whose AUDIO must equal the chunked run's bit for
+    bit under the random cuts too."""
+    kw = {} if af_filt_len is None else dict(af_filt_len=af_filt_len)
     L = so.chunk_sizes(cfg['fs'], cfg['fs_out'])[3]
     x = so.synth_iq(cfg, B * L, 33) if x is None else x
     assert len(x) == B * L
-    P1, g1 = make_gpu_receivers(cfg)
+    P1, g1 = make_gpu_receivers(cfg, **kw)
     am1, iq1 = [[] for _ in g1], [[] for _ in g1]
     for k in range(B):
         for i, rx in enumerate(g1):
             am1[i].append(rx.demod_data(x[k * L:(k + 1) * L]).copy())
             iq1[i].append(rx.iq.copy())
-    P2, g2 = make_gpu_receivers(cfg, max_batch_chunks=B)
+    P2, g2 = make_gpu_receivers(cfg, max_batch_chunks=B, **kw)
     ctx = P2._pysdr_stream
     ctx.process_batch(x, B, L, on_device=False)
     pk_batch = None
@@ -602,19 +607,25 @@ def check_does_not_depend_on_the_cut(cfg, B=10, x=None, want_iq=None):
         pk_batch = pk
         assert list(cn) == [len(a) for a in am1[i]]
         assert np.array_equal(iq, np.concatenate(iq1[i])), i
-        assert np.array_equal(am, np.concatenate(am1[i])), i
+        if am_bar and i in am_bar:
+            ref = np.concatenate(am1[i])
+            assert am.shape == ref.shape and np.max(np.abs(am - ref)) <= am_bar[i] * np.max(np.abs(ref)), i
+        else:
+            assert np.array_equal(am, np.concatenate(am1[i])), i
     want_pk = [np.max(np.abs(x[k * L:(k + 1) * L].astype(np.complex128)) ** 2) for k in range(B)]
     assert np.allclose(pk_batch, want_pk, rtol=1e-6)
     rng = np.random.default_rng(6)
     cuts = np.sort(rng.choice(np.arange(1, B * L), 7, replace=False))
-    P3, g3 = make_gpu_receivers(cfg, max_batch_chunks=4)
-    iq3 = [[] for _ in g3]
+    P3, g3 = make_gpu_receivers(cfg, max_batch_chunks=4, **kw)
+    iq3, am3 = [[] for _ in g3], [[] for _ in g3]
     for a, b in zip(np.r_[0, cuts], np.r_[cuts, B * L]):
         for c in range(a, b, 4 * L):                      # a call may not exceed the context's capacity
             for i, rx in enumerate(g3):
-                rx.demod_data(x[c:min(c + 4 * L, b)]); iq3[i].append(rx.iq.copy())
+                am3[i].append(rx.demod_data(x[c:min(c + 4 * L, b)]).copy()); iq3[i].append(rx.iq.copy())
     for i in range(len(g3)):
         assert np.array_equal(np.concatenate(iq1[i]), np.concatenate(iq3[i])), i
+    for i in am_cut_rx:
+        assert np.array_equal(np.concatenate(am1[i]), np.concatenate(am3[i])), i
     worst = 0.0
     for i, o in enumerate(so.make_receivers(cfg, np.float32) if want_iq is None else want_iq):
         want = o if want_iq is not None else \
