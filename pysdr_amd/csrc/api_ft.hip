@@ -1,0 +1,360 @@
+// C ABI of the FT8 and FT4 skimmers (include/pysdr_hip.h).  Host-side only, like api_fsk.hip:
+// the kernels and their launch functions live in ft.hip, what both sides share in ft_plan.h.  One skimmer, templated on
+// the mode; every call is written once, and the extern "C" functions at the end forward to it under their own names.  A
+// skimmer borrows a channelizer as the other skimmers do (chan_client.h: what the channelizer's clients share) and queues
+// its kernels behind the channelizer's launch on the channelizer's stream.  Every device resource is an owner
+// (host_res.h): deleting the object frees it.  The decoder's calls are ldpc_host.h's, the frame report's and the row
+// floor's report_host.h's; both read the mode from the skimmer.
+#include "chan_client.h"
+#include "ft_plan.h"
+#include "ldpc_host.h"
+#include "report_host.h"
+
+using namespace pysdr;
+
+template <class M>
+struct FtSkimmer : ChanClient {
+  using Mode = M;
+  int max_out = 0;
+  FtCfg cfg{};
+  FtPlan plan;
+  unsigned long long t_done = 0;    // steps complete since create / reset
+  DevBuf<FtC> d_y;                  // [nk][ypitch]: Mode::kHpad of history room, then the call's outputs
+  DevBuf<FtC> d_tw;                 // [NT]
+  DevBuf<float> d_ring;             // [nk][tr][NB]
+  DevBuf<float> d_sc;               // [9][nfine]
+  DevBuf<int32_t> d_hi;             // [9][nfine]
+  DevBuf<int32_t> d_events;         // [nfine][cap][2]
+  DevBuf<int32_t> d_counts;         // [nfine]
+  DevBuf<int32_t> d_cand;           // [kFtLlrMax][2]
+  DevBuf<float> d_llr;              // [kFtLlrMax][174]
+  std::vector<float> h_tw;
+  std::vector<int32_t> h_cand;
+  LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
+  ReportBufs report;                // the frame report's and the row floor's (report_host.h)
+};
+
+struct pysdr_ft8 : FtSkimmer<Ft8Mode> {};
+struct pysdr_ft4 : FtSkimmer<Ft4Mode> {};
+
+namespace {
+
+// the two public cfg structs are FtCfg's layout (ft_plan.h asserts it)
+const FtCfg* ft_cfg(const pysdr_ft8_cfg* c) { return reinterpret_cast<const FtCfg*>(c); }
+const FtCfg* ft_cfg(const pysdr_ft4_cfg* c) { return reinterpret_cast<const FtCfg*>(c); }
+
+template <class W>
+int ft_alloc(W* w) {
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine, S = (size_t)w->plan.S;
+  PYSDR_HIP_CHECK(w->d_y.alloc(nk * (size_t)w->plan.ypitch));
+  PYSDR_HIP_CHECK(w->d_tw.alloc(4 * S));
+  PYSDR_HIP_CHECK(w->d_ring.alloc(nk * (size_t)w->plan.tr * (size_t)w->plan.nb));
+  PYSDR_HIP_CHECK(w->d_sc.alloc((size_t)kFtKeep * nf));
+  PYSDR_HIP_CHECK(w->d_hi.alloc((size_t)kFtKeep * nf));
+  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap * kFtEventWords));
+  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
+  PYSDR_HIP_CHECK(w->d_cand.alloc((size_t)kFtLlrMax * 2));
+  PYSDR_HIP_CHECK(w->d_llr.alloc((size_t)kFtLlrMax * kFtBits));
+  return PYSDR_OK;
+}
+
+template <class W>
+int ft_reset_locked(W* w) {
+  const int rc = pysdr_chan_reset(w->ch);
+  if (rc != PYSDR_OK) return rc;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nk = (size_t)w->nk, nf = (size_t)w->plan.nfine;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // the host arrays may still feed an earlier copy
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_tw.get(), w->h_tw.data(), w->h_tw.size() * sizeof(float), hipMemcpyHostToDevice, st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_y.get(), 0, nk * (size_t)w->plan.ypitch * sizeof(FtC), st));   // y[k] = 0 for k < 0
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_ring.get(), 0, nk * (size_t)w->plan.tr * (size_t)w->plan.nb * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sc.get(), 0, (size_t)kFtKeep * nf * sizeof(float), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_hi.get(), 0, (size_t)kFtKeep * nf * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * kFtEventWords * sizeof(int32_t), st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  w->last_n_out = 0;
+  w->t_done = 0;
+  return PYSDR_OK;
+}
+
+// `who` in every call below: the public function's name, for the messages
+
+template <class Mode>
+int ft_plan_call(const char* who, int nk, int S, int max_out, const FtCfg* cfg, int32_t out[8]) {
+  if (!out) { set_last_error("%s: out is NULL", who); return PYSDR_ERR_ARG; }
+  FtPlan p;
+  if (!ft_plan<Mode>(nk, S, max_out, cfg, &p)) {
+    set_last_error("%s: S %d is neither %d nor %d, nk %d < 1 or nk S / 2 > %d, max_out %d outside [1, %d], a spectrum ring "
+                   "above %lld bytes, or a cfg outside the rules (NULL; smin >= 0, 0 <= hmin <= %d, 0 < pmax <= 1e18, all finite)", who, S,
+                   Mode::kS0, Mode::kS1, nk, kFtFineMax, max_out, kFtMaxOutMax, kFtRingBytesMax, Mode::kSync);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = 1; out[1] = ft_threads<Mode>(S); out[2] = ft_lds_bytes<Mode>(S); out[3] = S; out[4] = p.cap; out[5] = p.groups;
+  out[6] = p.nsub; out[7] = p.tr;
+  return PYSDR_OK;
+}
+
+// who_plan: the plan function's name, whose refusal a create call passes on
+template <class W>
+int ft_create(const char* who, const char* who_plan, pysdr_chan* ch, int S, const FtCfg* cfg, const float* tw, int max_out, W** out) {
+  using Mode = typename W::Mode;
+  if (!out) { set_last_error("%s: out is NULL", who); return PYSDR_ERR_ARG; }
+  *out = nullptr;
+  if (!ch || !cfg || !tw) { set_last_error("%s: NULL channelizer, cfg or tw", who); return PYSDR_ERR_ARG; }
+  W* w = new W();
+  int32_t pl[8];
+  int rc = client_bind(w, ch);
+  if (rc == PYSDR_OK) rc = ft_plan_call<Mode>(who_plan, w->nk, S, max_out, cfg, pl);
+  if (rc != PYSDR_OK) { delete w; return rc; }
+  w->max_out = max_out; w->cfg = *cfg;
+  ft_plan<Mode>(w->nk, S, max_out, cfg, &w->plan);
+  w->h_tw.assign(tw, tw + 2 * 4 * (size_t)S);
+  w->h_cand.reserve((size_t)kFtLlrMax * 2);
+  return client_create(w, who, ft_alloc<W>, ft_reset_locked<W>, out);
+}
+
+template <class W>
+int ft_reset(W* w, const char* who) {
+  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  return ft_reset_locked(w);
+}
+
+template <class W>
+int ft_sync_call(W* w, const char* who) {
+  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  return client_sync(w);
+}
+
+template <class W>
+int ft_process(W* w, const char* who, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+               long long ev_pitch, long long* steps) {
+  using Mode = typename W::Mode;
+  if (!w || !n_out) { set_last_error("%s: NULL skimmer or n_out", who); return PYSDR_ERR_ARG; }
+  *n_out = 0;
+  std::lock_guard<std::mutex> lk(w->mu);
+  ClientStep step;
+  int rc = client_begin(w, who, iq, n, &step);
+  if (rc != PYSDR_OK) return rc;
+  const int words = w->plan.cap * kFtEventWords;
+  if (events && ev_pitch < words) {
+    set_last_error("%s: ev_pitch %lld < the event cap's %d words", who, ev_pitch, words);
+    return PYSDR_ERR_STATE;
+  }
+  if (step.nf_want > (unsigned long long)w->max_out) {
+    set_last_error("%s: the call would complete %llu outputs, max_out is %d", who, step.nf_want, w->max_out);
+    return PYSDR_ERR_STATE;
+  }
+  int nf = 0;
+  rc = client_feed(w, who, "skimmer", iq, n, on_device, w->d_y.get() + Mode::kHpad, w->plan.ypitch, step, &nf);
+  if (rc != PYSDR_OK) return rc;
+  const size_t nfine = (size_t)w->plan.nfine;
+  const int S = w->plan.S;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  if (steps) { steps[0] = (long long)w->t_done; steps[1] = 0; }
+  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
+    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
+  } else {
+    const unsigned long long t1 = ft_steps_done(step.m0 + (unsigned long long)nf, S);
+    FtArgs a{};
+    a.y = w->d_y.get() + Mode::kHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.ns = (int)(t1 - w->t_done);
+    a.e_first = a.ns > 0 ? (int)((unsigned long long)(S / 4) * w->t_done + (unsigned long long)(S - 1) - step.m0) : 0;
+    a.tr = w->plan.tr; a.t_first = (long long)w->t_done;
+    a.cfg = w->cfg; a.tw = w->d_tw.get(); a.ring = w->d_ring.get(); a.sc = w->d_sc.get(); a.hi = w->d_hi.get();
+    a.events = w->d_events.get(); a.counts = w->d_counts.get();
+    if (a.ns < 0 || a.ns > ft_steps_per_call(w->max_out, S) || a.e_first < 0 || a.e_first >= (w->t_done ? S / 4 : S)) {
+      set_last_error("%s: the step count lost its place (%d steps, first at output %d)", who, a.ns, a.e_first);
+      return PYSDR_ERR_STATE;
+    }
+    if (a.ns == 0) PYSDR_HIP_CHECK(hipMemsetAsync(a.counts, 0, nfine * sizeof(int32_t), st));   // outputs but no step: only the history rolls
+    rc = launch_ft_steps(Mode::kLdpcSource, S, a, st);
+    if (rc) return rc;
+    w->t_done = t1;
+    *n_out = nf;
+    if (steps) steps[1] = a.ns;
+    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (events)
+      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)words * sizeof(int32_t),
+                                       (size_t)words * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
+  }
+  if (counts || events || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
+  return PYSDR_OK;
+}
+
+template <class W>
+int ft_fetch(W* w, const char* who, const int* rows, int nrows, int32_t* events, long long pitch) {
+  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  return client_fetch_events(w, who, "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap * kFtEventWords, rows, nrows, events, pitch);
+}
+
+template <class W>
+int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, float* out) {
+  using Mode = typename W::Mode;
+  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (n < 0 || n > kFtLlrMax || (n > 0 && (!F || !t0 || !out))) {
+    set_last_error("%s: n %d outside [0, %d] / NULL F, t0 or out", who, n, kFtLlrMax);
+    return PYSDR_ERR_ARG;
+  }
+  std::lock_guard<std::mutex> lk(w->mu);
+  const long long done = (long long)w->t_done;
+  for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
+    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+      set_last_error("%s: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the "
+                     "ring (%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done,
+                     t0[i] + kFtLag<Mode>, w->plan.tr);
+      return F[i] < 0 || F[i] >= w->plan.nfine ? PYSDR_ERR_ARG : PYSDR_ERR_STATE;
+    }
+  if (n == 0) return PYSDR_OK;
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // h_cand may still feed an earlier copy
+  w->h_cand.resize((size_t)n * 2);
+  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % w->plan.tr); }
+  PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  FtLlrArgs a{};
+  a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.n = n; a.cand = w->d_cand.get(); a.out = w->d_llr.get();
+  const int rc = launch_ft_llr(Mode::kLdpcSource, a, st);
+  if (rc) return rc;
+  PYSDR_HIP_CHECK(hipMemcpyAsync(out, a.out, (size_t)n * kFtBits * sizeof(float), hipMemcpyDeviceToHost, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  return PYSDR_OK;
+}
+
+template <class W>
+int ft_state(W* w, const char* who, float* sc, int32_t* hits, float* ring, long long* t_done) {
+  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  std::lock_guard<std::mutex> lk(w->mu);
+  PYSDR_HIP_CHECK(hipSetDevice(w->device));
+  hipStream_t st = w->stream;
+  const size_t nf = (size_t)w->plan.nfine;
+  if (sc) PYSDR_HIP_CHECK(hipMemcpyAsync(sc, w->d_sc.get(), (size_t)kFtKeep * nf * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (hits) PYSDR_HIP_CHECK(hipMemcpyAsync(hits, w->d_hi.get(), (size_t)kFtKeep * nf * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (ring)
+    PYSDR_HIP_CHECK(hipMemcpyAsync(ring, w->d_ring.get(), (size_t)w->nk * (size_t)w->plan.tr * (size_t)w->plan.nb * sizeof(float),
+                                   hipMemcpyDeviceToHost, st));
+  PYSDR_HIP_CHECK(hipStreamSynchronize(st));
+  if (t_done) *t_done = (long long)w->t_done;
+  return PYSDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- FT8 ---------------------------------------------------------------------------------------------------------------
+int pysdr_ft8_plan(int nk, int S, int max_out, const pysdr_ft8_cfg* cfg, int32_t out[8]) {
+  return ft_plan_call<Ft8Mode>("pysdr_ft8_plan", nk, S, max_out, ft_cfg(cfg), out);
+}
+int pysdr_ft8_create(pysdr_chan* ch, int S, const pysdr_ft8_cfg* cfg, const float* tw, int max_out, pysdr_ft8** out) {
+  return ft_create("pysdr_ft8_create", "pysdr_ft8_plan", ch, S, ft_cfg(cfg), tw, max_out, out);
+}
+void pysdr_ft8_destroy(pysdr_ft8* w) { client_destroy(w); }
+int pysdr_ft8_reset(pysdr_ft8* w) { return ft_reset(w, "pysdr_ft8_reset"); }
+int pysdr_ft8_sync(pysdr_ft8* w) { return ft_sync_call(w, "pysdr_ft8_sync"); }
+int pysdr_ft8_process(pysdr_ft8* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                      long long ev_pitch, long long* steps) {
+  return ft_process(w, "pysdr_ft8_process", iq, n, on_device, n_out, counts, events, ev_pitch, steps);
+}
+int pysdr_ft8_fetch(pysdr_ft8* w, const int* rows, int nrows, int32_t* events, long long pitch) {
+  return ft_fetch(w, "pysdr_ft8_fetch", rows, nrows, events, pitch);
+}
+int pysdr_ft8_llr(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, float* out) { return ft_llr(w, "pysdr_ft8_llr", F, t0, n, out); }
+int pysdr_ft8_state(pysdr_ft8* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
+  return ft_state(w, "pysdr_ft8_state", sc, hits, ring, t_done);
+}
+int pysdr_ft8_decode(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                     float* post) {
+  return ldpc_decode_ring(w, "pysdr_ft8_decode", F, t0, n, cfg, status, bits, post);
+}
+int pysdr_ft8_decode_llr(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+  return ldpc_decode_llr(w, "pysdr_ft8_decode_llr", llr, n, cfg, status, bits, post);
+}
+int pysdr_ft8_decode_osd(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                         uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_ring(w, "pysdr_ft8_decode_osd", F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+int pysdr_ft8_decode_llr_osd(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                             float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_llr(w, "pysdr_ft8_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+int pysdr_ft8_report(pysdr_ft8* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
+  return report_frames(w, "pysdr_ft8_report", F, t0, bits, n, power, errs);
+}
+int pysdr_ft8_floor(pysdr_ft8* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft8_floor", t_end, nsym, out); }
+
+// ---- FT4 ---------------------------------------------------------------------------------------------------------------
+int pysdr_ft4_plan(int nk, int S, int max_out, const pysdr_ft4_cfg* cfg, int32_t out[8]) {
+  return ft_plan_call<Ft4Mode>("pysdr_ft4_plan", nk, S, max_out, ft_cfg(cfg), out);
+}
+int pysdr_ft4_create(pysdr_chan* ch, int S, const pysdr_ft4_cfg* cfg, const float* tw, int max_out, pysdr_ft4** out) {
+  return ft_create("pysdr_ft4_create", "pysdr_ft4_plan", ch, S, ft_cfg(cfg), tw, max_out, out);
+}
+void pysdr_ft4_destroy(pysdr_ft4* w) { client_destroy(w); }
+int pysdr_ft4_reset(pysdr_ft4* w) { return ft_reset(w, "pysdr_ft4_reset"); }
+int pysdr_ft4_sync(pysdr_ft4* w) { return ft_sync_call(w, "pysdr_ft4_sync"); }
+int pysdr_ft4_process(pysdr_ft4* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                      long long ev_pitch, long long* steps) {
+  return ft_process(w, "pysdr_ft4_process", iq, n, on_device, n_out, counts, events, ev_pitch, steps);
+}
+int pysdr_ft4_fetch(pysdr_ft4* w, const int* rows, int nrows, int32_t* events, long long pitch) {
+  return ft_fetch(w, "pysdr_ft4_fetch", rows, nrows, events, pitch);
+}
+int pysdr_ft4_llr(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, float* out) { return ft_llr(w, "pysdr_ft4_llr", F, t0, n, out); }
+int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
+  return ft_state(w, "pysdr_ft4_state", sc, hits, ring, t_done);
+}
+int pysdr_ft4_decode(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                     float* post) {
+  return ldpc_decode_ring(w, "pysdr_ft4_decode", F, t0, n, cfg, status, bits, post);
+}
+int pysdr_ft4_decode_llr(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
+  return ldpc_decode_llr(w, "pysdr_ft4_decode_llr", llr, n, cfg, status, bits, post);
+}
+int pysdr_ft4_decode_osd(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                         uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_ring(w, "pysdr_ft4_decode_osd", F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+int pysdr_ft4_decode_llr_osd(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
+                             float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return ldpc_decode_llr(w, "pysdr_ft4_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+}
+int pysdr_ft4_report(pysdr_ft4* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
+  return report_frames(w, "pysdr_ft4_report", F, t0, bits, n, power, errs);
+}
+int pysdr_ft4_floor(pysdr_ft4* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft4_floor", t_end, nsym, out); }
+
+// ---- the decoders' and the report's plans, which need no skimmer ---------------------------------------------------------
+int pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_ldpc_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!ldpc_cfg_ok(cfg)) {
+    set_last_error("pysdr_ldpc_plan: a cfg outside the rules (NULL; iters in [1, %d]; alpha finite and in (0, 1])", kLdpcItersMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kLdpcThreads; out[1] = kLdpcLdsBytes; out[2] = kLdpcMax; out[3] = cfg->iters;
+  return PYSDR_OK;
+}
+
+int pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_osd_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!osd_cfg_ok(cfg)) {
+    set_last_error("pysdr_osd_plan: a cfg outside the rule (NULL; order in [0, %d])", kOsdOrderMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kOsdThreads; out[1] = kOsdLdsBytes; out[2] = osd_patterns(cfg->order); out[3] = kLdpcMax;
+  return PYSDR_OK;
+}
+
+int pysdr_report_plan(int mode, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_report_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!report_plan(mode, out)) {
+    set_last_error("pysdr_report_plan: mode %d is neither PYSDR_REPORT_FT8 nor PYSDR_REPORT_FT4", mode);
+    return PYSDR_ERR_ARG;
+  }
+  return PYSDR_OK;
+}
+
+}  // extern "C"

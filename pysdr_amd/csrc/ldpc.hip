@@ -9,8 +9,8 @@
 // between two words, so that the one being read is never the one being cleared.  The new c of a final iteration are
 // computed and never read.  The steps are ldpc_plan.h's, the very functions the scalar transcription runs.
 // Three sources of soft bits through one template flag: a device buffer [n][174], or the spectrum ring of an FT8 or an
-// FT4 skimmer read through ft8_llr_bit / ft4_llr_bit, so that soft bits never touch global memory.
-#include "ft4_plan.h"
+// FT4 skimmer read through ft_llr_bit of the source's mode, so that soft bits never touch global memory.
+#include "ft_plan.h"
 #include "ldpc_plan.h"
 #include "objects_plan.h"
 
@@ -38,7 +38,7 @@ __global__ __launch_bounds__(kLdpcThreads) void ldpc_decode_kernel(const LdpcArg
       const int F = a.cand[2 * cand], slot0 = a.cand[2 * cand + 1];
       const int row = F / a.nsub, j = F - row * a.nsub;
       const float* ring = a.ring + (size_t)row * (size_t)a.tr * (size_t)a.nb;
-      llr = SRC == kLdpcFromFt8Ring ? ft8_llr_bit(ring, a.tr, a.nb, slot0, j, tid) : ft4_llr_bit(ring, a.tr, a.nb, slot0, j, tid);
+      llr = ft_llr_bit<FtRingMode<SRC>>(ring, a.tr, a.nb, slot0, j, tid);
     }
     e0 = kLdpc.edge[tid][0]; e1 = kLdpc.edge[tid][1]; e2 = kLdpc.edge[tid][2];
   }

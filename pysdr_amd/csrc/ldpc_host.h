@@ -1,4 +1,4 @@
-// The host half of the LDPC decoder, shared by the FT8 and the FT4 skimmer (api_ft8.hip, api_ft4.hip) over chan_client.h:
+// The host half of the LDPC decoder, shared by the FT8 and the FT4 skimmer (api_ft.hip) over chan_client.h:
 // the result buffers a skimmer owns, and the two calls -- candidates from the spectrum ring, soft bits from the host --
 // written once for both objects, which name their fields alike (plan, t_done, d_ring, d_cand, h_cand, d_llr).  A call may
 // ask for the second stage, ordered-statistics decoding (osd.hip), launched behind min-sum on the same stream.  Every
@@ -81,20 +81,21 @@ int ldpc_run(W* w, int source, LdpcArgs& a, const pysdr_ldpc_cfg* cfg, int32_t* 
   return PYSDR_OK;
 }
 
-// Candidates (F[i], t0[i]) from the ring.  `ok`: the skimmer's rule for a candidate (ft8_llr_ok / ft4_llr_ok); lag: the
-// last step of a frame behind its first, for the message.
-template <class W, class Ok>
-int ldpc_decode_ring(W* w, const char* who, int source, Ok ok, int lag, const int32_t* F, const long long* t0, int n,
-                     const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post, const OsdCall& osd = kNoOsd) {
+// Candidates (F[i], t0[i]) from the ring.  The skimmer's mode (W::Mode, ft_plan.h) gives the rule for a candidate, the
+// last step of a frame behind its first, for the message, and the kernels' source.
+template <class W>
+int ldpc_decode_ring(W* w, const char* who, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                     uint8_t* bits, float* post, const OsdCall& osd = kNoOsd) {
+  using Mode = typename W::Mode;
   if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
   if (!ldpc_call_ok(who, n, cfg, F, t0, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   std::lock_guard<std::mutex> lk(w->mu);
   const long long done = (long long)w->t_done;
   for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
-    if (!ok(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
       set_last_error("%s: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the ring "
-                     "(%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done, t0[i] + lag,
-                     w->plan.tr);
+                     "(%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done,
+                     t0[i] + kFtLag<Mode>, w->plan.tr);
       return F[i] < 0 || F[i] >= w->plan.nfine ? PYSDR_ERR_ARG : PYSDR_ERR_STATE;
     }
   if (n == 0) return PYSDR_OK;
@@ -108,7 +109,7 @@ int ldpc_decode_ring(W* w, const char* who, int source, Ok ok, int lag, const in
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   LdpcArgs a{};
   a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.cand = w->d_cand.get(); a.n = n;
-  return ldpc_run(w, source, a, cfg, status, bits, post, osd);
+  return ldpc_run(w, Mode::kLdpcSource, a, cfg, status, bits, post, osd);
 }
 
 // Soft bits from the host, through the skimmer's soft-bit buffer.

@@ -11,6 +11,7 @@
 #include <cstdint>
 
 #include "../../include/pysdr_hip.h"
+#include "ft_plan.h"
 
 #if defined(__HIPCC__)
 #define PYSDR_LDPC_HD __host__ __device__
@@ -280,9 +281,7 @@ inline void ldpc_decode_scalar(const float* llr, int iters, float alpha, int32_t
     for (int n = 0; n < kLdpcN; ++n) post[n] = tot[n];
 }
 
-// ---- kernel arguments and the launch (ldpc.hip) ----------------------------------------------------------------------
-enum LdpcSource { kLdpcFromBuffer = 0, kLdpcFromFt8Ring = 1, kLdpcFromFt4Ring = 2 };
-
+// ---- kernel arguments and the launch (ldpc.hip); the sources of soft bits are ft_plan.h's LdpcSource -------------------
 struct LdpcArgs {
   const float* llr;        // kLdpcFromBuffer: [n][174]
   const float* ring;       // the ring sources: the skimmer's spectrum ring [nk][tr][nb] ...

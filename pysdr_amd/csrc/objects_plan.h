@@ -192,17 +192,11 @@ int launch_psk_decode(int S, const PskArgs& a, hipStream_t st);
 struct FskArgs;
 int launch_fsk_decode(int S, const FskArgs& a, hipStream_t st);
 
-// ---- FT8 skimmer (ft8.hip, host half api_ft8.hip; plan, steps and kernel arguments: ft8_plan.h) ------------------------
-struct Ft8Args;
-struct Ft8LlrArgs;
-int launch_ft8_steps(int S, const Ft8Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
-int launch_ft8_llr(const Ft8LlrArgs& a, hipStream_t st);
-
-// ---- FT4 skimmer (ft4.hip, host half api_ft4.hip; plan, steps and kernel arguments: ft4_plan.h) ------------------------
-struct Ft4Args;
-struct Ft4LlrArgs;
-int launch_ft4_steps(int S, const Ft4Args& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks
-int launch_ft4_llr(const Ft4LlrArgs& a, hipStream_t st);
+// ---- FT8 and FT4 skimmers (ft.hip, host half api_ft.hip; modes, plan, steps and kernel arguments: ft_plan.h) ----------------
+struct FtArgs;
+struct FtLlrArgs;
+int launch_ft_steps(int source, int S, const FtArgs& a, hipStream_t st);   // spectrum of the call's steps, then sync and peaks; source:
+int launch_ft_llr(int source, const FtLlrArgs& a, hipStream_t st);         // the mode's LdpcSource
 
 // ---- LDPC(174,91) decoder (ldpc.hip, host half ldpc_host.h; tables, steps and kernel arguments: ldpc_plan.h) -----------
 struct LdpcArgs;

@@ -10,7 +10,7 @@
 //   winner       the least (distance, k) by a shuffle butterfly; one lane does the CRC, the packing and the stores.
 // The workgroup is one wavefront, so its barriers order the LDS between lanes and cost no wait; every one of them is
 // reached by all 64 lanes.  The steps are osd_plan.h's, the very functions the scalar transcription runs.
-#include "ft4_plan.h"
+#include "ft_plan.h"
 #include "objects_plan.h"
 #include "osd_plan.h"
 
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kOsdThreads) void osd_decode_kernel(const OsdArgs a
       const int F = a.cand[2 * cand], slot0 = a.cand[2 * cand + 1];
       const int row = F / a.nsub, j = F - row * a.nsub;
       const float* ring = a.ring + (size_t)row * (size_t)a.tr * (size_t)a.nb;
-      x = SRC == kLdpcFromFt8Ring ? ft8_llr_bit(ring, a.tr, a.nb, slot0, j, n) : ft4_llr_bit(ring, a.tr, a.nb, slot0, j, n);
+      x = ft_llr_bit<FtRingMode<SRC>>(ring, a.tr, a.nb, slot0, j, n);
     }
     s_key[n] = osd_key(x);
     s_hard[n] = x > 0.f ? 1 : 0;

@@ -81,7 +81,7 @@ int launch_frame_report(int mode, const ReportArgs& a, hipStream_t st) {
 
 int launch_ring_floor(const FloorArgs& a, hipStream_t st) {
   if (!a.ring || !a.out || a.nk < 1 || a.nb < 1 || a.nb > kFloorThreads || !floor_nsym_ok(a.nsym) || a.slot_end < 0 || a.slot_end >= a.tr ||
-      kFt8StepsPerSym * (a.nsym - 1) >= a.tr) {
+      kFtStepsPerSym * (a.nsym - 1) >= a.tr) {
     set_last_error("launch_ring_floor: %d rows of %d bins, %d symbols ending in slot %d of %d", a.nk, a.nb, a.nsym, a.slot_end, a.tr);
     return PYSDR_ERR_ARG;
   }

@@ -1,5 +1,5 @@
 // The host half of the frame report and the row floor, shared by the FT8 and the FT4 skimmer
-// (api_ft8.hip, api_ft4.hip) over chan_client.h as ldpc_host.h is: the buffers a skimmer owns for it, and the two calls,
+// (api_ft.hip) over chan_client.h as ldpc_host.h is: the buffers a skimmer owns for it, and the two calls,
 // written once for both objects, which name their fields alike (plan, t_done, d_ring).  The mask of places a candidate may
 // read is computed here, per candidate, by report_plan.h's pure function.  Every check comes before any launch: a refusal
 // changes nothing.  Host only; not part of the public ABI.
@@ -30,11 +30,12 @@ inline int report_bufs_ready(ReportBufs* b, int nk, int nb) {
   return PYSDR_OK;
 }
 
-// Candidates (F[i], t0[i]) with their message bits.  `ok`: the skimmer's rule for a candidate (ft8_llr_ok / ft4_llr_ok);
-// lag: the last step of a frame behind its first.
-template <class W, class Ok>
-int report_frames(W* w, const char* who, int mode, Ok ok, int lag, const int32_t* F, const long long* t0, const uint8_t* bits, int n,
-                  float* power, int32_t* errs) {
+// Candidates (F[i], t0[i]) with their message bits.  The skimmer's mode (W::Mode, ft_plan.h) gives the rule for a
+// candidate, the last step of a frame behind its first and the kernel's mode.
+template <class W>
+int report_frames(W* w, const char* who, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
+  using Mode = typename W::Mode;
+  constexpr int lag = kFtLag<Mode>;
   if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
   if (!report_n_ok(n) || (n > 0 && (!F || !t0 || !bits || !power || !errs))) {
     set_last_error("%s: n %d outside [0, %d] / NULL F, t0, bits, power or errs", who, n, kReportMax);
@@ -43,7 +44,7 @@ int report_frames(W* w, const char* who, int mode, Ok ok, int lag, const int32_t
   std::lock_guard<std::mutex> lk(w->mu);
   const long long done = (long long)w->t_done;
   for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
-    if (!ok(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
       set_last_error("%s: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the ring "
                      "(%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done, t0[i] + lag,
                      w->plan.tr);
@@ -74,7 +75,7 @@ int report_frames(W* w, const char* who, int mode, Ok ok, int lag, const int32_t
   ReportArgs a{};
   a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.nfine = w->plan.nfine; a.n = n;
   a.cand = w->report.d_cand.get(); a.power = w->report.d_power.get(); a.errs = w->report.d_errs.get();
-  rc = launch_frame_report(mode, a, st);
+  rc = launch_frame_report(Mode::kReportMode, a, st);
   if (rc) return rc;
   PYSDR_HIP_CHECK(hipMemcpyAsync(power, a.power, (size_t)n * kReportCols * sizeof(float), hipMemcpyDeviceToHost, st));
   PYSDR_HIP_CHECK(hipMemcpyAsync(errs, a.errs, (size_t)n * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -94,7 +95,7 @@ int report_floor(W* w, const char* who, long long t_end, int nsym, float* out) {
   const long long done = (long long)w->t_done;
   if (!floor_ok(t_end, nsym, done, w->plan.tr)) {
     set_last_error("%s: the steps %lld to %lld are not all complete and in the ring (%lld steps done, the ring holds %d)", who,
-                   t_end - kFt8StepsPerSym * (long long)(nsym - 1), t_end, done, w->plan.tr);
+                   t_end - kFtStepsPerSym * (long long)(nsym - 1), t_end, done, w->plan.tr);
     return PYSDR_ERR_STATE;
   }
   PYSDR_HIP_CHECK(hipSetDevice(w->device));

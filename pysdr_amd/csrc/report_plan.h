@@ -11,12 +11,10 @@
 // Plain C++: nothing here calls the HIP runtime.
 #pragma once
 
-#include "ft4_plan.h"
+#include "ft_plan.h"
 #include "ldpc_plan.h"
 
 namespace pysdr {
-
-enum ReportMode { kReportFt8 = PYSDR_REPORT_FT8, kReportFt4 = PYSDR_REPORT_FT4 };
 
 constexpr int kReportThreads = 128;        // one workgroup per candidate: lane k < 79 (103) owns symbol k
 constexpr int kReportMax = 4096;           // candidates of one call
@@ -31,20 +29,19 @@ constexpr float kReportMissing = -1.0f;    // a place that may not be read
 constexpr int kFloorThreads = 64;          // one workgroup per row, a lane per bin: NB <= 62
 constexpr int kFloorSymsMax = 128;
 
-template <int MODE> struct ReportGeom;
-template <> struct ReportGeom<kReportFt8> {
-  static constexpr int kSyms = kFt8Syms, kTones = kFt8Tones, kLag = kFt8Lag, kExtra = 14;
-};
-template <> struct ReportGeom<kReportFt4> {
-  static constexpr int kSyms = kFt4Syms, kTones = kFt4Tones, kLag = kFt4Lag, kExtra = 6;
+// ReportMode (ft_plan.h) names the mode; its numbers are the mode's own
+template <int MODE> struct ReportGeom {
+  using Mode = FtReportMode<MODE>;
+  static constexpr int kSyms = Mode::kSyms, kTones = Mode::kTones, kLag = kFtLag<Mode>, kExtra = kFtExtra<Mode>;
 };
 static_assert(ReportGeom<kReportFt8>::kSyms <= kReportThreads && ReportGeom<kReportFt4>::kSyms <= kReportThreads, "a lane per symbol");
-static_assert(ReportGeom<kReportFt4>::kSyms <= kReportPitch && kReportPitch % 2 == 1, "a column holds every symbol");
+static_assert(ReportGeom<kReportFt8>::kSyms <= kReportPitch && ReportGeom<kReportFt4>::kSyms <= kReportPitch && kReportPitch % 2 == 1,
+              "a column holds every symbol");
 static_assert(kLdpcN <= kReportCwBytes && kLdpcK <= kReportThreads, "a lane per systematic bit");
-static_assert(96 / 2 + 14 <= kFloorThreads && 72 / 2 + 6 <= kFloorThreads, "a lane per bin");
+static_assert(FtGeom<Ft8Mode, Ft8Mode::kS1>::kNb <= kFloorThreads && FtGeom<Ft4Mode, Ft4Mode::kS1>::kNb <= kFloorThreads, "a lane per bin");
 
 constexpr bool report_mode_ok(int mode) { return mode == kReportFt8 || mode == kReportFt4; }
-constexpr int report_syms(int mode) { return mode == kReportFt8 ? kFt8Syms : kFt4Syms; }
+constexpr int report_syms(int mode) { return mode == kReportFt8 ? Ft8Mode::kSyms : Ft4Mode::kSyms; }
 constexpr bool report_n_ok(long long n) { return n >= 0 && n <= kReportMax; }
 
 // ---- the message, the codeword, the tones ------------------------------------------------------------------------------
@@ -53,47 +50,47 @@ inline void report_words(const uint8_t* bits12, uint32_t w[3]) {
   for (int k = 0; k < 3; ++k)
     w[k] = ((uint32_t)bits12[4 * k] << 24) | ((uint32_t)bits12[4 * k + 1] << 16) | ((uint32_t)bits12[4 * k + 2] << 8) | (uint32_t)bits12[4 * k + 3];
 }
-PYSDR_FT8_HD inline int report_popc(uint32_t v) {
+PYSDR_FT_HD inline int report_popc(uint32_t v) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __popc(v);
 #else
   return __builtin_popcount(v);
 #endif
 }
-PYSDR_FT8_HD inline uint8_t report_msg_bit(uint32_t w0, uint32_t w1, uint32_t w2, int i) {
+PYSDR_FT_HD inline uint8_t report_msg_bit(uint32_t w0, uint32_t w1, uint32_t w2, int i) {
   const uint32_t w = i < 32 ? w0 : (i < 64 ? w1 : w2);
   return (uint8_t)((w >> (31 - (i & 31))) & 1u);
 }
 // parity bit j < 83 (codeword bit 91 + j): the generator's row and the message, AND, population count; bits beyond the 91st
 // meet zeros in the row
-PYSDR_FT8_HD inline uint8_t report_parity(uint32_t w0, uint32_t w1, uint32_t w2, int j) {
+PYSDR_FT_HD inline uint8_t report_parity(uint32_t w0, uint32_t w1, uint32_t w2, int j) {
   return (uint8_t)((report_popc(w0 & kLdpc.gen[j][0]) + report_popc(w1 & kLdpc.gen[j][1]) + report_popc(w2 & kLdpc.gen[j][2])) & 1);
 }
 // Tone of frame symbol k from the codeword (a byte per bit); *sync: k is a Costas symbol.
 template <int MODE>
-PYSDR_FT8_HD inline int report_tone(const uint8_t* cw, int k, bool* sync) {
+PYSDR_FT_HD inline int report_tone(const uint8_t* cw, int k, bool* sync) {
   if (MODE == kReportFt8) {
     const int blk = k / 36, r = k - 36 * blk;               // the arrays begin at 0, 36, 72
     *sync = r < 7;
-    if (r < 7) return ft8_costas(r);
-    const int d = k - 7 * (blk + 1);                        // data symbol: ft8_data_sym's inverse
-    return ft8_gray(4 * cw[3 * d] + 2 * cw[3 * d + 1] + cw[3 * d + 2]);
+    if (r < 7) return Ft8Mode::costas(r);
+    const int d = k - 7 * (blk + 1);                        // data symbol: Ft8Mode::data_sym's inverse
+    return Ft8Mode::gray(4 * cw[3 * d] + 2 * cw[3 * d + 1] + cw[3 * d + 2]);
   }
   const int blk = k / 33, r = k - 33 * blk;                 // 0, 33, 66, 99
   *sync = r < 4;
-  if (r < 4) return ft4_costas(4 * blk + r);
+  if (r < 4) return Ft4Mode::costas(4 * blk + r);
   const int d = k - 4 * (blk + 1);
-  return ft4_gray(2 * cw[2 * d] + cw[2 * d + 1]);
+  return Ft4Mode::gray(2 * cw[2 * d] + cw[2 * d + 1]);
 }
 
 // ---- which places a call may read ----------------------------------------------------------------------------------------
 // A frame that begins at step t is whole and in the ring: pysdr_*_llr's rule for t0, applied to t0 + dt.
-PYSDR_FT8_HD constexpr bool report_time_ok(long long t, int lag, long long t_done, int tr) {
+PYSDR_FT_HD constexpr bool report_time_ok(long long t, int lag, long long t_done, int tr) {
   return t >= 0 && t + lag < t_done && t_done - t <= tr;
 }
-PYSDR_FT8_HD constexpr int report_wrap(long long F, int nfine) { return (int)(((F % nfine) + nfine) % nfine); }
+PYSDR_FT_HD constexpr int report_wrap(long long F, int nfine) { return (int)(((F % nfine) + nfine) % nfine); }
 // bit 3 (dt + 1) + (dF + 1) is set where place (dt, dF) may be read; `circular`: the raster is the whole circle (nk == M)
-PYSDR_FT8_HD constexpr int report_mask(long long F, long long t0, long long t_done, int nfine, int tr, int lag, bool circular) {
+PYSDR_FT_HD constexpr int report_mask(long long F, long long t0, long long t_done, int nfine, int tr, int lag, bool circular) {
   int m = 0;
   for (int dt = -1; dt <= 1; ++dt)
     for (int dF = -1; dF <= 1; ++dF)
@@ -106,13 +103,13 @@ PYSDR_FT8_HD constexpr int report_mask(long long F, long long t0, long long t_do
 // where the mask forbids the place: never read), v[9] the symbol's tones at the candidate's own place added ascending;
 // *miss: the sent tone is not strictly greater than every other tone there.
 template <int MODE>
-PYSDR_FT8_HD inline void report_symbol(const float* ring, int tr, int nb, int nsub, int nfine, int F, int slot0, int mask,
+PYSDR_FT_HD inline void report_symbol(const float* ring, int tr, int nb, int nsub, int nfine, int F, int slot0, int mask,
                                        const uint8_t* cw, int k, float* v, bool* miss, bool* sync) {
   constexpr int T = ReportGeom<MODE>::kTones;
   const int tone = report_tone<MODE>(cw, k, sync);
   {
     const int row = F / nsub, j = F - row * nsub;
-    const int sl = (slot0 + kFt8StepsPerSym * k) % tr;
+    const int sl = (slot0 + kFtStepsPerSym * k) % tr;
     const float* p = ring + ((size_t)row * (size_t)tr + (size_t)sl) * (size_t)nb + j;
     float pt[T];
 #pragma unroll
@@ -138,14 +135,14 @@ PYSDR_FT8_HD inline void report_symbol(const float* ring, int tr, int nb, int ns
     if ((mask >> place) & 1) {
       const int Fn = report_wrap((long long)F + dF, nfine);
       const int row = Fn / nsub, j = Fn - row * nsub;
-      const int sl = (slot0 + dt + kFt8StepsPerSym * k + tr) % tr;
+      const int sl = (slot0 + dt + kFtStepsPerSym * k + tr) % tr;
       e = ring[((size_t)row * (size_t)tr + (size_t)sl) * (size_t)nb + j + 2 * tone];
     }
     v[place] = e;
   }
 }
 // A column of nsym values added ascending, from the first; a place that was not read is exactly -1.
-PYSDR_FT8_HD inline float report_column(const float* col, int nsym, bool read) {
+PYSDR_FT_HD inline float report_column(const float* col, int nsym, bool read) {
   if (!read) return kReportMissing;
   float acc = col[0];
   for (int k = 1; k < nsym; ++k) acc = acc + col[k];
@@ -179,16 +176,16 @@ inline void report_scalar(const float* ring, int tr, int nb, int nsub, int nfine
 
 // ---- the row floor -----------------------------------------------------------------------------------------------------------
 // The steps t_end - 4 (nsym - 1) .. t_end in fours are complete and in the ring.
-PYSDR_FT8_HD constexpr bool floor_nsym_ok(long long nsym) { return nsym >= 1 && nsym <= kFloorSymsMax; }
-PYSDR_FT8_HD constexpr bool floor_ok(long long t_end, long long nsym, long long t_done, int tr) {
-  return floor_nsym_ok(nsym) && t_end - kFt8StepsPerSym * (nsym - 1) >= 0 && t_end < t_done &&
-         t_done - (t_end - kFt8StepsPerSym * (nsym - 1)) <= tr;
+PYSDR_FT_HD constexpr bool floor_nsym_ok(long long nsym) { return nsym >= 1 && nsym <= kFloorSymsMax; }
+PYSDR_FT_HD constexpr bool floor_ok(long long t_end, long long nsym, long long t_done, int tr) {
+  return floor_nsym_ok(nsym) && t_end - kFtStepsPerSym * (nsym - 1) >= 0 && t_end < t_done &&
+         t_done - (t_end - kFtStepsPerSym * (nsym - 1)) <= tr;
 }
 // Bin b of a row's floor: rows[tr][nb] is the row's ring, slot_end = t_end mod tr; the span is shorter than the ring.
-PYSDR_FT8_HD inline float floor_bin(const float* rows, int tr, int nb, int slot_end, int nsym, int b) {
+PYSDR_FT_HD inline float floor_bin(const float* rows, int tr, int nb, int slot_end, int nsym, int b) {
   float acc = 0.f;
   for (int i = 0; i < nsym; ++i) {
-    const int sl = (slot_end - kFt8StepsPerSym * (nsym - 1 - i) + tr) % tr;
+    const int sl = (slot_end - kFtStepsPerSym * (nsym - 1 - i) + tr) % tr;
     const float p = rows[(size_t)sl * (size_t)nb + b];
     acc = i == 0 ? p : acc + p;
   }

@@ -1,5 +1,5 @@
-"""FT4 skimmer: four Costas arrays and soft bits on a fine raster of the band (kernels ``ft4.hip``, host
-half ``api_ft4.hip``).  4-GFSK at 125 / 6 baud, tones one baud apart, 103 symbols of which 16 are four different Costas
+"""FT4 skimmer: four Costas arrays and soft bits on a fine raster of the band (kernels ``ft.hip``, host
+half ``api_ft.hip``).  4-GFSK at 125 / 6 baud, tones one baud apart, 103 symbols of which 16 are four different Costas
 arrays.  A channelizer with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders
 run on the device, one every 10.4 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The
 device finds every frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` it
@@ -8,19 +8,19 @@ bits as decoded; the bit scrambler FT4 applies before the CRC is not here, so ``
 settings, plan and tables; the finder and the soft bits' helpers are ``ft8.py``'s as they are."""
 from __future__ import annotations
 
-import ctypes as C
 import sys
 
 import numpy as np
 
-from . import _lib
-from . import channelizer as _chan
 from . import psk as _psk
 from ._lib import Ft4Cfg
 from . import ft8 as _ft8
 from .ft8 import FT8_Decoders, FT8_Skimmer, hard_bits, owners, unit_llr, unpack  # noqa: F401  (this mode's too)
+from .ft8 import cfg_dict, steps_done, tables  # noqa: F401  (no mode's number is in them)
 from .ft8 import delta, noise_floor, noise_of, refine, snr_db, spots  # noqa: F401  (the frame report's host half, DESIGN.md 3 item 26)
 
+NAME, PLAN_CALL = "FT4", "pysdr_ft4_plan"
+_MODE = sys.modules[__name__]
 BAUD = 125.0 / 6.0
 COSTAS = ((0, 1, 3, 2), (1, 0, 2, 3), (2, 3, 1, 0), (3, 2, 0, 1))   # at symbols 0, 33, 66 and 99
 GRAY4 = (0, 1, 3, 2)                             # value v is sent on tone GRAY4[v]
@@ -55,17 +55,7 @@ def spot_line(rec, f_centre=0.0):
 def shape(fs):
     """-> (S, D, M): S = 48 row samples per symbol if fs / (48 baud) is an integer D and the channelizer accepts M = 4 D,
     otherwise S = 72 likewise, otherwise ValueError (``ft8.shape``'s rules)."""
-    for S in SHAPES:
-        d = float(fs) / (S * BAUD)
-        D = int(round(d))
-        if D < 1 or abs(d - D) > 1e-9 * max(d, 1.0):
-            continue
-        try:
-            _chan.plan(4 * D, D, 16 * D)
-        except _lib.PysdrError:
-            continue
-        return S, D, 4 * D
-    raise ValueError(f"no FT4 raster for fs = {fs}: fs / 1000 or fs / 1500 must be an integer D with M = 4 D a channelizer size")
+    return _ft8.mode_shape(_MODE, fs)
 
 
 def prototype(fs, M, S):
@@ -78,24 +68,7 @@ def fine_channelizer(fs, band, device=0, max_in=1 << 22):
     """A ``fine.FineChannelizer`` for ``FT4_Skimmer(fs, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4 apart whose
     centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 48 where ``fine.shape`` finds a shape, else 72; M2 / D2 =
     4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
-    from . import fine
-    err = None
-    for S in SHAPES:
-        try:
-            M1, D1, M2, D2 = fine.shape(fs, S * BAUD, 4)
-        except ValueError as e:
-            err = e
-            continue
-        h2 = prototype(float(fs) / D1, M2, S)
-        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
-                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
-    raise ValueError(f"no FT4 raster in two stages for fs = {fs}: {err}")
-
-
-def tables(S):
-    """-> tw float32 [4 S][2] = (cos, -sin)(2 pi i / NT): derived in float64, rounded once"""
-    t = 2 * np.pi * np.arange(4 * S) / (4 * S)
-    return np.ascontiguousarray(np.stack((np.cos(t), -np.sin(t)), axis=1), np.float32)
+    return _ft8.mode_fine_channelizer(_MODE, fs, band, device, max_in)
 
 
 def params(smin=4.0, hmin=12, pmax=1e18):
@@ -103,21 +76,11 @@ def params(smin=4.0, hmin=12, pmax=1e18):
     return Ft4Cfg(smin=float(np.float32(smin)), hmin=int(hmin), pmax=float(np.float32(pmax)))
 
 
-def cfg_dict(cfg):
-    return {k: getattr(cfg, k) for k, _ in Ft4Cfg._fields_}
-
-
 def plan(nk, S, max_out, cfg):
     """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
     samples, event cap per decoder and call, workgroups, decoders per row, ring depth in steps.  Raises PysdrError
     outside the rules."""
-    v = _lib.plan_call("pysdr_ft4_plan", 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
-    return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6], "tr": v[7]}
-
-
-def steps_done(n_out, S):
-    """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1"""
-    return (int(n_out) - S) // (S // 4) + 1 if n_out >= S else 0
+    return _ft8.mode_plan(_MODE, nk, S, max_out, cfg)
 
 
 def tones(bits):

@@ -1,5 +1,5 @@
-"""FT8 skimmer: Costas sync and soft bits on a fine raster of the band (kernels ``ft8.hip``, host half
-``api_ft8.hip``).  8-FSK at 6.25 baud, tones 6.25 Hz apart, 79 symbols of which 21 are three Costas arrays.  A channelizer
+"""FT8 skimmer: Costas sync and soft bits on a fine raster of the band (kernels ``ft.hip``, host half
+``api_ft.hip``).  8-FSK at 6.25 baud, tones 6.25 Hz apart, 79 symbols of which 21 are three Costas arrays.  A channelizer
 with M / D = 4 delivers rows at ``S`` samples per symbol; inside every row ``NSUB = S / 2`` decoders run on the device, one
 every 3.125 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The device finds every
 frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` the device also runs
@@ -39,11 +39,11 @@ LLR_MAX = 4096
 UNPACK = _msg.unpack77                           # the 77 decoded bits -> text (``ft4.py``: None, its scrambler is not here)
 
 
-def shape(fs):
-    """-> (S, D, M): S = 64 row samples per symbol if fs / (64 baud) is an integer D and the channelizer accepts M = 4 D,
-    otherwise S = 96 likewise, otherwise ValueError."""
-    for S in SHAPES:
-        d = float(fs) / (S * BAUD)
+# ---- written once for both modes: ``mode`` is this module or ``ft4.py``, read for NAME, BAUD, SHAPES and PLAN_CALL ----------
+def mode_shape(mode, fs):
+    """``shape`` for ``mode``"""
+    for S in mode.SHAPES:
+        d = float(fs) / (S * mode.BAUD)
         D = int(round(d))
         if D < 1 or abs(d - D) > 1e-9 * max(d, 1.0):
             continue
@@ -52,7 +52,56 @@ def shape(fs):
         except _lib.PysdrError:
             continue
         return S, D, 4 * D
-    raise ValueError(f"no FT8 raster for fs = {fs}: fs / 400 or fs / 600 must be an integer D with M = 4 D a channelizer size")
+    r0, r1 = (f"{S * mode.BAUD:g}" for S in mode.SHAPES)
+    raise ValueError(f"no {mode.NAME} raster for fs = {fs}: fs / {r0} or fs / {r1} must be an integer D with M = 4 D a channelizer size")
+
+
+def mode_fine_channelizer(mode, fs, band, device=0, max_in=1 << 22):
+    """``fine_channelizer`` for ``mode``"""
+    from . import fine
+    err = None
+    for S in mode.SHAPES:
+        try:
+            M1, D1, M2, D2 = fine.shape(fs, S * mode.BAUD, 4)
+        except ValueError as e:
+            err = e
+            continue
+        h2 = mode.prototype(float(fs) / D1, M2, S)
+        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
+                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
+    raise ValueError(f"no {mode.NAME} raster in two stages for fs = {fs}: {err}")
+
+
+def mode_plan(mode, nk, S, max_out, cfg):
+    """``plan`` for ``mode``"""
+    v = _lib.plan_call(mode.PLAN_CALL, 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
+    return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6], "tr": v[7]}
+
+
+def tables(S):
+    """-> tw float32 [4 S][2] = (cos, -sin)(2 pi i / NT): derived in float64, rounded once"""
+    t = 2 * np.pi * np.arange(4 * S) / (4 * S)
+    return np.ascontiguousarray(np.stack((np.cos(t), -np.sin(t)), axis=1), np.float32)
+
+
+def cfg_dict(cfg):
+    return {k: getattr(cfg, k) for k, _ in type(cfg)._fields_}
+
+
+def steps_done(n_out, S):
+    """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1"""
+    return (int(n_out) - S) // (S // 4) + 1 if n_out >= S else 0
+
+
+# ---- this mode ------------------------------------------------------------------------------------------------------------
+NAME, PLAN_CALL = "FT8", "pysdr_ft8_plan"
+_MODE = sys.modules[__name__]
+
+
+def shape(fs):
+    """-> (S, D, M): S = 64 row samples per symbol if fs / (64 baud) is an integer D and the channelizer accepts M = 4 D,
+    otherwise S = 96 likewise, otherwise ValueError."""
+    return mode_shape(_MODE, fs)
 
 
 def prototype(fs, M, S):
@@ -67,24 +116,7 @@ def fine_channelizer(fs, band, device=0, max_in=1 << 22):
     """A ``fine.FineChannelizer`` for ``FT8_Skimmer(fs, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4 apart whose
     centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 64 where ``fine.shape`` finds a shape, else 96; M2 / D2 =
     4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
-    from . import fine
-    err = None
-    for S in SHAPES:
-        try:
-            M1, D1, M2, D2 = fine.shape(fs, S * BAUD, 4)
-        except ValueError as e:
-            err = e
-            continue
-        h2 = prototype(float(fs) / D1, M2, S)
-        return fine.FineChannelizer(fs, M1, M2, D1, D2, fine.prototype1(fs, M1, D1, M2), h2,
-                                    fine.channels_for(band, fs, M1, D1, M2), device, max_in)
-    raise ValueError(f"no FT8 raster in two stages for fs = {fs}: {err}")
-
-
-def tables(S):
-    """-> tw float32 [4 S][2] = (cos, -sin)(2 pi i / NT): derived in float64, rounded once"""
-    t = 2 * np.pi * np.arange(4 * S) / (4 * S)
-    return np.ascontiguousarray(np.stack((np.cos(t), -np.sin(t)), axis=1), np.float32)
+    return mode_fine_channelizer(_MODE, fs, band, device, max_in)
 
 
 def params(smin=3.0, hmin=13, pmax=1e18):
@@ -92,21 +124,11 @@ def params(smin=3.0, hmin=13, pmax=1e18):
     return Ft8Cfg(smin=float(np.float32(smin)), hmin=int(hmin), pmax=float(np.float32(pmax)))
 
 
-def cfg_dict(cfg):
-    return {k: getattr(cfg, k) for k, _ in Ft8Cfg._fields_}
-
-
 def plan(nk, S, max_out, cfg):
     """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
     samples, event cap per decoder and call, workgroups, decoders per row, ring depth in steps.  Raises PysdrError
     outside the rules."""
-    v = _lib.plan_call("pysdr_ft8_plan", 8, int(nk), int(S), int(max_out), C.byref(cfg) if cfg is not None else None)
-    return {"rows": v[0], "threads": v[1], "lds_bytes": v[2], "tile": v[3], "cap": v[4], "groups": v[5], "nsub": v[6], "tr": v[7]}
-
-
-def steps_done(n_out, S):
-    """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1"""
-    return (int(n_out) - S) // (S // 4) + 1 if n_out >= S else 0
+    return mode_plan(_MODE, nk, S, max_out, cfg)
 
 
 def unpack(words):

@@ -13,8 +13,9 @@ INCLUDES = ("tests/host_san/fake_hip", "pysdr_amd/csrc")
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
-def run(source, ok_marker, tmp_path, extra_flags=(), includes=INCLUDES):
-    """``source`` and ``includes`` are paths from the repository root.  -> the program's stdout, which holds ``ok_marker``"""
+def run(source, ok_marker, tmp_path, extra_flags=(), includes=INCLUDES, args=()):
+    """``source`` and ``includes`` are paths from the repository root, ``args`` the program's arguments.  -> the program's
+    stdout, which holds ``ok_marker``"""
     if shutil.which("g++") is None:
         pytest.skip("no g++")
     base = (["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas"]
@@ -28,7 +29,7 @@ def run(source, ok_marker, tmp_path, extra_flags=(), includes=INCLUDES):
             print("sanitizer runtime not linkable here, running the plain build:", p.stderr[-200:])
             continue
         assert p.returncode == 0, p.stderr[-3000:]
-        p = subprocess.run([exe], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+        p = subprocess.run([exe, *args], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
         if p.returncode != 0 and flags and "unexpected memory mapping" in p.stderr:
             print("sanitizer runtime not usable here, running the plain build:", p.stderr[-200:])
             continue

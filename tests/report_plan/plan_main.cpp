@@ -2,7 +2,7 @@
 // AddressSanitizer + UBSan.
 //   * the plan of both modes and its refusals; the LDS budget against the arrays the kernel declares.
 //   * the message words, the parity bits against the encoder, the tones against the skimmers' own tables: the Costas
-//     symbols in their places, ft8_data_sym / ft4_data_sym in the other direction, the Gray maps.
+//     symbols in their places, the modes' data_sym in the other direction, the Gray maps.
 //   * the mask of places: every combination of a first, a last and an inner fine row, circular or not, with a frame at
 //     the ring's oldest step, its newest, at step 0 and in between; the wrap of a fine row.
 //   * the row floor's rule: nsym, a span before step 0, one not complete, one that has left the ring.
@@ -40,26 +40,26 @@ static void check_tones() {
       ndata += sync ? 0 : 1;
     }
     if (MODE == kReportFt8) {
-      REQUIRE(nsync == 21 && ndata == kFt8Data, "%d sync, %d data", nsync, ndata);
+      REQUIRE(nsync == 21 && ndata == Ft8Mode::kData, "%d sync, %d data", nsync, ndata);
       for (int n = 0; n < 21; ++n) {
         bool sync = false;
-        REQUIRE(report_tone<MODE>(cw, ft8_costas_sym(n), &sync) == ft8_costas(n % 7) && sync, "Costas symbol %d", n);
+        REQUIRE(report_tone<MODE>(cw, Ft8Mode::costas_sym(n), &sync) == Ft8Mode::costas(n % 7) && sync, "Costas symbol %d", n);
       }
-      for (int d = 0; d < kFt8Data; ++d) {
+      for (int d = 0; d < Ft8Mode::kData; ++d) {
         bool sync = true;
         const int v = 4 * cw[3 * d] + 2 * cw[3 * d + 1] + cw[3 * d + 2];
-        REQUIRE(report_tone<MODE>(cw, ft8_data_sym(d), &sync) == ft8_gray(v) && !sync, "data symbol %d", d);
+        REQUIRE(report_tone<MODE>(cw, Ft8Mode::data_sym(d), &sync) == Ft8Mode::gray(v) && !sync, "data symbol %d", d);
       }
     } else {
-      REQUIRE(nsync == kFt4Sync && ndata == kFt4Data, "%d sync, %d data", nsync, ndata);
-      for (int n = 0; n < kFt4Sync; ++n) {
+      REQUIRE(nsync == Ft4Mode::kSync && ndata == Ft4Mode::kData, "%d sync, %d data", nsync, ndata);
+      for (int n = 0; n < Ft4Mode::kSync; ++n) {
         bool sync = false;
-        REQUIRE(report_tone<MODE>(cw, ft4_costas_sym(n), &sync) == ft4_costas(n) && sync, "Costas symbol %d", n);
+        REQUIRE(report_tone<MODE>(cw, Ft4Mode::costas_sym(n), &sync) == Ft4Mode::costas(n) && sync, "Costas symbol %d", n);
       }
-      for (int d = 0; d < kFt4Data; ++d) {
+      for (int d = 0; d < Ft4Mode::kData; ++d) {
         bool sync = true;
         const int v = 2 * cw[2 * d] + cw[2 * d + 1];
-        REQUIRE(report_tone<MODE>(cw, ft4_data_sym(d), &sync) == ft4_gray(v) && !sync, "data symbol %d", d);
+        REQUIRE(report_tone<MODE>(cw, Ft4Mode::data_sym(d), &sync) == Ft4Mode::gray(v) && !sync, "data symbol %d", d);
       }
     }
   }
@@ -71,7 +71,7 @@ static void run_case(int ci, const int32_t* hd, const std::vector<float>& ring, 
   const int tr = hd[2], nb = hd[3], nsub = hd[4], nfine = hd[1] * hd[4], n = hd[7];
   const long long t_done = hd[5];
   for (int i = 0; i < n; ++i) {
-    const bool ok = MODE == kReportFt8 ? ft8_llr_ok(Fs[i], t0s[i], t_done, nfine, tr) : ft4_llr_ok(Fs[i], t0s[i], t_done, nfine, tr);
+    const bool ok = ft_llr_ok<FtReportMode<MODE>>(Fs[i], t0s[i], t_done, nfine, tr);
     REQUIRE(ok, "case %d candidate %d (F %d, t0 %lld) is one the call refuses", ci, i, Fs[i], t0s[i]);
     const int mask = report_mask(Fs[i], t0s[i], t_done, nfine, tr, ReportGeom<MODE>::kLag, hd[6] != 0);
     REQUIRE((mask >> 4) & 1, "the candidate's own place");
@@ -120,10 +120,10 @@ int main() {
   }
   // ---- the mask of places
   {
-    const int nfine = 96, tr = 340, lag = kFt8Lag;
+    const int nfine = 96, tr = 340, lag = kFtLag<Ft8Mode>;
     const long long done = 400;                                       // frames may begin at 60 .. 87
-    REQUIRE(ft8_llr_ok(5, 60, done, nfine, tr) && !ft8_llr_ok(5, 59, done, nfine, tr) && ft8_llr_ok(5, 87, done, nfine, tr) &&
-            !ft8_llr_ok(5, 88, done, nfine, tr), "the window");
+    REQUIRE(ft_llr_ok<Ft8Mode>(5, 60, done, nfine, tr) && !ft_llr_ok<Ft8Mode>(5, 59, done, nfine, tr) && ft_llr_ok<Ft8Mode>(5, 87, done, nfine, tr) &&
+            !ft_llr_ok<Ft8Mode>(5, 88, done, nfine, tr), "the window");
     REQUIRE(report_mask(5, 70, done, nfine, tr, lag, false) == 0x1ff && report_mask(5, 70, done, nfine, tr, lag, true) == 0x1ff, "inner");
     REQUIRE(report_mask(5, 60, done, nfine, tr, lag, false) == 0x1f8 && report_mask(5, 87, done, nfine, tr, lag, false) == 0x03f, "time's ends");
     REQUIRE(report_mask(0, 70, done, nfine, tr, lag, false) == 0x1b6 && report_mask(95, 70, done, nfine, tr, lag, false) == 0x0db, "raster's ends");
@@ -131,7 +131,7 @@ int main() {
     REQUIRE(report_mask(0, 60, done, nfine, tr, lag, false) == 0x1b0 && report_mask(95, 87, done, nfine, tr, lag, false) == 0x01b, "corners");
     REQUIRE(report_mask(3, 0, 313, nfine, tr, lag, false) == 0x038 && report_mask(3, 0, 314, nfine, tr, lag, false) == 0x1f8 &&
             report_mask(3, 1, 314, nfine, tr, lag, false) == 0x03f, "a young stream");
-    REQUIRE(report_mask(3, 70, done, nfine, tr, kFt4Lag, false) == 0 , "an FT4 frame does not fit 340 steps");
+    REQUIRE(report_mask(3, 70, done, nfine, tr, kFtLag<Ft4Mode>, false) == 0 , "an FT4 frame does not fit 340 steps");
     REQUIRE(report_wrap(-1, nfine) == 95 && report_wrap(96, nfine) == 0 && report_wrap(40, nfine) == 40, "wrap");
   }
   // ---- the row floor's rule

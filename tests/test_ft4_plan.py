@@ -1,9 +1,9 @@
-"""The FT4 skimmer's plan (pysdr_ft4_plan, include/pysdr_hip.h; pysdr_amd/csrc/ft4_plan.h): what it refuses, the event cap
+"""The FT4 skimmer's plan (pysdr_ft4_plan, include/pysdr_hip.h; pysdr_amd/csrc/ft_plan.h): what it refuses, the event cap
 and the ring depth -- through the library, which needs no device for this -- the shapes of the raster at one stage and
 at two (8 MS/s, 512 kS/s), and the tile walk, the spectrum, the sync score with its symbol and tone tables, the soft
 bits, the cap proof, the ring-depth rule and pysdr_ft4_llr's validity window in a stand-alone C++ program
-(tests/ft4_plan/plan_main.cpp) built and run by tests/plan_program.py, under AddressSanitizer + UBSan where they are
-usable.  CPU only; nothing that is loaded into Python runs under a sanitizer."""
+(tests/ft_plan/plan_main.cpp, run for this mode) built and run by tests/plan_program.py, under AddressSanitizer + UBSan
+where they are usable.  CPU only; nothing that is loaded into Python runs under a sanitizer."""
 import ctypes as C
 
 import pytest
@@ -57,6 +57,11 @@ def test_plan_refuses_bad_shapes_and_settings(hiplib):
         rc, v = call(hiplib, nk, S, mo, cfg)
         assert rc == -1 and v == [-7] * 8, (nk, S, mo)
         assert b"pysdr_ft4_plan" in hiplib.pysdr_last_error()
+    # the whole text of one refusal: the mode's numbers in it come from the traits of ft_plan.h
+    assert call(hiplib, 10923, 48, 16, cfg)[0] == -1
+    assert hiplib.pysdr_last_error() == (
+        b"pysdr_ft4_plan: S 48 is neither 48 nor 72, nk 10923 < 1 or nk S / 2 > 262144, max_out 16 outside [1, 1048576], a spectrum ring "
+        b"above 1073741824 bytes, or a cfg outside the rules (NULL; smin >= 0, 0 <= hmin <= 16, 0 < pmax <= 1e18, all finite)")
     assert call(hiplib, 10922, 48, 256, cfg)[0] == 0 and call(hiplib, 7281, 72, 16, cfg)[0] == 0 and call(hiplib, 512, 48, 4096, cfg)[0] == 0
     assert call(hiplib, 4, 48, 16, None)[0] == -1
     bad = [("smin", -0.5), ("smin", float("nan")), ("smin", float("inf")), ("smin", float("-inf")), ("hmin", -1), ("hmin", 17)]
@@ -105,4 +110,4 @@ def test_the_shapes_of_one_stage_and_of_two(hiplib):
 def test_tiles_cover_every_sample_once_the_steps_equal_the_transcription_and_the_proofs_hold(tmp_path):
     """the tile walk over cut streams, spectrum, sync, peak and soft bits against plain transcriptions, the symbol and tone
     tables against the lists written out, the cap proof, the ring-depth rule and the validity window of the soft bits"""
-    plan_program.run("tests/ft4_plan/plan_main.cpp", "FT4_PLAN_OK", tmp_path, extra_flags=("-ffp-contract=off",))
+    plan_program.run("tests/ft_plan/plan_main.cpp", "FT4_PLAN_OK", tmp_path, extra_flags=("-ffp-contract=off",), args=("ft4",))

@@ -1,8 +1,8 @@
-"""The FT8 skimmer's plan (pysdr_ft8_plan, include/pysdr_hip.h; pysdr_amd/csrc/ft8_plan.h): what it refuses, the event cap
+"""The FT8 skimmer's plan (pysdr_ft8_plan, include/pysdr_hip.h; pysdr_amd/csrc/ft_plan.h): what it refuses, the event cap
 and the ring depth -- through the library, which needs no device for this -- the shape a fine channelizer takes at
 8 MS/s, and the tile walk, the spectrum, the sync score, the peak rule, the soft bits, the cap proof, the ring-depth rule
-and pysdr_ft8_llr's validity window in a stand-alone C++ program (tests/ft8_plan/plan_main.cpp) built and run by
-tests/plan_program.py, under AddressSanitizer + UBSan where they are usable.  CPU only; nothing that is loaded into
+and pysdr_ft8_llr's validity window in a stand-alone C++ program (tests/ft_plan/plan_main.cpp, run for this mode) built and
+run by tests/plan_program.py, under AddressSanitizer + UBSan where they are usable.  CPU only; nothing that is loaded into
 Python runs under a sanitizer."""
 import ctypes as C
 
@@ -55,6 +55,11 @@ def test_plan_refuses_bad_shapes_and_settings(hiplib):
         rc, v = call(hiplib, nk, S, mo, cfg)
         assert rc == -1 and v == [-7] * 8, (nk, S, mo)
         assert b"pysdr_ft8_plan" in hiplib.pysdr_last_error()
+    # the whole text of one refusal: the mode's numbers in it come from the traits of ft_plan.h
+    assert call(hiplib, 8193, 64, 16, cfg)[0] == -1
+    assert hiplib.pysdr_last_error() == (
+        b"pysdr_ft8_plan: S 64 is neither 64 nor 96, nk 8193 < 1 or nk S / 2 > 262144, max_out 16 outside [1, 1048576], a spectrum ring "
+        b"above 1073741824 bytes, or a cfg outside the rules (NULL; smin >= 0, 0 <= hmin <= 21, 0 < pmax <= 1e18, all finite)")
     assert call(hiplib, 8192, 64, 256, cfg)[0] == 0 and call(hiplib, 512, 64, 4096, cfg)[0] == 0
     assert call(hiplib, 4, 64, 16, None)[0] == -1
     bad = [("smin", -0.5), ("smin", float("nan")), ("smin", float("inf")), ("smin", float("-inf")), ("hmin", -1), ("hmin", 22)]
@@ -102,4 +107,4 @@ def test_a_fine_channelizer_for_8_ms_per_second_is_valid_and_gives_rows_100_hz_a
 def test_tiles_cover_every_sample_once_the_steps_equal_the_transcription_and_the_proofs_hold(tmp_path):
     """the tile walk over cut streams, spectrum, sync, peak and soft bits against plain transcriptions, the cap proof, the
     ring-depth rule and the validity window of the soft bits"""
-    plan_program.run("tests/ft8_plan/plan_main.cpp", "FT8_PLAN_OK", tmp_path, extra_flags=("-ffp-contract=off",))
+    plan_program.run("tests/ft_plan/plan_main.cpp", "FT8_PLAN_OK", tmp_path, extra_flags=("-ffp-contract=off",), args=("ft8",))

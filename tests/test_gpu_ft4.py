@@ -1,4 +1,4 @@
-"""The FT4 skimmer on the GPU (pysdr_amd/csrc/ft4.hip, api_ft4.hip) against the float32 oracle of the
+"""The FT4 skimmer on the GPU (pysdr_amd/csrc/ft.hip, api_ft.hip) against the float32 oracle of the
 definition (tests/ft4_oracle.py): counts, event words, scores, hit counts, the spectrum ring and the soft bits are EQUAL
 after every call, floats by their bits.  The oracle side is fed the rows of an independent Channelizer of the same shape
 and prototype on the same input, so only the skimmer's own arithmetic is judged.  Streams are 7 s: a frame with its ramps
