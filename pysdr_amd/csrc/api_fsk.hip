@@ -1,15 +1,15 @@
 // C ABI of the RTTY raster skimmer (include/pysdr_hip.h).  Host-side only, like api_psk.hip: the
 // kernel and its launch function live in fsk.hip, what both sides share in fsk_plan.h.  The skimmer borrows a channelizer
 // as the CW and PSK31 skimmers do (chan_client.h: what the channelizer's clients share) and queues its decoders behind
-// the channelizer's launch on the channelizer's stream.  Every device resource is an owner (host_res.h): deleting the
-// object frees it.
-#include "chan_client.h"
+// the channelizer's launch on the channelizer's stream.  The call list is skimmer_host.h's, the skimmers' shared core;
+// here is what only this kind has: its struct, buffers, tables, first state, plan, launch arguments, the two further
+// outputs of a call and the state call.  Every device resource is an owner (host_res.h): deleting the object frees it.
 #include "fsk_plan.h"
+#include "skimmer_host.h"
 
 using namespace pysdr;
 
-struct pysdr_fsk : ChanClient {
-  int max_out = 0;
+struct pysdr_fsk : SkimmerBase {    // rows = nfine, words = cap
   pysdr_fsk_cfg cfg{};
   FskPlan plan;
   DevBuf<FskC> d_y;                 // [nk][ypitch]: kFskHpad of history room, then the call's outputs
@@ -17,10 +17,9 @@ struct pysdr_fsk : ChanClient {
   DevBuf<float> d_g;                // [S]
   DevBuf<float> d_sf;               // [4][nfine]
   DevBuf<int32_t> d_si;             // [8][nfine]
-  DevBuf<int32_t> d_events;         // [nfine][cap]
-  DevBuf<int32_t> d_counts;         // [nfine]
   std::vector<float> h_tw, h_g;
   std::vector<int32_t> h_si;        // the state after create / reset
+  FskC* feed_rows() { return d_y.get() + kFskHpad; }
 };
 
 namespace {
@@ -32,9 +31,7 @@ int fsk_alloc(pysdr_fsk* w) {
   PYSDR_HIP_CHECK(w->d_g.alloc(S));
   PYSDR_HIP_CHECK(w->d_sf.alloc((size_t)kFskStateFloats * nf));
   PYSDR_HIP_CHECK(w->d_si.alloc((size_t)kFskStateInts * nf));
-  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap));
-  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
-  return PYSDR_OK;
+  return skimmer_alloc(w);
 }
 
 int fsk_reset_locked(pysdr_fsk* w) {
@@ -49,8 +46,7 @@ int fsk_reset_locked(pysdr_fsk* w) {
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_si.get(), w->h_si.data(), w->h_si.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_y.get(), 0, nk * (size_t)w->plan.ypitch * sizeof(FskC), st));   // y[k] = 0 for k < 0
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sf.get(), 0, (size_t)kFskStateFloats * nf * sizeof(float), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * sizeof(int32_t), st));
+  if (const int rc2 = skimmer_clear(w, st)) return rc2;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   w->last_n_out = 0;
   return PYSDR_OK;
@@ -75,88 +71,50 @@ int pysdr_fsk_plan(int nk, int S, int max_out, const pysdr_fsk_cfg* cfg, int32_t
 }
 
 int pysdr_fsk_create(pysdr_chan* ch, int S, const pysdr_fsk_cfg* cfg, const float* tw, const float* g, int max_out, pysdr_fsk** out) {
-  if (!out) { set_last_error("pysdr_fsk_create: out is NULL"); return PYSDR_ERR_ARG; }
-  *out = nullptr;
-  if (!ch || !cfg || !tw || !g) { set_last_error("pysdr_fsk_create: NULL channelizer, cfg, tw or g"); return PYSDR_ERR_ARG; }
-  pysdr_fsk* w = new pysdr_fsk();
-  int32_t pl[8];
-  int rc = client_bind(w, ch);
-  if (rc == PYSDR_OK) rc = pysdr_fsk_plan(w->nk, S, max_out, cfg, pl);
-  if (rc != PYSDR_OK) { delete w; return rc; }
-  w->max_out = max_out; w->cfg = *cfg;
-  fsk_plan(w->nk, S, max_out, cfg, &w->plan);
-  w->h_tw.assign(tw, tw + 2 * 8 * (size_t)S);
-  w->h_g.assign(g, g + (size_t)S);
-  const size_t nf = (size_t)w->plan.nfine;
-  w->h_si.assign((size_t)kFskStateInts * nf, 0);
-  for (size_t i = 0; i < nf; ++i) { w->h_si[nf + i] = S; w->h_si[4 * nf + i] = 1; }   // cnt = S, prev = 1
-  return client_create(w, "pysdr_fsk_create", fsk_alloc, fsk_reset_locked, out);
+  return skimmer_create("pysdr_fsk_create", ch && cfg && tw && g, "NULL channelizer, cfg, tw or g", ch, max_out, out, fsk_alloc, fsk_reset_locked,
+                        [&](pysdr_fsk* w) -> int {
+    int32_t pl[8];
+    if (!fsk_plan(w->nk, S, max_out, cfg, &w->plan)) return pysdr_fsk_plan(w->nk, S, max_out, cfg, pl);
+    w->cfg = *cfg;
+    w->rows = w->plan.nfine; w->words = w->plan.cap;
+    w->h_tw.assign(tw, tw + 2 * 8 * (size_t)S);
+    w->h_g.assign(g, g + (size_t)S);
+    const size_t nf = (size_t)w->plan.nfine;
+    w->h_si.assign((size_t)kFskStateInts * nf, 0);
+    for (size_t i = 0; i < nf; ++i) { w->h_si[nf + i] = S; w->h_si[4 * nf + i] = 1; }   // cnt = S, prev = 1
+    return PYSDR_OK;
+  });
 }
 
 void pysdr_fsk_destroy(pysdr_fsk* w) { client_destroy(w); }
-
-int pysdr_fsk_reset(pysdr_fsk* w) {
-  if (!w) { set_last_error("pysdr_fsk_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  return fsk_reset_locked(w);
-}
-
-int pysdr_fsk_sync(pysdr_fsk* w) {
-  if (!w) { set_last_error("pysdr_fsk_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
-  return client_sync(w);
-}
+int pysdr_fsk_reset(pysdr_fsk* w) { return skimmer_reset(w, "pysdr_fsk_reset", fsk_reset_locked); }
+int pysdr_fsk_sync(pysdr_fsk* w) { return skimmer_sync(w, "pysdr_fsk_sync"); }
 
 int pysdr_fsk_process(pysdr_fsk* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
                       long long ev_pitch, float* qn, int32_t* open) {
-  if (!w || !n_out) { set_last_error("pysdr_fsk_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
-  *n_out = 0;
-  std::lock_guard<std::mutex> lk(w->mu);
-  ClientStep step;
-  int rc = client_begin(w, "pysdr_fsk_process", iq, n, &step);
-  if (rc != PYSDR_OK) return rc;
-  if (events && ev_pitch < w->plan.cap) {
-    set_last_error("pysdr_fsk_process: ev_pitch %lld < the event cap %d", ev_pitch, w->plan.cap);
-    return PYSDR_ERR_STATE;
-  }
-  if (step.nf_want > (unsigned long long)w->max_out) {
-    set_last_error("pysdr_fsk_process: the call would complete %llu outputs, max_out is %d", step.nf_want, w->max_out);
-    return PYSDR_ERR_STATE;
-  }
-  int nf = 0;
-  rc = client_feed(w, "pysdr_fsk_process", "skimmer", iq, n, on_device, w->d_y.get() + kFskHpad, w->plan.ypitch, step, &nf);
-  if (rc != PYSDR_OK) return rc;
-  const size_t nfine = (size_t)w->plan.nfine;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  hipStream_t st = w->stream;
-  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
-    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
-  } else {
+  return skimmer_process(w, "pysdr_fsk_process", iq, n, on_device, n_out, counts, events, ev_pitch,
+                         [&](const ClientStep& step, int nf, hipStream_t st) -> int {
+    if (nf == 0) return PYSDR_OK;
     FskArgs a{};
-    a.y = w->d_y.get() + kFskHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.y = w->feed_rows(); a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
     a.m0_mod = (int)(step.m0 % (unsigned long long)(8 * w->plan.S));
     a.cfg = w->cfg; a.tw = w->d_tw.get(); a.g = w->d_g.get();
     a.sf = w->d_sf.get(); a.si = w->d_si.get(); a.events = w->d_events.get(); a.counts = w->d_counts.get();
-    rc = launch_fsk_decode(w->plan.S, a, st);
-    if (rc) return rc;
-    *n_out = nf;
-    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (events)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)a.cap * sizeof(int32_t),
-                                       (size_t)a.cap * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
-  }
-  if (qn) PYSDR_HIP_CHECK(hipMemcpyAsync(qn, w->d_sf.get(), nfine * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (open) PYSDR_HIP_CHECK(hipMemcpyAsync(open, w->d_si.get() + kFskOpenAt * nfine, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (counts || events || qn || open || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
-  return PYSDR_OK;
+    return launch_fsk_decode(w->plan.S, a, st);
+  }, qn || open, [&](hipStream_t st) -> int {                          // the state as it stands, on an empty call too
+    const size_t nfine = (size_t)w->plan.nfine;
+    if (qn) PYSDR_HIP_CHECK(hipMemcpyAsync(qn, w->d_sf.get(), nfine * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (open) PYSDR_HIP_CHECK(hipMemcpyAsync(open, w->d_si.get() + kFskOpenAt * nfine, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return PYSDR_OK;
+  });
 }
 
 int pysdr_fsk_fetch(pysdr_fsk* w, const int* rows, int nrows, int32_t* events, long long pitch) {
-  if (!w) { set_last_error("pysdr_fsk_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
-  return client_fetch_events(w, "pysdr_fsk_fetch", "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap, rows, nrows, events, pitch);
+  return skimmer_fetch(w, "pysdr_fsk_fetch", "fine row", rows, nrows, events, pitch);
 }
 
 int pysdr_fsk_state(pysdr_fsk* w, float* f, int32_t* ints) {
-  if (!w) { set_last_error("pysdr_fsk_state: NULL skimmer"); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer("pysdr_fsk_state");
   std::lock_guard<std::mutex> lk(w->mu);
   PYSDR_HIP_CHECK(hipSetDevice(w->device));
   hipStream_t st = w->stream;

@@ -2,10 +2,11 @@
 // the kernels and their launch functions live in ft.hip, what both sides share in ft_plan.h.  One skimmer, templated on
 // the mode; every call is written once, and the extern "C" functions at the end forward to it under their own names.  A
 // skimmer borrows a channelizer as the other skimmers do (chan_client.h: what the channelizer's clients share) and queues
-// its kernels behind the channelizer's launch on the channelizer's stream.  Every device resource is an owner
-// (host_res.h): deleting the object frees it.  The decoder's calls are ldpc_host.h's, the frame report's and the row
-// floor's report_host.h's; both read the mode from the skimmer.
-#include "chan_client.h"
+// its kernels behind the channelizer's launch on the channelizer's stream.  The call list is skimmer_host.h's, the
+// skimmers' shared core, which reset, sync and fetch forward to directly; here is what only this kind has: its struct,
+// buffers, plan, the step count that a process call keeps, the soft bits and the state call.  Every device resource is
+// an owner (host_res.h): deleting the object frees it.  The decoder's calls are ldpc_host.h's, the frame report's and
+// the row floor's report_host.h's; both read the mode from the skimmer.
 #include "ft_plan.h"
 #include "ldpc_host.h"
 #include "report_host.h"
@@ -13,9 +14,8 @@
 using namespace pysdr;
 
 template <class M>
-struct FtSkimmer : ChanClient {
+struct FtSkimmer : SkimmerBase {    // rows = nfine, words = cap * kFtEventWords
   using Mode = M;
-  int max_out = 0;
   FtCfg cfg{};
   FtPlan plan;
   unsigned long long t_done = 0;    // steps complete since create / reset
@@ -24,14 +24,13 @@ struct FtSkimmer : ChanClient {
   DevBuf<float> d_ring;             // [nk][tr][NB]
   DevBuf<float> d_sc;               // [9][nfine]
   DevBuf<int32_t> d_hi;             // [9][nfine]
-  DevBuf<int32_t> d_events;         // [nfine][cap][2]
-  DevBuf<int32_t> d_counts;         // [nfine]
   DevBuf<int32_t> d_cand;           // [kFtLlrMax][2]
   DevBuf<float> d_llr;              // [kFtLlrMax][174]
   std::vector<float> h_tw;
   std::vector<int32_t> h_cand;
   LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
   ReportBufs report;                // the frame report's and the row floor's (report_host.h)
+  FtC* feed_rows() { return d_y.get() + Mode::kHpad; }
 };
 
 struct pysdr_ft8 : FtSkimmer<Ft8Mode> {};
@@ -51,11 +50,9 @@ int ft_alloc(W* w) {
   PYSDR_HIP_CHECK(w->d_ring.alloc(nk * (size_t)w->plan.tr * (size_t)w->plan.nb));
   PYSDR_HIP_CHECK(w->d_sc.alloc((size_t)kFtKeep * nf));
   PYSDR_HIP_CHECK(w->d_hi.alloc((size_t)kFtKeep * nf));
-  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap * kFtEventWords));
-  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
   PYSDR_HIP_CHECK(w->d_cand.alloc((size_t)kFtLlrMax * 2));
   PYSDR_HIP_CHECK(w->d_llr.alloc((size_t)kFtLlrMax * kFtBits));
-  return PYSDR_OK;
+  return skimmer_alloc(w);
 }
 
 template <class W>
@@ -71,8 +68,7 @@ int ft_reset_locked(W* w) {
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_ring.get(), 0, nk * (size_t)w->plan.tr * (size_t)w->plan.nb * sizeof(float), st));
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sc.get(), 0, (size_t)kFtKeep * nf * sizeof(float), st));
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_hi.get(), 0, (size_t)kFtKeep * nf * sizeof(int32_t), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * kFtEventWords * sizeof(int32_t), st));
+  if (const int rc2 = skimmer_clear(w, st)) return rc2;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   w->last_n_out = 0;
   w->t_done = 0;
@@ -100,67 +96,28 @@ int ft_plan_call(const char* who, int nk, int S, int max_out, const FtCfg* cfg, 
 template <class W>
 int ft_create(const char* who, const char* who_plan, pysdr_chan* ch, int S, const FtCfg* cfg, const float* tw, int max_out, W** out) {
   using Mode = typename W::Mode;
-  if (!out) { set_last_error("%s: out is NULL", who); return PYSDR_ERR_ARG; }
-  *out = nullptr;
-  if (!ch || !cfg || !tw) { set_last_error("%s: NULL channelizer, cfg or tw", who); return PYSDR_ERR_ARG; }
-  W* w = new W();
-  int32_t pl[8];
-  int rc = client_bind(w, ch);
-  if (rc == PYSDR_OK) rc = ft_plan_call<Mode>(who_plan, w->nk, S, max_out, cfg, pl);
-  if (rc != PYSDR_OK) { delete w; return rc; }
-  w->max_out = max_out; w->cfg = *cfg;
-  ft_plan<Mode>(w->nk, S, max_out, cfg, &w->plan);
-  w->h_tw.assign(tw, tw + 2 * 4 * (size_t)S);
-  w->h_cand.reserve((size_t)kFtLlrMax * 2);
-  return client_create(w, who, ft_alloc<W>, ft_reset_locked<W>, out);
-}
-
-template <class W>
-int ft_reset(W* w, const char* who) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  return ft_reset_locked(w);
-}
-
-template <class W>
-int ft_sync_call(W* w, const char* who) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
-  return client_sync(w);
+  return skimmer_create(who, ch && cfg && tw, "NULL channelizer, cfg or tw", ch, max_out, out, ft_alloc<W>, ft_reset_locked<W>, [&](W* w) -> int {
+    int32_t pl[8];
+    if (!ft_plan<Mode>(w->nk, S, max_out, cfg, &w->plan)) return ft_plan_call<Mode>(who_plan, w->nk, S, max_out, cfg, pl);
+    w->cfg = *cfg;
+    w->rows = w->plan.nfine; w->words = w->plan.cap * kFtEventWords;
+    w->h_tw.assign(tw, tw + 2 * 4 * (size_t)S);
+    w->h_cand.reserve((size_t)kFtLlrMax * 2);
+    return PYSDR_OK;
+  });
 }
 
 template <class W>
 int ft_process(W* w, const char* who, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
                long long ev_pitch, long long* steps) {
   using Mode = typename W::Mode;
-  if (!w || !n_out) { set_last_error("%s: NULL skimmer or n_out", who); return PYSDR_ERR_ARG; }
-  *n_out = 0;
-  std::lock_guard<std::mutex> lk(w->mu);
-  ClientStep step;
-  int rc = client_begin(w, who, iq, n, &step);
-  if (rc != PYSDR_OK) return rc;
-  const int words = w->plan.cap * kFtEventWords;
-  if (events && ev_pitch < words) {
-    set_last_error("%s: ev_pitch %lld < the event cap's %d words", who, ev_pitch, words);
-    return PYSDR_ERR_STATE;
-  }
-  if (step.nf_want > (unsigned long long)w->max_out) {
-    set_last_error("%s: the call would complete %llu outputs, max_out is %d", who, step.nf_want, w->max_out);
-    return PYSDR_ERR_STATE;
-  }
-  int nf = 0;
-  rc = client_feed(w, who, "skimmer", iq, n, on_device, w->d_y.get() + Mode::kHpad, w->plan.ypitch, step, &nf);
-  if (rc != PYSDR_OK) return rc;
-  const size_t nfine = (size_t)w->plan.nfine;
-  const int S = w->plan.S;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  hipStream_t st = w->stream;
-  if (steps) { steps[0] = (long long)w->t_done; steps[1] = 0; }
-  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
-    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
-  } else {
+  return skimmer_process(w, who, iq, n, on_device, n_out, counts, events, ev_pitch, [&](const ClientStep& step, int nf, hipStream_t st) -> int {
+    const int S = w->plan.S;
+    if (steps) { steps[0] = (long long)w->t_done; steps[1] = 0; }
+    if (nf == 0) return PYSDR_OK;
     const unsigned long long t1 = ft_steps_done(step.m0 + (unsigned long long)nf, S);
     FtArgs a{};
-    a.y = w->d_y.get() + Mode::kHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.y = w->feed_rows(); a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
     a.ns = (int)(t1 - w->t_done);
     a.e_first = a.ns > 0 ? (int)((unsigned long long)(S / 4) * w->t_done + (unsigned long long)(S - 1) - step.m0) : 0;
     a.tr = w->plan.tr; a.t_first = (long long)w->t_done;
@@ -170,31 +127,19 @@ int ft_process(W* w, const char* who, const void* iq, int n, int on_device, int*
       set_last_error("%s: the step count lost its place (%d steps, first at output %d)", who, a.ns, a.e_first);
       return PYSDR_ERR_STATE;
     }
-    if (a.ns == 0) PYSDR_HIP_CHECK(hipMemsetAsync(a.counts, 0, nfine * sizeof(int32_t), st));   // outputs but no step: only the history rolls
-    rc = launch_ft_steps(Mode::kLdpcSource, S, a, st);
+    if (a.ns == 0) PYSDR_HIP_CHECK(hipMemsetAsync(a.counts, 0, (size_t)w->rows * sizeof(int32_t), st));   // outputs but no step: only the history rolls
+    const int rc = launch_ft_steps(Mode::kLdpcSource, S, a, st);
     if (rc) return rc;
     w->t_done = t1;
-    *n_out = nf;
     if (steps) steps[1] = a.ns;
-    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (events)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)words * sizeof(int32_t),
-                                       (size_t)words * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
-  }
-  if (counts || events || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
-  return PYSDR_OK;
-}
-
-template <class W>
-int ft_fetch(W* w, const char* who, const int* rows, int nrows, int32_t* events, long long pitch) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
-  return client_fetch_events(w, who, "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap * kFtEventWords, rows, nrows, events, pitch);
+    return PYSDR_OK;
+  });
 }
 
 template <class W>
 int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, float* out) {
   using Mode = typename W::Mode;
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   if (n < 0 || n > kFtLlrMax || (n > 0 && (!F || !t0 || !out))) {
     set_last_error("%s: n %d outside [0, %d] / NULL F, t0 or out", who, n, kFtLlrMax);
     return PYSDR_ERR_ARG;
@@ -226,7 +171,7 @@ int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, 
 
 template <class W>
 int ft_state(W* w, const char* who, float* sc, int32_t* hits, float* ring, long long* t_done) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   std::lock_guard<std::mutex> lk(w->mu);
   PYSDR_HIP_CHECK(hipSetDevice(w->device));
   hipStream_t st = w->stream;
@@ -253,14 +198,14 @@ int pysdr_ft8_create(pysdr_chan* ch, int S, const pysdr_ft8_cfg* cfg, const floa
   return ft_create("pysdr_ft8_create", "pysdr_ft8_plan", ch, S, ft_cfg(cfg), tw, max_out, out);
 }
 void pysdr_ft8_destroy(pysdr_ft8* w) { client_destroy(w); }
-int pysdr_ft8_reset(pysdr_ft8* w) { return ft_reset(w, "pysdr_ft8_reset"); }
-int pysdr_ft8_sync(pysdr_ft8* w) { return ft_sync_call(w, "pysdr_ft8_sync"); }
+int pysdr_ft8_reset(pysdr_ft8* w) { return skimmer_reset(w, "pysdr_ft8_reset", ft_reset_locked<pysdr_ft8>); }
+int pysdr_ft8_sync(pysdr_ft8* w) { return skimmer_sync(w, "pysdr_ft8_sync"); }
 int pysdr_ft8_process(pysdr_ft8* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
                       long long ev_pitch, long long* steps) {
   return ft_process(w, "pysdr_ft8_process", iq, n, on_device, n_out, counts, events, ev_pitch, steps);
 }
 int pysdr_ft8_fetch(pysdr_ft8* w, const int* rows, int nrows, int32_t* events, long long pitch) {
-  return ft_fetch(w, "pysdr_ft8_fetch", rows, nrows, events, pitch);
+  return skimmer_fetch(w, "pysdr_ft8_fetch", "fine row", rows, nrows, events, pitch);
 }
 int pysdr_ft8_llr(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, float* out) { return ft_llr(w, "pysdr_ft8_llr", F, t0, n, out); }
 int pysdr_ft8_state(pysdr_ft8* w, float* sc, int32_t* hits, float* ring, long long* t_done) {
@@ -294,14 +239,14 @@ int pysdr_ft4_create(pysdr_chan* ch, int S, const pysdr_ft4_cfg* cfg, const floa
   return ft_create("pysdr_ft4_create", "pysdr_ft4_plan", ch, S, ft_cfg(cfg), tw, max_out, out);
 }
 void pysdr_ft4_destroy(pysdr_ft4* w) { client_destroy(w); }
-int pysdr_ft4_reset(pysdr_ft4* w) { return ft_reset(w, "pysdr_ft4_reset"); }
-int pysdr_ft4_sync(pysdr_ft4* w) { return ft_sync_call(w, "pysdr_ft4_sync"); }
+int pysdr_ft4_reset(pysdr_ft4* w) { return skimmer_reset(w, "pysdr_ft4_reset", ft_reset_locked<pysdr_ft4>); }
+int pysdr_ft4_sync(pysdr_ft4* w) { return skimmer_sync(w, "pysdr_ft4_sync"); }
 int pysdr_ft4_process(pysdr_ft4* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
                       long long ev_pitch, long long* steps) {
   return ft_process(w, "pysdr_ft4_process", iq, n, on_device, n_out, counts, events, ev_pitch, steps);
 }
 int pysdr_ft4_fetch(pysdr_ft4* w, const int* rows, int nrows, int32_t* events, long long pitch) {
-  return ft_fetch(w, "pysdr_ft4_fetch", rows, nrows, events, pitch);
+  return skimmer_fetch(w, "pysdr_ft4_fetch", "fine row", rows, nrows, events, pitch);
 }
 int pysdr_ft4_llr(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, float* out) { return ft_llr(w, "pysdr_ft4_llr", F, t0, n, out); }
 int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long long* t_done) {

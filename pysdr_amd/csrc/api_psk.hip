@@ -1,14 +1,15 @@
 // C ABI of the PSK31 skimmer (include/pysdr_hip.h).  Host-side only, like api_cw.hip: the kernel and
 // its launch function live in psk.hip, what both sides share in psk_plan.h.  The skimmer borrows a channelizer as the CW
 // skimmer does (chan_client.h: what the channelizer's clients share) and queues its decoders behind the channelizer's
-// launch on the channelizer's stream.  Every device resource is an owner (host_res.h): deleting the object frees it.
-#include "chan_client.h"
+// launch on the channelizer's stream.  The call list is skimmer_host.h's, the skimmers' shared core; here is what only
+// this kind has: its struct, buffers, tables, first state, plan, launch arguments, the two further outputs of a call and
+// the state call.  Every device resource is an owner (host_res.h): deleting the object frees it.
 #include "psk_plan.h"
+#include "skimmer_host.h"
 
 using namespace pysdr;
 
-struct pysdr_psk : ChanClient {
-  int max_out = 0;
+struct pysdr_psk : SkimmerBase {    // rows = nfine, words = cap
   pysdr_psk_cfg cfg{};
   PskPlan plan;
   DevBuf<PskC> d_y;                 // [nk][ypitch]: kPskHpad of history room, then the call's outputs
@@ -17,10 +18,9 @@ struct pysdr_psk : ChanClient {
   DevBuf<float> d_e;                // [S][nfine]
   DevBuf<float> d_sf;               // [4][nfine]
   DevBuf<int32_t> d_si;             // [5][nfine]
-  DevBuf<int32_t> d_events;         // [nfine][cap]
-  DevBuf<int32_t> d_counts;         // [nfine]
   std::vector<float> h_tw, h_g;
   std::vector<int32_t> h_si;        // the state after create / reset
+  PskC* feed_rows() { return d_y.get() + kPskHpad; }
 };
 
 namespace {
@@ -33,9 +33,7 @@ int psk_alloc(pysdr_psk* w) {
   PYSDR_HIP_CHECK(w->d_e.alloc(S * nf));
   PYSDR_HIP_CHECK(w->d_sf.alloc((size_t)kPskStateFloats * nf));
   PYSDR_HIP_CHECK(w->d_si.alloc((size_t)kPskStateInts * nf));
-  PYSDR_HIP_CHECK(w->d_events.alloc(nf * (size_t)w->plan.cap));
-  PYSDR_HIP_CHECK(w->d_counts.alloc(nf));
-  return PYSDR_OK;
+  return skimmer_alloc(w);
 }
 
 int psk_reset_locked(pysdr_psk* w) {
@@ -51,8 +49,7 @@ int psk_reset_locked(pysdr_psk* w) {
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_y.get(), 0, nk * (size_t)w->plan.ypitch * sizeof(PskC), st));   // y[k] = 0 for k < 0
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_e.get(), 0, S * nf * sizeof(float), st));
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sf.get(), 0, (size_t)kPskStateFloats * nf * sizeof(float), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_counts.get(), 0, nf * sizeof(int32_t), st));
-  PYSDR_HIP_CHECK(hipMemsetAsync(w->d_events.get(), 0, nf * (size_t)w->plan.cap * sizeof(int32_t), st));
+  if (const int rc2 = skimmer_clear(w, st)) return rc2;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   w->last_n_out = 0;
   return PYSDR_OK;
@@ -77,88 +74,50 @@ int pysdr_psk_plan(int nk, int S, int max_out, const pysdr_psk_cfg* cfg, int32_t
 }
 
 int pysdr_psk_create(pysdr_chan* ch, int S, const pysdr_psk_cfg* cfg, const float* tw, const float* g, int max_out, pysdr_psk** out) {
-  if (!out) { set_last_error("pysdr_psk_create: out is NULL"); return PYSDR_ERR_ARG; }
-  *out = nullptr;
-  if (!ch || !cfg || !tw || !g) { set_last_error("pysdr_psk_create: NULL channelizer, cfg, tw or g"); return PYSDR_ERR_ARG; }
-  pysdr_psk* w = new pysdr_psk();
-  int32_t pl[8];
-  int rc = client_bind(w, ch);
-  if (rc == PYSDR_OK) rc = pysdr_psk_plan(w->nk, S, max_out, cfg, pl);
-  if (rc != PYSDR_OK) { delete w; return rc; }
-  w->max_out = max_out; w->cfg = *cfg;
-  psk_plan(w->nk, S, max_out, cfg, &w->plan);
-  w->h_tw.assign(tw, tw + 2 * 32 * (size_t)S);
-  w->h_g.assign(g, g + 2 * (size_t)S);
-  const size_t nf = (size_t)w->plan.nfine;
-  w->h_si.assign((size_t)kPskStateInts * nf, 0);
-  for (size_t i = 0; i < nf; ++i) w->h_si[nf + i] = S;                 // cnt = S
-  return client_create(w, "pysdr_psk_create", psk_alloc, psk_reset_locked, out);
+  return skimmer_create("pysdr_psk_create", ch && cfg && tw && g, "NULL channelizer, cfg, tw or g", ch, max_out, out, psk_alloc, psk_reset_locked,
+                        [&](pysdr_psk* w) -> int {
+    int32_t pl[8];
+    if (!psk_plan(w->nk, S, max_out, cfg, &w->plan)) return pysdr_psk_plan(w->nk, S, max_out, cfg, pl);
+    w->cfg = *cfg;
+    w->rows = w->plan.nfine; w->words = w->plan.cap;
+    w->h_tw.assign(tw, tw + 2 * 32 * (size_t)S);
+    w->h_g.assign(g, g + 2 * (size_t)S);
+    const size_t nf = (size_t)w->plan.nfine;
+    w->h_si.assign((size_t)kPskStateInts * nf, 0);
+    for (size_t i = 0; i < nf; ++i) w->h_si[nf + i] = S;               // cnt = S
+    return PYSDR_OK;
+  });
 }
 
 void pysdr_psk_destroy(pysdr_psk* w) { client_destroy(w); }
-
-int pysdr_psk_reset(pysdr_psk* w) {
-  if (!w) { set_last_error("pysdr_psk_reset: NULL skimmer"); return PYSDR_ERR_ARG; }
-  std::lock_guard<std::mutex> lk(w->mu);
-  return psk_reset_locked(w);
-}
-
-int pysdr_psk_sync(pysdr_psk* w) {
-  if (!w) { set_last_error("pysdr_psk_sync: NULL skimmer"); return PYSDR_ERR_ARG; }
-  return client_sync(w);
-}
+int pysdr_psk_reset(pysdr_psk* w) { return skimmer_reset(w, "pysdr_psk_reset", psk_reset_locked); }
+int pysdr_psk_sync(pysdr_psk* w) { return skimmer_sync(w, "pysdr_psk_sync"); }
 
 int pysdr_psk_process(pysdr_psk* w, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
                       long long ev_pitch, float* qn, int32_t* open) {
-  if (!w || !n_out) { set_last_error("pysdr_psk_process: NULL skimmer or n_out"); return PYSDR_ERR_ARG; }
-  *n_out = 0;
-  std::lock_guard<std::mutex> lk(w->mu);
-  ClientStep step;
-  int rc = client_begin(w, "pysdr_psk_process", iq, n, &step);
-  if (rc != PYSDR_OK) return rc;
-  if (events && ev_pitch < w->plan.cap) {
-    set_last_error("pysdr_psk_process: ev_pitch %lld < the event cap %d", ev_pitch, w->plan.cap);
-    return PYSDR_ERR_STATE;
-  }
-  if (step.nf_want > (unsigned long long)w->max_out) {
-    set_last_error("pysdr_psk_process: the call would complete %llu outputs, max_out is %d", step.nf_want, w->max_out);
-    return PYSDR_ERR_STATE;
-  }
-  int nf = 0;
-  rc = client_feed(w, "pysdr_psk_process", "skimmer", iq, n, on_device, w->d_y.get() + kPskHpad, w->plan.ypitch, step, &nf);
-  if (rc != PYSDR_OK) return rc;
-  const size_t nfine = (size_t)w->plan.nfine;
-  PYSDR_HIP_CHECK(hipSetDevice(w->device));
-  hipStream_t st = w->stream;
-  if (nf == 0) {                                                       // no output: nothing launched, no state change, no event
-    if (counts) std::memset(counts, 0, nfine * sizeof(int32_t));
-  } else {
+  return skimmer_process(w, "pysdr_psk_process", iq, n, on_device, n_out, counts, events, ev_pitch,
+                         [&](const ClientStep& step, int nf, hipStream_t st) -> int {
+    if (nf == 0) return PYSDR_OK;
     PskArgs a{};
-    a.y = w->d_y.get() + kPskHpad; a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
+    a.y = w->feed_rows(); a.ypitch = w->plan.ypitch; a.n_out = nf; a.nk = w->nk; a.cap = w->plan.cap; a.nfine = w->plan.nfine;
     a.m0_mod = (int)(step.m0 % (unsigned long long)(32 * w->plan.S));
     a.cfg = w->cfg; a.tw = w->d_tw.get(); a.g = w->d_g.get();
     a.e = w->d_e.get(); a.sf = w->d_sf.get(); a.si = w->d_si.get(); a.events = w->d_events.get(); a.counts = w->d_counts.get();
-    rc = launch_psk_decode(w->plan.S, a, st);
-    if (rc) return rc;
-    *n_out = nf;
-    if (counts) PYSDR_HIP_CHECK(hipMemcpyAsync(counts, a.counts, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (events)
-      PYSDR_HIP_CHECK(hipMemcpy2DAsync(events, (size_t)ev_pitch * sizeof(int32_t), a.events, (size_t)a.cap * sizeof(int32_t),
-                                       (size_t)a.cap * sizeof(int32_t), nfine, hipMemcpyDeviceToHost, st));
-  }
-  if (qn) PYSDR_HIP_CHECK(hipMemcpyAsync(qn, w->d_sf.get(), nfine * sizeof(float), hipMemcpyDeviceToHost, st));
-  if (open) PYSDR_HIP_CHECK(hipMemcpyAsync(open, w->d_si.get() + 3 * nfine, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  if (counts || events || qn || open || !on_device) PYSDR_HIP_CHECK(hipStreamSynchronize(st));   // host buffers are the caller's again
-  return PYSDR_OK;
+    return launch_psk_decode(w->plan.S, a, st);
+  }, qn || open, [&](hipStream_t st) -> int {                          // the state as it stands, on an empty call too
+    const size_t nfine = (size_t)w->plan.nfine;
+    if (qn) PYSDR_HIP_CHECK(hipMemcpyAsync(qn, w->d_sf.get(), nfine * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (open) PYSDR_HIP_CHECK(hipMemcpyAsync(open, w->d_si.get() + 3 * nfine, nfine * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return PYSDR_OK;
+  });
 }
 
 int pysdr_psk_fetch(pysdr_psk* w, const int* rows, int nrows, int32_t* events, long long pitch) {
-  if (!w) { set_last_error("pysdr_psk_fetch: NULL skimmer"); return PYSDR_ERR_ARG; }
-  return client_fetch_events(w, "pysdr_psk_fetch", "fine row", w->d_events.get(), w->plan.nfine, w->plan.cap, rows, nrows, events, pitch);
+  return skimmer_fetch(w, "pysdr_psk_fetch", "fine row", rows, nrows, events, pitch);
 }
 
 int pysdr_psk_state(pysdr_psk* w, float* e, float* f, int32_t* ints) {
-  if (!w) { set_last_error("pysdr_psk_state: NULL skimmer"); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer("pysdr_psk_state");
   std::lock_guard<std::mutex> lk(w->mu);
   PYSDR_HIP_CHECK(hipSetDevice(w->device));
   hipStream_t st = w->stream;

@@ -1,9 +1,11 @@
-// What the objects that borrow a channelizer share -- channel bank (api_objects.hip), CW skimmer (api_cw.hip), PSK31 skimmer
-// (api_psk.hip): each queues its own kernel behind the channelizer's launch, on the channelizer's stream, with no host
-// synchronisation in between.  Here, once: the borrowed handle's fields, the two steps of a call around the client's own
-// checks (what the channelizer is about to complete; the channelizer's pass into the client's row buffer), the copy of
-// fetched rows, sync and destroy.  A client knows the channelizer through chan_info() alone (objects_plan.h), so it runs
-// on either kind of handle (chan_object.h) unchanged.  Host only; not part of the public ABI.
+// What the objects that borrow a channelizer share -- the channel bank (api_objects.hip) and, through skimmer_host.h, the
+// five skimmers (api_cw.hip, api_psk.hip, api_fsk.hip, api_ft.hip): each queues its own kernel behind the channelizer's
+// launch, on the channelizer's stream, with no host synchronisation in between.  Here, once: the borrowed handle's
+// fields, the two steps of a call around the client's own checks (what the channelizer is about to complete; the
+// channelizer's pass into the client's row buffer), the copy of fetched rows, sync, destroy and the tail of create.  The
+// layer above it that the skimmers share -- event rows, the handle check, the whole call list -- is skimmer_host.h.  A
+// client knows the channelizer through chan_info() alone (objects_plan.h), so it runs on either kind of handle
+// (chan_object.h) unchanged.  Host only; not part of the public ABI.
 #pragma once
 
 #include "host_res.h"

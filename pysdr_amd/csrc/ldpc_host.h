@@ -1,13 +1,13 @@
-// The host half of the LDPC decoder, shared by the FT8 and the FT4 skimmer (api_ft.hip) over chan_client.h:
+// The host half of the LDPC decoder, shared by the FT8 and the FT4 skimmer (api_ft.hip) over skimmer_host.h:
 // the result buffers a skimmer owns, and the two calls -- candidates from the spectrum ring, soft bits from the host --
 // written once for both objects, which name their fields alike (plan, t_done, d_ring, d_cand, h_cand, d_llr).  A call may
 // ask for the second stage, ordered-statistics decoding (osd.hip), launched behind min-sum on the same stream.  Every
 // check comes before any launch: a refusal changes nothing.  Host only; not part of the public ABI.
 #pragma once
 
-#include "chan_client.h"
 #include "ldpc_plan.h"
 #include "osd_plan.h"
+#include "skimmer_host.h"
 
 namespace pysdr {
 
@@ -87,7 +87,7 @@ template <class W>
 int ldpc_decode_ring(W* w, const char* who, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
                      uint8_t* bits, float* post, const OsdCall& osd = kNoOsd) {
   using Mode = typename W::Mode;
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   if (!ldpc_call_ok(who, n, cfg, F, t0, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   std::lock_guard<std::mutex> lk(w->mu);
   const long long done = (long long)w->t_done;
@@ -116,7 +116,7 @@ int ldpc_decode_ring(W* w, const char* who, const int32_t* F, const long long* t
 template <class W>
 int ldpc_decode_llr(W* w, const char* who, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                     float* post, const OsdCall& osd = kNoOsd) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   if (!ldpc_call_ok(who, n, cfg, llr, llr, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   const long long bad = ldpc_first_nonfinite(llr, (size_t)n * kLdpcN);
   if (bad >= 0) {

@@ -1,12 +1,12 @@
 // The host half of the frame report and the row floor, shared by the FT8 and the FT4 skimmer
-// (api_ft.hip) over chan_client.h as ldpc_host.h is: the buffers a skimmer owns for it, and the two calls,
+// (api_ft.hip) over skimmer_host.h as ldpc_host.h is: the buffers a skimmer owns for it, and the two calls,
 // written once for both objects, which name their fields alike (plan, t_done, d_ring).  The mask of places a candidate may
 // read is computed here, per candidate, by report_plan.h's pure function.  Every check comes before any launch: a refusal
 // changes nothing.  Host only; not part of the public ABI.
 #pragma once
 
-#include "chan_client.h"
 #include "report_plan.h"
+#include "skimmer_host.h"
 
 namespace pysdr {
 
@@ -36,7 +36,7 @@ template <class W>
 int report_frames(W* w, const char* who, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
   using Mode = typename W::Mode;
   constexpr int lag = kFtLag<Mode>;
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   if (!report_n_ok(n) || (n > 0 && (!F || !t0 || !bits || !power || !errs))) {
     set_last_error("%s: n %d outside [0, %d] / NULL F, t0, bits, power or errs", who, n, kReportMax);
     return PYSDR_ERR_ARG;
@@ -86,7 +86,7 @@ int report_frames(W* w, const char* who, const int32_t* F, const long long* t0, 
 // Every bin of every row summed over the nsym symbol steps that end at t_end.
 template <class W>
 int report_floor(W* w, const char* who, long long t_end, int nsym, float* out) {
-  if (!w) { set_last_error("%s: NULL skimmer", who); return PYSDR_ERR_ARG; }
+  if (!w) return no_skimmer(who);
   if (!floor_nsym_ok(nsym) || !out) {
     set_last_error("%s: nsym %d outside [1, %d] / NULL out", who, nsym, kFloorSymsMax);
     return PYSDR_ERR_ARG;

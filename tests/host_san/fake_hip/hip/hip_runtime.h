@@ -106,6 +106,7 @@ struct Line {
   explicit Line(const char* what) : s(what) {}
   Line& i(const char* k, long long v) { s += ' '; s += k; s += '='; s += std::to_string(v); return *this; }
   Line& f(const char* k, double v) { char b[64]; std::snprintf(b, sizeof(b), " %s=%a", k, v); s += b; return *this; }   // bit for bit
+  Line& t(const char* k, const char* text) { s += ' '; s += k; s += "=\""; s += text; s += '"'; return *this; }
   Line& p(const char* k, const void* ptr) { s += ' '; s += k; s += '='; s += ptr_name(ptr); return *this; }
   Line& st(const void* stream) { s += ' '; s += stream_name(stream); return *this; }
   Line& ev(const void* e) { s += ' '; s += event_name(e); return *this; }

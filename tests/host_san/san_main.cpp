@@ -34,6 +34,7 @@
 #define FAILS(expr)                                                                                 \
   do {                                                                                              \
     if ((expr) == 0) { std::fprintf(stderr, "%s:%d %s unexpectedly succeeded\n", __FILE__, __LINE__, #expr); std::exit(1); } \
+    if (fake_hip::tracing()) fake_hip::Line("refused").t("error", pysdr_last_error());   /* the queue trace holds the message texts too */ \
   } while (0)
 
 struct Rate { double fs; int up, down, in_chunk; };

@@ -1,5 +1,6 @@
 // The launch layer of libpysdr_hip.so for the sanitizer build of its HOST half (tests/host_san):
-// every launch_* that the host files call (api.hip, api_objects.hip, api_cw.hip, api_psk.hip, api_fine.hip), as a host
+// every launch_* that the host files call (api.hip, api_objects.hip, api_cw.hip, api_psk.hip, api_fine.hip; the two
+// skimmers bring skimmer_host.h, the call list they share with api_fsk.hip and api_ft.hip, into the build), as a host
 // function that
 //   * reads every input element and writes every output element the real kernel is entitled to touch
 //     (the "device" memory is malloc'ed by the fake HIP runtime, so AddressSanitizer checks the sizes and
