@@ -724,6 +724,61 @@ int  pysdr_ft4_report(pysdr_ft4* ft4, const int32_t* F, const long long* t0, con
 int  pysdr_ft8_floor(pysdr_ft8* ft8, long long t_end, int nsym, float* out);
 int  pysdr_ft4_floor(pysdr_ft4* ft4, long long t_end, int nsym, float* out);
 
+/* ---- Second pass: subtract decoded frames, search the residue ---------------------------------------
+ * Off unless pysdr_ft8_keep / pysdr_ft4_keep is called, which is allowed only before the stream begins (after create or
+ * reset; PYSDR_ERR_STATE later).  From then on every process call also copies its outputs into a sample ring yk [nk][TY]
+ * (row sample n at n mod TY) and its new steps into a residue ring ring2 [nk][TR2][NB] (step t at t mod TR2), which is
+ * bit for bit the spectrum ring until a subtraction touches it; reset clears both.  The first pass never reads either.
+ * TR2 = hold + 2 reach_t + 4 + max_out / QS + 1 steps, TY = QS TR2 + S rounded up to 16; each ring is at most 2^30 bytes.
+ * cfg: reach_t in [1, 120], trials in [1, 9], pulse [P S] uint32 (P = 3, FT4: 5: the cumulative phase of one symbol of
+ * tone 1 over the P symbols its frequency pulse spans, 2^32 a turn, the last entry 2^32 = 0), lut [4096][2] = (cos, sin)
+ * (2 pi i / 4096); both tables derived by the caller in float64 and rounded once.
+ * pysdr_*_subtract: n <= 256 frames (F[i], t0[i]) with bits [n][12] as pysdr_*_report takes them and trials
+ * [n][cfg.trials][2] = (dn, fw): dn, |dn| < QS, the row samples the frame starts away from QS t0, fw the 32-bit phase word
+ * per row sample of tone 0's offset from fine row F.  Every row that holds tones of the frame is a job -- the frame's own
+ * and at most one neighbour; the jobs of a row run in the order given.  A job builds the unit reference r[n] =
+ * lut[(phase + 2^19) >> 20], phase = n (w + fw) + sum of tone[k'] pulse[..] over the symbols whose pulse covers the sample
+ * (w: tone 0's word in that row, round(q 2^32 / (4 S))), takes a_k = (1 / S) sum y[n] conj(r[n]) per symbol k (n ascending)
+ * for every trial, picks the trial of greatest sum |a_k|^2 (k ascending; the lower index on a tie) and sets y[n] -= a_k r[n]
+ * in yk.  A symbol with a sample before the stream's start is left alone.  out [n][2][4] per (frame, row job): the bits of
+ * the float32 power of the symbols used before and after, the trial chosen, the symbols used (zeros where a frame has
+ * one job).  Then the steps t0 - 4 .. t0 + lag + 4 of ring2 are recomputed from yk for every job's row, with the streaming
+ * kernel's arithmetic.  PYSDR_ERR_STATE unless those steps are all complete and held.
+ * pysdr_*_rescan: the fine rows F_lo .. F_hi (at most 256) of ring2 scored at the start steps t_lo - 4 .. t_hi + 4 (at most
+ * 256) and judged by the streaming kernel's peak rule at t_lo .. t_hi under cfg; counts [nF], events [nF][52][2], the
+ * existing two words with the step counted from t_lo.  PYSDR_ERR_STATE unless every such frame is whole and held.
+ * pysdr_*_pass_decode: pysdr_*_decode_osd on ring2 (osd may be NULL: min-sum alone; detail then must be NULL).
+ * pysdr_*_pass_llr: pysdr_*_llr on ring2.
+ * pysdr_*_pass_state: yk [nk][TY][2] and ring2 (either may be NULL); kept = {row samples so far, TY, TR2}.
+ * Every call checks all of its arguments before any launch, and a refusal changes nothing; PYSDR_ERR_STATE without keep.
+ * pysdr_pass_plan needs no device: mode PYSDR_REPORT_FT8 / FT4 -> out = {threads, LDS bytes, TY, TR2, jobs per call,
+ * frames per call, events per fine row of a rescan, P}. */
+typedef struct pysdr_pass_cfg {
+  int32_t reach_t;
+  int32_t trials;
+  const uint32_t* pulse;
+  const float* lut;
+} pysdr_pass_cfg;
+int  pysdr_pass_plan(int mode, int nk, int S, int max_out, int reach_t, int32_t out[8]);
+int  pysdr_ft8_keep(pysdr_ft8* ft8, const pysdr_pass_cfg* cfg);
+int  pysdr_ft4_keep(pysdr_ft4* ft4, const pysdr_pass_cfg* cfg);
+int  pysdr_ft8_subtract(pysdr_ft8* ft8, const int32_t* F, const long long* t0, const uint8_t* bits, const int32_t* trials, int n,
+                        int32_t* out);
+int  pysdr_ft4_subtract(pysdr_ft4* ft4, const int32_t* F, const long long* t0, const uint8_t* bits, const int32_t* trials, int n,
+                        int32_t* out);
+int  pysdr_ft8_rescan(pysdr_ft8* ft8, int F_lo, int F_hi, long long t_lo, long long t_hi, const pysdr_ft8_cfg* cfg, int32_t* counts,
+                      int32_t* events);
+int  pysdr_ft4_rescan(pysdr_ft4* ft4, int F_lo, int F_hi, long long t_lo, long long t_hi, const pysdr_ft4_cfg* cfg, int32_t* counts,
+                      int32_t* events);
+int  pysdr_ft8_pass_decode(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                           uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+int  pysdr_ft4_pass_decode(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                           uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail);
+int  pysdr_ft8_pass_llr(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, float* out);
+int  pysdr_ft4_pass_llr(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, float* out);
+int  pysdr_ft8_pass_state(pysdr_ft8* ft8, float* yk, float* ring2, long long* kept);
+int  pysdr_ft4_pass_state(pysdr_ft4* ft4, float* yk, float* ring2, long long* kept);
+
 /* ---- device memory for resident streams --------------------------------------- */
 int pysdr_dev_alloc(int device, size_t bytes, void** out);
 int pysdr_dev_free(int device, void* p);

@@ -68,6 +68,10 @@ class OsdCfg(C.Structure):
     _fields_ = [("order", C.c_int32)]
 
 
+class PassCfg(C.Structure):
+    _fields_ = [("reach_t", C.c_int32), ("trials", C.c_int32), ("pulse", C.POINTER(C.c_uint32)), ("lut", C.POINTER(C.c_float))]
+
+
 class FskCfg(C.Structure):
     _fields_ = [("a_q", C.c_float), ("a_b", C.c_float), ("hi", C.c_float), ("lo", C.c_float), ("bal", C.c_float),
                 ("pmax", C.c_float), ("n0", C.c_int32)]
@@ -233,6 +237,15 @@ PROTOTYPES = {
     "pysdr_ft4_report": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), _i, _pf, C.POINTER(C.c_int32)]),
     "pysdr_ft8_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
     "pysdr_ft4_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
+    "pysdr_pass_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    **{f"pysdr_{k}_{what}": (_i, [_vp] + args) for k, cfg in (("ft8", Ft8Cfg), ("ft4", Ft4Cfg)) for what, args in (
+        ("keep", [C.POINTER(PassCfg)]),
+        ("subtract", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
+        ("rescan", [_i, _i, C.c_longlong, C.c_longlong, C.POINTER(cfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        ("pass_decode", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf,
+                         C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
+        ("pass_llr", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
+        ("pass_state", [_pf, _pf, C.POINTER(C.c_longlong)]))},
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -9,6 +9,7 @@
 // the row floor's report_host.h's; both read the mode from the skimmer.
 #include "ft_plan.h"
 #include "ldpc_host.h"
+#include "pass_host.h"
 #include "report_host.h"
 
 using namespace pysdr;
@@ -30,6 +31,7 @@ struct FtSkimmer : SkimmerBase {    // rows = nfine, words = cap * kFtEventWords
   std::vector<int32_t> h_cand;
   LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
   ReportBufs report;                // the frame report's and the row floor's (report_host.h)
+  PassBufs pass;                    // the second pass's rings and tables, once kept (pass_host.h)
   FtC* feed_rows() { return d_y.get() + Mode::kHpad; }
 };
 
@@ -69,11 +71,15 @@ int ft_reset_locked(W* w) {
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_sc.get(), 0, (size_t)kFtKeep * nf * sizeof(float), st));
   PYSDR_HIP_CHECK(hipMemsetAsync(w->d_hi.get(), 0, (size_t)kFtKeep * nf * sizeof(int32_t), st));
   if (const int rc2 = skimmer_clear(w, st)) return rc2;
+  if (const int rc3 = pass_clear(&w->pass, w->nk, w->plan.nb, st)) return rc3;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));
   w->last_n_out = 0;
   w->t_done = 0;
   return PYSDR_OK;
 }
+
+// the first pass's spectrum ring, as the decoder asks for it under the skimmer's lock
+template <class W> RingRef first_ring(W* w) { return RingRef{w->d_ring.get(), w->plan.tr}; }
 
 // `who` in every call below: the public function's name, for the messages
 
@@ -130,14 +136,16 @@ int ft_process(W* w, const char* who, const void* iq, int n, int on_device, int*
     if (a.ns == 0) PYSDR_HIP_CHECK(hipMemsetAsync(a.counts, 0, (size_t)w->rows * sizeof(int32_t), st));   // outputs but no step: only the history rolls
     const int rc = launch_ft_steps(Mode::kLdpcSource, S, a, st);
     if (rc) return rc;
+    if (const int rc2 = pass_step(w, step.m0, nf, a.ns, a.t_first, st)) return rc2;   // (nothing unless pysdr_*_keep was called)
     w->t_done = t1;
     if (steps) steps[1] = a.ns;
     return PYSDR_OK;
   });
 }
 
+// residue: from the second pass's ring2 (PYSDR_ERR_STATE unless kept) instead of the spectrum ring
 template <class W>
-int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, float* out) {
+int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, float* out, bool residue = false) {
   using Mode = typename W::Mode;
   if (!w) return no_skimmer(who);
   if (n < 0 || n > kFtLlrMax || (n > 0 && (!F || !t0 || !out))) {
@@ -145,12 +153,15 @@ int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, 
     return PYSDR_ERR_ARG;
   }
   std::lock_guard<std::mutex> lk(w->mu);
+  if (residue && !w->pass.kept) return pass_not_kept(who);
+  const float* ring = residue ? w->pass.d_ring2.get() : w->d_ring.get();
+  const int tr = residue ? w->pass.plan.tr2 : w->plan.tr;
   const long long done = (long long)w->t_done;
   for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
-    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, tr)) {
       set_last_error("%s: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the "
                      "ring (%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done,
-                     t0[i] + kFtLag<Mode>, w->plan.tr);
+                     t0[i] + kFtLag<Mode>, tr);
       return F[i] < 0 || F[i] >= w->plan.nfine ? PYSDR_ERR_ARG : PYSDR_ERR_STATE;
     }
   if (n == 0) return PYSDR_OK;
@@ -158,10 +169,10 @@ int ft_llr(W* w, const char* who, const int32_t* F, const long long* t0, int n, 
   hipStream_t st = w->stream;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // h_cand may still feed an earlier copy
   w->h_cand.resize((size_t)n * 2);
-  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % w->plan.tr); }
+  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % tr); }
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   FtLlrArgs a{};
-  a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.n = n; a.cand = w->d_cand.get(); a.out = w->d_llr.get();
+  a.ring = ring; a.tr = tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.n = n; a.cand = w->d_cand.get(); a.out = w->d_llr.get();
   const int rc = launch_ft_llr(Mode::kLdpcSource, a, st);
   if (rc) return rc;
   PYSDR_HIP_CHECK(hipMemcpyAsync(out, a.out, (size_t)n * kFtBits * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -213,14 +224,14 @@ int pysdr_ft8_state(pysdr_ft8* w, float* sc, int32_t* hits, float* ring, long lo
 }
 int pysdr_ft8_decode(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                      float* post) {
-  return ldpc_decode_ring(w, "pysdr_ft8_decode", F, t0, n, cfg, status, bits, post);
+  return ldpc_decode_ring(w, "pysdr_ft8_decode", first_ring<std::remove_pointer_t<decltype(w)>>, F, t0, n, cfg, status, bits, post);
 }
 int pysdr_ft8_decode_llr(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
   return ldpc_decode_llr(w, "pysdr_ft8_decode_llr", llr, n, cfg, status, bits, post);
 }
 int pysdr_ft8_decode_osd(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
-  return ldpc_decode_ring(w, "pysdr_ft8_decode_osd", F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+  return ldpc_decode_ring(w, "pysdr_ft8_decode_osd", first_ring<std::remove_pointer_t<decltype(w)>>, F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
 }
 int pysdr_ft8_decode_llr_osd(pysdr_ft8* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                              float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
@@ -230,6 +241,22 @@ int pysdr_ft8_report(pysdr_ft8* w, const int32_t* F, const long long* t0, const 
   return report_frames(w, "pysdr_ft8_report", F, t0, bits, n, power, errs);
 }
 int pysdr_ft8_floor(pysdr_ft8* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft8_floor", t_end, nsym, out); }
+int pysdr_ft8_keep(pysdr_ft8* w, const pysdr_pass_cfg* cfg) { return pass_keep(w, "pysdr_ft8_keep", reinterpret_cast<const PassCfg*>(cfg)); }
+int pysdr_ft8_subtract(pysdr_ft8* w, const int32_t* F, const long long* t0, const uint8_t* bits, const int32_t* trials, int n, int32_t* out) {
+  return pass_subtract(w, "pysdr_ft8_subtract", F, t0, bits, trials, n, out);
+}
+int pysdr_ft8_rescan(pysdr_ft8* w, int F_lo, int F_hi, long long t_lo, long long t_hi, const pysdr_ft8_cfg* cfg, int32_t* counts,
+                     int32_t* events) {
+  return pass_rescan(w, "pysdr_ft8_rescan", F_lo, F_hi, t_lo, t_hi, ft_cfg(cfg), counts, events);
+}
+int pysdr_ft8_pass_decode(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return pass_decode(w, "pysdr_ft8_pass_decode", F, t0, n, cfg, status, bits, post, osd, detail);
+}
+int pysdr_ft8_pass_llr(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, float* out) {
+  return ft_llr(w, "pysdr_ft8_pass_llr", F, t0, n, out, true);
+}
+int pysdr_ft8_pass_state(pysdr_ft8* w, float* yk, float* ring2, long long* kept) { return pass_state(w, "pysdr_ft8_pass_state", yk, ring2, kept); }
 
 // ---- FT4 ---------------------------------------------------------------------------------------------------------------
 int pysdr_ft4_plan(int nk, int S, int max_out, const pysdr_ft4_cfg* cfg, int32_t out[8]) {
@@ -254,14 +281,14 @@ int pysdr_ft4_state(pysdr_ft4* w, float* sc, int32_t* hits, float* ring, long lo
 }
 int pysdr_ft4_decode(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                      float* post) {
-  return ldpc_decode_ring(w, "pysdr_ft4_decode", F, t0, n, cfg, status, bits, post);
+  return ldpc_decode_ring(w, "pysdr_ft4_decode", first_ring<std::remove_pointer_t<decltype(w)>>, F, t0, n, cfg, status, bits, post);
 }
 int pysdr_ft4_decode_llr(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits, float* post) {
   return ldpc_decode_llr(w, "pysdr_ft4_decode_llr", llr, n, cfg, status, bits, post);
 }
 int pysdr_ft4_decode_osd(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
-  return ldpc_decode_ring(w, "pysdr_ft4_decode_osd", F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
+  return ldpc_decode_ring(w, "pysdr_ft4_decode_osd", first_ring<std::remove_pointer_t<decltype(w)>>, F, t0, n, cfg, status, bits, post, OsdCall{true, osd, detail});
 }
 int pysdr_ft4_decode_llr_osd(pysdr_ft4* w, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                              float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
@@ -271,6 +298,22 @@ int pysdr_ft4_report(pysdr_ft4* w, const int32_t* F, const long long* t0, const 
   return report_frames(w, "pysdr_ft4_report", F, t0, bits, n, power, errs);
 }
 int pysdr_ft4_floor(pysdr_ft4* w, long long t_end, int nsym, float* out) { return report_floor(w, "pysdr_ft4_floor", t_end, nsym, out); }
+int pysdr_ft4_keep(pysdr_ft4* w, const pysdr_pass_cfg* cfg) { return pass_keep(w, "pysdr_ft4_keep", reinterpret_cast<const PassCfg*>(cfg)); }
+int pysdr_ft4_subtract(pysdr_ft4* w, const int32_t* F, const long long* t0, const uint8_t* bits, const int32_t* trials, int n, int32_t* out) {
+  return pass_subtract(w, "pysdr_ft4_subtract", F, t0, bits, trials, n, out);
+}
+int pysdr_ft4_rescan(pysdr_ft4* w, int F_lo, int F_hi, long long t_lo, long long t_hi, const pysdr_ft4_cfg* cfg, int32_t* counts,
+                     int32_t* events) {
+  return pass_rescan(w, "pysdr_ft4_rescan", F_lo, F_hi, t_lo, t_hi, ft_cfg(cfg), counts, events);
+}
+int pysdr_ft4_pass_decode(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+                          uint8_t* bits, float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
+  return pass_decode(w, "pysdr_ft4_pass_decode", F, t0, n, cfg, status, bits, post, osd, detail);
+}
+int pysdr_ft4_pass_llr(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, float* out) {
+  return ft_llr(w, "pysdr_ft4_pass_llr", F, t0, n, out, true);
+}
+int pysdr_ft4_pass_state(pysdr_ft4* w, float* yk, float* ring2, long long* kept) { return pass_state(w, "pysdr_ft4_pass_state", yk, ring2, kept); }
 
 // ---- the decoders' and the report's plans, which need no skimmer ---------------------------------------------------------
 int pysdr_ldpc_plan(const pysdr_ldpc_cfg* cfg, int32_t out[4]) {
@@ -290,6 +333,22 @@ int pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]) {
     return PYSDR_ERR_ARG;
   }
   out[0] = kOsdThreads; out[1] = kOsdLdsBytes; out[2] = osd_patterns(cfg->order); out[3] = kLdpcMax;
+  return PYSDR_OK;
+}
+
+int pysdr_pass_plan(int mode, int nk, int S, int max_out, int reach_t, int32_t out[8]) {
+  if (!out) { set_last_error("pysdr_pass_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  PassPlan p;
+  const bool ok = mode == kReportFt8 ? pass_plan<Ft8Mode>(nk, S, max_out, reach_t, &p)
+                                     : (mode == kReportFt4 ? pass_plan<Ft4Mode>(nk, S, max_out, reach_t, &p) : false);
+  if (!ok) {
+    set_last_error("pysdr_pass_plan: mode %d is neither PYSDR_REPORT_FT8 nor PYSDR_REPORT_FT4, S %d is not one of the mode's, nk %d < 1 or "
+                   "nk S / 2 > %d, max_out %d outside [1, %d], reach_t %d outside [1, %d], or a ring above %lld bytes", mode, S, nk, kFtFineMax,
+                   max_out, kFtMaxOutMax, reach_t, kPassReachMax, kFtRingBytesMax);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kPassThreads; out[1] = p.lds_bytes; out[2] = p.ty; out[3] = p.tr2; out[4] = kPassJobsMax; out[5] = kPassMax;
+  out[6] = kPassEventCap; out[7] = mode == kReportFt8 ? kPassPulse<Ft8Mode> : kPassPulse<Ft4Mode>;
   return PYSDR_OK;
 }
 

@@ -278,15 +278,21 @@ PYSDR_FT_HD inline FtScore ft_sync(const float* ring, int tr, int nb, int slot0,
 
 // Step 3: is tc an event?  sc and hi hold the decoder's last 9 scores and hit counts, that of step t at index
 // (t mod 9) * stride; score[tc + 4] is the newest.
-PYSDR_FT_HD inline bool ft_peak(const float* sc, const int32_t* hi, long long stride, long long tc, const FtCfg& c) {
-  const int s0 = (int)(tc % kFtKeep);
-  const float v = sc[s0 * stride];
-  if (!(v >= c.smin) || hi[s0 * stride] < c.hmin) return false;
+// The comparison itself, for any store of scores: v and hits are step tc's, at(d) the score of step tc + d, d = -4 .. 4
+// without 0.  The streaming kernel's nine slots (ft_peak) and the second pass's dense window (pass.hip) both judge with it.
+template <class At>
+PYSDR_FT_HD inline bool ft_peak_rule(float v, int32_t hits, long long tc, const FtCfg& c, At at) {
+  if (!(v >= c.smin) || hits < c.hmin) return false;
   for (int d = 1; d <= kFtReach; ++d) {
-    if (tc - d >= 0 && !(v > sc[((s0 + kFtKeep - d) % kFtKeep) * stride])) return false;
-    if (!(v >= sc[((s0 + d) % kFtKeep) * stride])) return false;
+    if (tc - d >= 0 && !(v > at(-d))) return false;
+    if (!(v >= at(d))) return false;
   }
   return true;
+}
+PYSDR_FT_HD inline bool ft_peak(const float* sc, const int32_t* hi, long long stride, long long tc, const FtCfg& c) {
+  const int s0 = (int)(tc % kFtKeep);
+  return ft_peak_rule(sc[s0 * stride], hi[s0 * stride], tc, c,
+                      [=](int d) { return sc[((s0 + kFtKeep + d) % kFtKeep) * stride]; });
 }
 
 // Soft bit i < 174 of the frame whose first step sits in slot0 of the row's ring, decoder j: data symbol i / 3 (FT4: i / 2),

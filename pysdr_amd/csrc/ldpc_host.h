@@ -81,21 +81,36 @@ int ldpc_run(W* w, int source, LdpcArgs& a, const pysdr_ldpc_cfg* cfg, int32_t* 
   return PYSDR_OK;
 }
 
-// Candidates (F[i], t0[i]) from the ring.  The skimmer's mode (W::Mode, ft_plan.h) gives the rule for a candidate, the
-// last step of a frame behind its first, for the message, and the kernels' source.
-template <class W>
-int ldpc_decode_ring(W* w, const char* who, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
+// A spectrum ring of a skimmer's, ring[nk][tr][nb], as a decode call names it; ring is NULL where there is none.
+struct RingRef {
+  const float* ring;
+  int tr;
+};
+
+// Candidates (F[i], t0[i]) from a spectrum ring of the skimmer's: the first pass's, or the second pass's residue
+// (pass_host.h).  which(w) names it and is asked under the skimmer's lock, so the ring it names cannot be replaced
+// before the launch; a ring that is not there is PYSDR_ERR_STATE.  The skimmer's mode (W::Mode, ft_plan.h) gives the rule for a candidate, the last step of
+// a frame behind its first, for the message, and the kernels' source.
+template <class W, class Which>
+int ldpc_decode_ring(W* w, const char* who, Which which, const int32_t* F, const long long* t0, int n, const pysdr_ldpc_cfg* cfg, int32_t* status,
                      uint8_t* bits, float* post, const OsdCall& osd = kNoOsd) {
   using Mode = typename W::Mode;
   if (!w) return no_skimmer(who);
   if (!ldpc_call_ok(who, n, cfg, F, t0, status, bits) || !osd_call_ok(who, osd)) return PYSDR_ERR_ARG;
   std::lock_guard<std::mutex> lk(w->mu);
+  const RingRef ref = which(w);
+  if (!ref.ring) {
+    set_last_error("%s: nothing is kept for a second pass: call the skimmer's keep after create or reset", who);
+    return PYSDR_ERR_STATE;
+  }
+  const float* ring = ref.ring;
+  const int tr = ref.tr;
   const long long done = (long long)w->t_done;
   for (int i = 0; i < n; ++i)                                          // every candidate first: a refusal changes nothing
-    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, w->plan.tr)) {
+    if (!ft_llr_ok<Mode>(F[i], t0[i], done, w->plan.nfine, tr)) {
       set_last_error("%s: candidate %d (F %d, t0 %lld): F outside [0, %d), or a frame not yet complete or gone from the ring "
                      "(%lld steps done, its last is %lld, the ring holds %d)", who, i, (int)F[i], t0[i], w->plan.nfine, done,
-                     t0[i] + kFtLag<Mode>, w->plan.tr);
+                     t0[i] + kFtLag<Mode>, tr);
       return F[i] < 0 || F[i] >= w->plan.nfine ? PYSDR_ERR_ARG : PYSDR_ERR_STATE;
     }
   if (n == 0) return PYSDR_OK;
@@ -105,10 +120,10 @@ int ldpc_decode_ring(W* w, const char* who, const int32_t* F, const long long* t
   hipStream_t st = w->stream;
   PYSDR_HIP_CHECK(hipStreamSynchronize(st));                          // h_cand may still feed an earlier copy
   w->h_cand.resize((size_t)n * 2);
-  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % w->plan.tr); }
+  for (int i = 0; i < n; ++i) { w->h_cand[2 * (size_t)i] = F[i]; w->h_cand[2 * (size_t)i + 1] = (int32_t)(t0[i] % tr); }
   PYSDR_HIP_CHECK(hipMemcpyAsync(w->d_cand.get(), w->h_cand.data(), (size_t)n * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   LdpcArgs a{};
-  a.ring = w->d_ring.get(); a.tr = w->plan.tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.cand = w->d_cand.get(); a.n = n;
+  a.ring = ring; a.tr = tr; a.nb = w->plan.nb; a.nsub = w->plan.nsub; a.cand = w->d_cand.get(); a.n = n;
   return ldpc_run(w, Mode::kLdpcSource, a, cfg, status, bits, post, osd);
 }
 

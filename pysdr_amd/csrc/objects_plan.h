@@ -212,4 +212,13 @@ struct FloorArgs;
 int launch_frame_report(int mode, const ReportArgs& a, hipStream_t st);  // mode: ReportMode
 int launch_ring_floor(const FloorArgs& a, hipStream_t st);
 
+// ---- second pass (pass.hip, host half pass_host.h; steps and kernel arguments: pass_plan.h) --------------------------------
+struct PassKeepArgs;
+struct PassSubArgs;
+struct PassSpecArgs;
+struct PassScanArgs;
+int launch_pass_keep(const PassKeepArgs& a, hipStream_t st);
+int launch_pass_subtract(int source, int S, const PassSubArgs& a, const PassSpecArgs& s, hipStream_t st);   // subtract, then respectrum
+int launch_pass_rescan(int source, const PassScanArgs& a, hipStream_t st);                                  // source: LdpcSource
+
 }  // namespace pysdr

@@ -17,6 +17,7 @@ from ._lib import Ft4Cfg
 from . import ft8 as _ft8
 from .ft8 import FT8_Decoders, FT8_Skimmer, hard_bits, owners, unit_llr, unpack  # noqa: F401  (this mode's too)
 from .ft8 import cfg_dict, steps_done, tables  # noqa: F401  (no mode's number is in them)
+from .ft8 import pack91, pass_lut, pass_plan, pass_pulse, trial_grid  # noqa: F401  (the second pass's host half)
 from .ft8 import delta, noise_floor, noise_of, refine, snr_db, spots  # noqa: F401  (the frame report's host half)
 
 NAME, PLAN_CALL = "FT4", "pysdr_ft4_plan"
@@ -39,6 +40,11 @@ REPORT_MODE = 1                                  # PYSDR_REPORT_FT4
 TONES = 4
 FLOOR_QUANTILE = 0.02                            # a row's floor: this quantile of its NB bin means, all but the least of them
 FLOOR_ROWS = (4, 8)                              # a candidate's noise: the median floor of the rows this far away: behind the prototype's stop band
+PULSE_SYMBOLS = 5                                # symbols the frequency pulse of ``waveform`` spans (BT = 1)
+PULSE_K = np.pi * np.sqrt(2 / np.log(2))
+REACH_T = 40                                     # steps a rescan looks to either side of a subtracted frame
+TRIAL_DN = 0.25                                  # steps between the trial times (``ft8.py``)
+TRIAL_DF = 1.0                                   # Hz between the trial frequencies: ``ft8.py``'s 0.3 Hz scaled by the baud
 CAL = -0.7                                       # dB: the bias of so low a quantile, measured (tests/test_report_oracle.py)
 
 

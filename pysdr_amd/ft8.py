@@ -322,6 +322,65 @@ def spot_line(rec, f_centre=0.0, slot_seconds=SLOT_SECONDS):
     return f"{when:6s} {int(round(rec['snr'])):3d} {dt:4.1f} {int(round(f_centre + rec['f_fine'])):4d} ~  {rec['text'] or ''}".rstrip()
 
 
+# ---- the second pass: tables and the trial grid, derived here in float64 and rounded once ----------
+PULSE_SYMBOLS = 3                                # symbols the frequency pulse of ``waveform`` spans (BT = 2)
+PULSE_K = 2 * np.pi * np.sqrt(2 / np.log(2))
+REACH_T = 40                                     # steps a rescan looks to either side of a subtracted frame
+PASS_TRIALS, PASS_MAX, PASS_LUT, PASS_EVENT_CAP, PASS_ROWS_MAX, PASS_WINDOW_MAX = 9, 256, 4096, 52, 256, 256
+# The trial grid: 3 times x 3 frequencies around the refined values.  ``refine`` leaves the time within 0.35 step and the
+# frequency within 0.4 Hz, so a quarter step and 0.3 Hz to either side cover both, and the best
+# trial is then within an eighth of a step and 0.15 Hz: about -27 dB of the frame left by the frequency error alone.
+TRIAL_DN = 0.25                                  # steps between the trial times
+TRIAL_DF = 0.3                                   # Hz between the trial frequencies
+
+
+def pass_pulse(mode, S):
+    """uint32 [PULSE_SYMBOLS S]: the phase one symbol of tone 1 has added by row sample i of the symbols its frequency
+    pulse spans, 2^32 a turn: the cumulative sum of ``waveform``'s pulse at the samples' middles, scaled so that the
+    whole pulse is exactly one turn (which the last entry holds as 0)."""
+    import math
+    P = mode.PULSE_SYMBOLS
+    tau = (np.arange(P * S) + 0.5) / S - P / 2
+    erf = np.vectorize(math.erf)
+    g = 0.5 * (erf(mode.PULSE_K * (tau + 0.5)) - erf(mode.PULSE_K * (tau - 0.5)))
+    c = np.cumsum(g)
+    return np.ascontiguousarray((np.rint(c / c[-1] * 2.0 ** 32).astype(np.uint64) & 0xFFFFFFFF).astype(np.uint32))
+
+
+def pass_lut():
+    """float32 [4096][2] = (cos, sin)(2 pi i / 4096)"""
+    t = 2 * np.pi * np.arange(PASS_LUT) / PASS_LUT
+    return np.ascontiguousarray(np.stack((np.cos(t), np.sin(t)), axis=1), np.float32)
+
+
+def pass_plan(mode, nk, S, max_out, reach_t=None):
+    """What a second pass keeps and launches (no device needed): dict of threads, LDS bytes, ty (samples of a row kept),
+    tr2 (steps kept), jobs and frames per subtract call, events per fine row of a rescan, symbols of the pulse."""
+    v = _lib.plan_call("pysdr_pass_plan", 8, int(mode.REPORT_MODE), int(nk), int(S), int(max_out), int(mode.REACH_T if reach_t is None else reach_t))
+    return dict(zip(("threads", "lds_bytes", "ty", "tr2", "max_jobs", "max_frames", "event_cap", "pulse_symbols"), v))
+
+
+def trial_grid(mode, df, dt, qs, fs_out):
+    """int32 [9][2] = (dn, fw): the refined offsets ``df`` (raster steps of baud / 2) and ``dt`` (steps) -> 3 times (outer)
+    x 3 frequencies (inner) around them: dn in row samples, fw the phase word per row sample.  ``subtract`` refuses a dn of
+    a step or more, so a trial time beyond QS - 1 samples is MOVED to QS - 1 (-(QS - 1)): that trial is then not the one the
+    grid asked for.  ``refine`` leaves |dt| <= 0.5, so only the outer trials of a frame half a step off are moved, by at
+    most QS / 4 - 1 samples."""
+    out = np.zeros((9, 2), np.int64)
+    for a, it in enumerate((-1, 0, 1)):
+        dn = int(np.clip(np.rint((dt + it * mode.TRIAL_DN) * qs), -(qs - 1), qs - 1))
+        for b, jf in enumerate((-1, 0, 1)):
+            hz = df * mode.BAUD / 2 + jf * mode.TRIAL_DF
+            out[3 * a + b] = dn, int(np.rint(hz / fs_out * 2.0 ** 32))
+    return (out & 0xFFFFFFFF).astype(np.uint32).view(np.int32)              # (dn as its two's complement, which int32 reads back)
+
+
+def pack91(bits91, n):
+    """uint8 [n][91] -> [n][12], MSB first, as the decoder packs them"""
+    b = np.ascontiguousarray(bits91, np.uint8).reshape(n, _ldpc.K) & 1
+    return np.ascontiguousarray(np.packbits(np.concatenate((b, np.zeros((n, 5), np.uint8)), axis=1), axis=1))
+
+
 class FT8_Decoders(DecoderBank):
     """The decoder bank on a borrowed ``Channelizer`` (which it resets, and which must be fed only through it)."""
     KIND, DESTROY = "ft8", "pysdr_ft8_destroy"
@@ -397,7 +456,7 @@ class FT8_Decoders(DecoderBank):
             raise ValueError("detail is the second stage's: it needs osd")
         return osd, np.zeros((n, 4), np.int32) if detail else None
 
-    def decode(self, F, t0, cfg=None, post=False, osd=None, detail=False):
+    def decode(self, F, t0, cfg=None, post=False, osd=None, detail=False, residual=False):
         """The candidates (F[i], t0[i]) of ``llr``, under its rules, through the LDPC decoder on the device, straight from
         the spectrum ring (``cfg``: ``ldpc.params()``).  -> dict of status int32 [n] (2: a codeword with
         a good CRC and a message that is not all zero, 1: any other codeword, 0: none), iterations, nerr (hard bits the
@@ -405,18 +464,24 @@ class FT8_Decoders(DecoderBank):
         post float32 [n][174], the decoder's final sums.  With ``osd`` (an order 0 to 2 or ``ldpc.osd_params()``) the
         candidates min-sum left without a message go through ordered-statistics decoding in a second launch (DESIGN.md 3
         item 25) and the answer gains osd int32 [n] (0: the stage did not run; 1, 2, 3: it did and no, one or two rows of
-        the basis were flipped) and, with ``detail``, detail int32 [n][4] (k, last, weight, the distance's bits)."""
+        the basis were flipped) and, with ``detail``, detail int32 [n][4] (k, last, weight, the distance's bits).
+        ``residual``: from the second pass's residue (``keep``) instead of the spectrum ring."""
         F = np.ascontiguousarray(F, np.int32)
         t0 = np.ascontiguousarray(t0, np.int64)
         cfg = _ldpc.params() if cfg is None else cfg
         osd, de = self._osd(osd, detail, len(F))
         st, bits, po = self._decoded(len(F), post)
+        if residual:
+            self._need_kept()
         for i in range(0, len(F), LLR_MAX):
             f, t = F[i:i + LLR_MAX], t0[i:i + LLR_MAX]
             args = (f.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_longlong)), len(f), C.byref(cfg),
                     st[i:].ctypes.data_as(C.POINTER(C.c_int32)), bits[i:].ctypes.data_as(C.POINTER(C.c_uint8)),
                     None if po is None else _lib.as_pf(po[i:]))
-            if osd is None:
+            if residual:
+                self._call("pass_decode", *args, None if osd is None else C.byref(osd),
+                           None if de is None else de[i:].ctypes.data_as(C.POINTER(C.c_int32)))
+            elif osd is None:
                 self._call("decode", *args)
             else:
                 self._call("decode_osd", *args, C.byref(osd), None if de is None else de[i:].ctypes.data_as(C.POINTER(C.c_int32)))
@@ -467,6 +532,83 @@ class FT8_Decoders(DecoderBank):
         self._call("floor", C.c_longlong(t_end), nsym, _lib.as_pf(out))
         return out
 
+    # ---- the second pass ---------------------------------------------------------------------------
+    kept = None                                                          # ``keep``'s plan once it was called
+
+    def keep(self, reach_t=None, trials=PASS_TRIALS):
+        """From now on -- allowed only before the stream begins, after create or ``reset`` -- every call also keeps its
+        row samples and a second spectrum ring for ``subtract``, ``rescan`` and ``decode(residual=True)``.  ``reach_t``:
+        steps a rescan will look to either side of a subtracted frame (default the mode's ``REACH_T``); ``trials``: the
+        (dn, fw) pairs every frame of a ``subtract`` call carries.  -> the plan (``pass_plan``)."""
+        m = self.MODE
+        reach_t = m.REACH_T if reach_t is None else int(reach_t)
+        plan = pass_plan(m, self.nk, self.S, self.max_out, reach_t)          # a bad reach_t fails here
+        self._pulse, self._lut = pass_pulse(m, self.S), pass_lut()
+        cfg = _lib.PassCfg(reach_t=reach_t, trials=int(trials), pulse=self._pulse.ctypes.data_as(C.POINTER(C.c_uint32)), lut=_lib.as_pf(self._lut))
+        self._call("keep", C.byref(cfg))
+        self.kept = dict(plan, reach_t=reach_t, trials=int(trials))
+        return self.kept
+
+    def _need_kept(self):
+        if self.kept is None:
+            raise _lib.PysdrError(f"{type(self).__name__}: nothing is kept for a second pass: call keep() first")
+
+    def subtract(self, F, t0, bits91, trials):
+        """Take the frames (F[i], t0[i]) with the 91 bits of each out of the kept row samples and recompute the steps they
+        touch in the residue.  ``trials`` int32 [n][kept trials][2] = (dn, fw) (``trial_grid``).  -> dict of before, after
+        float32 [n][2] (power of the frame's symbols in its own row and in the neighbour that holds some of its tones, 0
+        where there is none), trial and used int32 [n][2].  At most 256 frames; PysdrError for a frame whose steps
+        t0 - 4 .. t0 + lag + 4 are not all complete and held."""
+        self._need_kept()
+        F = np.ascontiguousarray(F, np.int32)
+        t0 = np.ascontiguousarray(t0, np.int64)
+        packed = pack91(bits91, len(F))
+        tr = np.ascontiguousarray(trials, np.int32).reshape(len(F), self.kept["trials"], 2)
+        out = np.zeros((len(F), 2, 4), np.int32)
+        p32 = C.POINTER(C.c_int32)
+        self._call("subtract", F.ctypes.data_as(p32), t0.ctypes.data_as(C.POINTER(C.c_longlong)), packed.ctypes.data_as(C.POINTER(C.c_uint8)),
+                   tr.ctypes.data_as(p32), len(F), out.ctypes.data_as(p32))
+        pw = np.ascontiguousarray(out[:, :, :2]).view(np.float32)
+        return dict(before=pw[:, :, 0].copy(), after=pw[:, :, 1].copy(), trial=out[:, :, 2].copy(), used=out[:, :, 3].copy())
+
+    def rescan(self, F_lo, F_hi, t_lo, t_hi, cfg=None):
+        """The sync score of the fine rows F_lo .. F_hi of the residue at the start steps t_lo - 4 .. t_hi + 4, judged at
+        t_lo .. t_hi by the streaming peak rule under ``cfg`` (default the bank's) -> events (t0, F, score, hits) sorted by
+        (F, t0).  At most 256 fine rows and 256 start steps."""
+        self._need_kept()
+        cfg = self.cfg if cfg is None else cfg
+        nF = int(F_hi) - int(F_lo) + 1
+        counts = np.zeros(max(nF, 1), np.int32)
+        ev = np.zeros((max(nF, 1), PASS_EVENT_CAP, 2), np.int32)
+        p32 = C.POINTER(C.c_int32)
+        self._call("rescan", int(F_lo), int(F_hi), C.c_longlong(int(t_lo)), C.c_longlong(int(t_hi)), C.byref(cfg), counts.ctypes.data_as(p32),
+                   ev.ctypes.data_as(p32))
+        out = []
+        for k in range(nF):
+            for i in range(int(counts[k])):
+                u, hits, score = unpack(ev[k, i])
+                out.append((int(t_lo) + u, int(F_lo) + k, score, hits))
+        return out
+
+    def pass_llr(self, F, t0):
+        """``llr`` from the residue"""
+        self._need_kept()
+        F = np.ascontiguousarray(F, np.int32)
+        t0 = np.ascontiguousarray(t0, np.int64)
+        out = np.zeros((len(F), self.MODE.BITS), np.float32)
+        self._call("pass_llr", F.ctypes.data_as(C.POINTER(C.c_int32)), t0.ctypes.data_as(C.POINTER(C.c_longlong)), len(F), _lib.as_pf(out))
+        return out
+
+    def pass_state(self):
+        """dict of yk complex64 [nk][TY] (row sample n at n mod TY), ring2 float32 [nk][TR2][NB] (step t at t mod TR2) and
+        n_kept, the row samples since create / reset"""
+        self._need_kept()
+        yk = np.empty((self.nk, self.kept["ty"]), np.complex64)
+        r2 = np.empty((self.nk, self.kept["tr2"], self.nb), np.float32)
+        info = (C.c_longlong * 3)()
+        self._call("pass_state", yk.ctypes.data_as(C.POINTER(C.c_float)), _lib.as_pf(r2), info)
+        return dict(yk=yk, ring2=r2, n_kept=int(info[0]))
+
     def state(self, ring=False):
         """dict of sc float32 [9][nfine] and hits int32 [9][nfine] (frame start t at index t mod 9), t_done, and with
         ``ring`` the spectrum ring float32 [nk][TR][NB] (step t at index t mod TR)"""
@@ -489,7 +631,10 @@ class FT8_Skimmer(Skimmer):
     With ``decode=True`` the owners go through the LDPC decoder on the device (``ldpc``: ``ldpc.params()``) and a record
     gains ``status``, ``ok`` (status 2), ``iterations``, ``nerr``, ``bits77``, ``i3``, ``n3`` and ``text`` (None where the
     frame did not decode or its message type is not unpacked); ``keep_llr=False`` then skips the soft bits' download and
-    the records carry no ``llr``.  ``osd=2`` (an order 0 to 2, or ``ldpc.osd_params()``) sends the frames min-sum could not
+    the records carry no ``llr``.  ``passes=2`` (with ``decode=True``; ``reach_t`` steps, default the mode's ``REACH_T``) takes
+    every decoded frame out of the kept row samples once it is due and searches the residue around it again (``_second``;
+    DESIGN.md 3 item 27): every record then carries ``pass``, 1 or 2, and a record of pass 2 is a frame found under a
+    stronger one (its ``llr`` is the residue's); ``report=True`` is refused with it, for the report reads the first ring.  ``osd=2`` (an order 0 to 2, or ``ldpc.osd_params()``) sends the frames min-sum could not
     decode through ordered-statistics decoding and a record gains ``osd``: 0, the stage did not
     run; 1, 2, 3, it did.  Off by default: the CRC-14 is that stage's only guard, and a frame that reaches it comes out as
     a false message with probability about 2^-14.  ``report=True`` measures every decoded frame in the spectrum ring
@@ -501,8 +646,17 @@ class FT8_Skimmer(Skimmer):
     DECODERS = FT8_Decoders                                              # the bank; its MODE is the skimmer's too
 
     def __init__(self, fs, channels=None, device=0, max_in=1 << 22, max_out=256, chan=None, t_first=None, decode=False, ldpc=None,
-                 keep_llr=True, osd=None, report=False):
+                 keep_llr=True, osd=None, report=False, passes=1, reach_t=None):
         m = self.DECODERS.MODE
+        self.passes = int(passes)
+        if self.passes not in (1, 2):
+            raise ValueError(f"{type(self).__name__}: passes is 1 or 2")
+        if self.passes == 2 and not decode:
+            raise ValueError(f"{type(self).__name__}: the second pass subtracts decoded frames: it needs decode=True")
+        if self.passes == 2 and report:
+            raise ValueError(f"{type(self).__name__}: the frame report reads the first spectrum ring, which a frame of the second pass "
+                             f"may have left: passes=2 and report=True do not go together")
+        self.reach_t = m.REACH_T if reach_t is None else int(reach_t)
         self.fs, self.baud, self.t_first = float(fs), m.BAUD, t_first
         self.decode, self.keep_llr = bool(decode), bool(keep_llr) or not decode
         self.ldpc = (_ldpc.params() if ldpc is None else ldpc) if decode else None
@@ -534,6 +688,8 @@ class FT8_Skimmer(Skimmer):
             self.h = chan.prototypes
         self.nsub, self.qs = self.S // 2, self.S // 4
         self.dec = self.DECODERS(self.chan, self.S, max_out)
+        if self.passes == 2:
+            self.dec.keep(self.reach_t)
         self.nk, self.nfine, self.fs_out = self.chan.nk, self.dec.nfine, self.chan.fs_out
         self.freqs = self.chan.freqs
         q = 2 * np.arange(self.nsub) - (self.dec.nb - 1)
@@ -541,11 +697,13 @@ class FT8_Skimmer(Skimmer):
         self.circular = self.nk == self.M
         self.records = []
         self._pending, self._recent = [], []
+        self._await, self._ok = [], []                                   # second pass: decoded frames not yet due; every ok record
 
     def reset(self):
         self.dec.reset()
         self.records = []
         self._pending, self._recent = [], []
+        self._await, self._ok = [], []
 
     def _events(self, x):
         """one call: the counts come off the device first, then only the rows that have events"""
@@ -596,7 +754,89 @@ class FT8_Skimmer(Skimmer):
             recs.append(rec)
         if self.report:
             self._measure(recs, dec["bits"])
+        if self.passes == 2:
+            self._hold_for_second(recs, dec["bits"])
         return recs
+
+    def _base_record(self, t0, F, score, hits):
+        m = self.DECODERS.MODE
+        rec = dict(t0=t0, F=F, freq=float(self.freqs_fine[F]), time=self.qs * t0 / self.fs_out, score=score, hits=hits)
+        if self.t_first is not None:
+            T = float(self.t_first) + rec["time"]
+            rec["slot"] = int(np.floor(T / m.SLOT_SECONDS))
+            rec["dt"] = T - m.SLOT_SECONDS * rec["slot"] - m.NOMINAL_START
+        return rec
+
+    def _hold_for_second(self, recs, bits):
+        """pass-1 records gain ``pass``; the decoded ones wait, with their bits and refined place, until they are due"""
+        for r in recs:
+            r["pass"] = 1
+        good = [k for k, r in enumerate(recs) if r["ok"]]
+        if not good:
+            return
+        rep = self.dec.report([recs[k]["F"] for k in good], [recs[k]["t0"] for k in good], bits[good])
+        for i, k in enumerate(good):
+            df, dt, _ = refine(rep["sig9"][i])
+            self._await.append((recs[k], bits[k].copy(), df, dt))
+            self._ok.append(recs[k])
+
+    def _fdist(self, a, b):
+        d = abs(int(a) - int(b))
+        return min(d, self.nfine - d) if self.circular else d
+
+    def _second(self):
+        """The second pass, in absolute steps: a decoded frame is due once step t0 + HOLD + reach_t - 1
+        is complete; due frames go in ascending t0, those of one t0 together: subtract them, rescan the residue around each
+        (F -+ (2 TONES + 2) fine rows inside the raster, t0 -+ reach_t), keep the owners among the new events that are not
+        within (4 steps, 2 fine rows) of a decoded record with t0' <= t0 + reach_t (every such record has been released by
+        then, however the stream was cut), decode them from the residue and keep the messages that are not one of those
+        records' within 8 steps.  -> the new records, ``pass`` 2."""
+        m, R, done = self.DECODERS.MODE, self.reach_t, self.dec.t_done
+        due = [a for a in self._await if a[0]["t0"] + m.HOLD + R <= done]
+        if not due:
+            return []
+        self._await = [a for a in self._await if a[0]["t0"] + m.HOLD + R > done]
+        due.sort(key=lambda a: (a[0]["t0"], a[0]["F"]))
+        out, W = [], 2 * m.TONES + 2
+        for t0 in sorted({a[0]["t0"] for a in due}):
+            grp = [a for a in due if a[0]["t0"] == t0]
+            Fs = [a[0]["F"] for a in grp]
+            trials = np.array([trial_grid(m, a[2], a[3], self.qs, self.fs_out) for a in grp], np.int32)
+            self.dec.subtract(Fs, [t0] * len(grp), np.array([a[1] for a in grp]), trials)
+            found = {}
+            for F in Fs:
+                for e in self.dec.rescan(max(0, F - W), min(self.nfine - 1, F + W), max(0, t0 - R), t0 + R):
+                    found[(e[0], e[1])] = e
+            events = sorted(found.values())
+            own = owners(events, nfine=self.nfine if self.circular else None)
+            known = [r for r in self._ok if r["t0"] <= t0 + R]
+            cand = [e for e, o in zip(events, own)
+                    if o and not any(abs(e[0] - r["t0"]) <= 4 and self._fdist(e[1], r["F"]) <= 2 for r in known)]
+            if not cand:
+                continue
+            cF, ct = [e[1] for e in cand], [e[0] for e in cand]
+            dec = self.dec.decode(cF, ct, self.ldpc, osd=self.osd, residual=True)
+            llr = self.dec.pass_llr(cF, ct) if self.keep_llr else None
+            for k, (et, eF, score, hits) in enumerate(cand):
+                if int(dec["status"][k]) != _ldpc.STATUS_OK:
+                    continue
+                b77 = dec["bits"][k, :77].copy()
+                if any(abs(r["t0"] - et) <= 8 and np.array_equal(r["bits77"], b77) for r in known):
+                    continue
+                rec = self._base_record(et, eF, score, hits)
+                if llr is not None:
+                    rec["llr"] = llr[k]
+                i3, n3 = _msg.types(b77)
+                rec.update(status=_ldpc.STATUS_OK, ok=True, iterations=int(dec["iterations"][k]), nerr=int(dec["nerr"][k]), bits77=b77, i3=i3,
+                           n3=n3, text=m.UNPACK(b77) if m.UNPACK is not None else None)
+                if self.osd is not None:
+                    rec["osd"] = int(dec["osd"][k])
+                rec["pass"] = 2
+                known.append(rec)
+                self._ok.append(rec)
+                out.append(rec)
+            self._ok = [r for r in self._ok if r["t0"] >= t0 - R - 8]      # older ones meet no later group
+        return out
 
     REPORT_KEYS = ("snr", "f_fine", "t_fine", "nhard", "nsync", "sig", "noise")
 
@@ -631,6 +871,8 @@ class FT8_Skimmer(Skimmer):
             n = min(len(x) - i, self.dec.max_samples())
             self._pending += self._events(x[i:i + n])
             out += self._release()
+            if self.passes == 2:
+                out += self._second()
             i += n
         self.records += out
         return out
