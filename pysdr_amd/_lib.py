@@ -79,6 +79,10 @@ class FskCfg(C.Structure):
 
 _vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
+_ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
+_cands = [_p32, _pll, _i]                                               # FT8 / FT4: candidates (F, t0, n) ...
+_decoded = [C.POINTER(LdpcCfg), _p32, _pu8, _pf]                        # ... the decoder's cfg, status, bits and post ...
+_osd = [C.POINTER(OsdCfg), _p32]                                        # ... and the second stage's cfg and detail
 
 # name -> (restype, argtypes); every symbol include/pysdr_hip.h declares
 PROTOTYPES = {
@@ -116,9 +120,9 @@ PROTOTYPES = {
     "pysdr_set_profile": (_i, [_vp, _i]),
     "pysdr_get_elapsed_ms": (_i, [_vp, _i, _i, _pf]),
     "pysdr_set_tile": (_i, [_vp, _i, _i]),
-    "pysdr_get_tuning": (_i, [_vp, C.POINTER(C.c_int32)]),
-    "pysdr_front_end_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
-    "pysdr_front_end_shapes": (_i, [_i, _i, C.POINTER(C.c_int32), _pi]),
+    "pysdr_get_tuning": (_i, [_vp, _p32]),
+    "pysdr_front_end_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p32]),
+    "pysdr_front_end_shapes": (_i, [_i, _i, _p32, _pi]),
     "pysdr_quad_mixer": (_i, [_i, _pf, _pf, _sz, _u32, _u32, C.POINTER(_u32)]),
     "pysdr_freq_word": (_u32, [_d, _d, _pd]),
     "pysdr_fir_real": (_i, [_i, _pf, _pf, _i, _pf, _sz]),
@@ -127,7 +131,7 @@ PROTOTYPES = {
     "pysdr_spectrum_frame": (_i, [_vp, _pf, _i, _i, _pf, _pi]),
     "pysdr_spectrum_batch": (_i, [_vp, _vp, _i, _sz, _vp]),
     "pysdr_spectrum_sync": (_i, [_vp]),
-    "pysdr_spectrum_get_tuning": (_i, [_vp, C.POINTER(C.c_int32)]),
+    "pysdr_spectrum_get_tuning": (_i, [_vp, _p32]),
     "pysdr_spectrum_elapsed_ms": (_i, [_vp, _pf]),
     "pysdr_spectrum_order": (_i, [_vp, _vp, _i]),
     "pysdr_ingest_create": (_i, [_vp, _i, C.POINTER(_vp)]),
@@ -143,22 +147,22 @@ PROTOTYPES = {
     "pysdr_waterfall_roll": (_i, [_vp, _i]),
     "pysdr_waterfall_image": (_i, [_vp, _f, _pf, _pf, _pf]),
     "pysdr_waterfall_image_rows": (_i, [_vp, _f, _i, _pf, _pf, _pf]),
-    "pysdr_waterfall_peaks": (_i, [_vp, _pf, _i, C.c_double, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
+    "pysdr_waterfall_peaks": (_i, [_vp, _pf, _i, C.c_double, _i, _p32, _i, _p32]),
     "pysdr_rtty_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pysdr_rtty_destroy": (None, [_vp]),
     "pysdr_rtty_reset": (_i, [_vp]),
-    "pysdr_rtty_decode": (_i, [_vp, _vp, _i, _i, _i, _pi, C.POINTER(C.c_longlong), _pd, _pi, _pi, _pi, _pf]),
-    "pysdr_chan_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_rtty_decode": (_i, [_vp, _vp, _i, _i, _i, _pi, _pll, _pd, _pi, _pi, _pi, _pf]),
+    "pysdr_chan_plan": (_i, [_i, _i, _i, _i, _i, _p32]),
     "pysdr_chan_create": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pysdr_chan_destroy": (None, [_vp]),
     "pysdr_chan_set_taps": (_i, [_vp, _pd, _i]),
     "pysdr_chan_reset": (_i, [_vp]),
     "pysdr_chan_sync": (_i, [_vp]),
-    "pysdr_chan_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
-    "pysdr_chan_fine_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_chan_process": (_i, [_vp, _vp, _i, _i, _vp, _ll, _i, _pi]),
+    "pysdr_chan_fine_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _p32]),
     "pysdr_chan_fine_create": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_vp)]),
     "pysdr_chan_fine_set_taps": (_i, [_vp, _pd, _i, _pd, _i]),
-    "pysdr_bank_plan": (_i, [_i, _i, _i, C.POINTER(C.c_int32)]),
+    "pysdr_bank_plan": (_i, [_i, _i, _i, _p32]),
     "pysdr_bank_create": (_i, [_vp, _d, _i, _i, C.POINTER(_vp)]),
     "pysdr_bank_destroy": (None, [_vp]),
     "pysdr_bank_set_mode": (_i, [_vp, _i, _pd, _i]),
@@ -166,86 +170,61 @@ PROTOTYPES = {
     "pysdr_bank_set_agc": (_i, [_vp, _i, _f]),
     "pysdr_bank_set_squelch": (_i, [_vp, _f]),
     "pysdr_bank_reset": (_i, [_vp]),
-    "pysdr_bank_process": (_i, [_vp, _vp, _i, _i, _vp, C.c_longlong, _i, _pi]),
-    "pysdr_bank_state": (_i, [_vp, _pf, _pf, _pf, _pf, C.POINTER(C.c_uint8)]),
-    "pysdr_bank_fetch": (_i, [_vp, _pi, _i, _pf, _pf, C.c_longlong]),
+    "pysdr_bank_process": (_i, [_vp, _vp, _i, _i, _vp, _ll, _i, _pi]),
+    "pysdr_bank_state": (_i, [_vp, _pf, _pf, _pf, _pf, _pu8]),
+    "pysdr_bank_fetch": (_i, [_vp, _pi, _i, _pf, _pf, _ll]),
     "pysdr_bank_sync": (_i, [_vp]),
-    "pysdr_cw_plan": (_i, [_i, _i, C.POINTER(CwCfg), C.POINTER(C.c_int32)]),
+    "pysdr_cw_plan": (_i, [_i, _i, C.POINTER(CwCfg), _p32]),
     "pysdr_cw_create": (_i, [_vp, C.POINTER(CwCfg), _i, C.POINTER(_vp)]),
     "pysdr_cw_destroy": (None, [_vp]),
     "pysdr_cw_reset": (_i, [_vp]),
     "pysdr_cw_sync": (_i, [_vp]),
-    "pysdr_cw_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_cw_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_cw_state": (_i, [_vp, _pf, _pf, _pf, C.POINTER(C.c_int32)]),
-    "pysdr_psk_plan": (_i, [_i, _i, _i, C.POINTER(PskCfg), C.POINTER(C.c_int32)]),
+    "pysdr_cw_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
+    "pysdr_cw_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_cw_state": (_i, [_vp, _pf, _pf, _pf, _p32]),
+    "pysdr_psk_plan": (_i, [_i, _i, _i, C.POINTER(PskCfg), _p32]),
     "pysdr_psk_create": (_i, [_vp, _i, C.POINTER(PskCfg), _pf, _pf, _i, C.POINTER(_vp)]),
     "pysdr_psk_destroy": (None, [_vp]),
     "pysdr_psk_reset": (_i, [_vp]),
     "pysdr_psk_sync": (_i, [_vp]),
-    "pysdr_psk_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong, _pf,
-                               C.POINTER(C.c_int32)]),
-    "pysdr_psk_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_psk_state": (_i, [_vp, _pf, _pf, C.POINTER(C.c_int32)]),
-    "pysdr_fsk_plan": (_i, [_i, _i, _i, C.POINTER(FskCfg), C.POINTER(C.c_int32)]),
+    "pysdr_psk_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll, _pf, _p32]),
+    "pysdr_psk_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_psk_state": (_i, [_vp, _pf, _pf, _p32]),
+    "pysdr_fsk_plan": (_i, [_i, _i, _i, C.POINTER(FskCfg), _p32]),
     "pysdr_fsk_create": (_i, [_vp, _i, C.POINTER(FskCfg), _pf, _pf, _i, C.POINTER(_vp)]),
     "pysdr_fsk_destroy": (None, [_vp]),
     "pysdr_fsk_reset": (_i, [_vp]),
     "pysdr_fsk_sync": (_i, [_vp]),
-    "pysdr_fsk_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong, _pf,
-                               C.POINTER(C.c_int32)]),
-    "pysdr_fsk_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_fsk_state": (_i, [_vp, _pf, C.POINTER(C.c_int32)]),
-    "pysdr_ft8_plan": (_i, [_i, _i, _i, C.POINTER(Ft8Cfg), C.POINTER(C.c_int32)]),
-    "pysdr_ft8_create": (_i, [_vp, _i, C.POINTER(Ft8Cfg), _pf, _i, C.POINTER(_vp)]),
-    "pysdr_ft8_destroy": (None, [_vp]),
-    "pysdr_ft8_reset": (_i, [_vp]),
-    "pysdr_ft8_sync": (_i, [_vp]),
-    "pysdr_ft8_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong,
-                               C.POINTER(C.c_longlong)]),
-    "pysdr_ft8_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_ft8_llr": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
-    "pysdr_ft8_state": (_i, [_vp, _pf, C.POINTER(C.c_int32), _pf, C.POINTER(C.c_longlong)]),
-    "pysdr_ft8_decode": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
-                              C.POINTER(C.c_uint8), _pf]),
-    "pysdr_ft8_decode_llr": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf]),
-    "pysdr_ft4_plan": (_i, [_i, _i, _i, C.POINTER(Ft4Cfg), C.POINTER(C.c_int32)]),
-    "pysdr_ft4_create": (_i, [_vp, _i, C.POINTER(Ft4Cfg), _pf, _i, C.POINTER(_vp)]),
-    "pysdr_ft4_destroy": (None, [_vp]),
-    "pysdr_ft4_reset": (_i, [_vp]),
-    "pysdr_ft4_sync": (_i, [_vp]),
-    "pysdr_ft4_process": (_i, [_vp, _vp, _i, _i, _pi, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_longlong,
-                               C.POINTER(C.c_longlong)]),
-    "pysdr_ft4_fetch": (_i, [_vp, _pi, _i, C.POINTER(C.c_int32), C.c_longlong]),
-    "pysdr_ft4_llr": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
-    "pysdr_ft4_state": (_i, [_vp, _pf, C.POINTER(C.c_int32), _pf, C.POINTER(C.c_longlong)]),
-    "pysdr_ft4_decode": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
-                              C.POINTER(C.c_uint8), _pf]),
-    "pysdr_ft4_decode_llr": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf]),
-    "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), C.POINTER(C.c_int32)]),
-    "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
-    "pysdr_ft8_decode_osd": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
-                                  C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
-    "pysdr_ft8_decode_llr_osd": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg),
-                                      C.POINTER(C.c_int32)]),
-    "pysdr_ft4_decode_osd": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32),
-                                  C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
-    "pysdr_ft4_decode_llr_osd": (_i, [_vp, _pf, _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf, C.POINTER(OsdCfg),
-                                      C.POINTER(C.c_int32)]),
-    "pysdr_report_plan": (_i, [_i, C.POINTER(C.c_int32)]),
-    "pysdr_ft8_report": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), _i, _pf, C.POINTER(C.c_int32)]),
-    "pysdr_ft4_report": (_i, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), _i, _pf, C.POINTER(C.c_int32)]),
-    "pysdr_ft8_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
-    "pysdr_ft4_floor": (_i, [_vp, C.c_longlong, _i, _pf]),
-    "pysdr_pass_plan": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
-    **{f"pysdr_{k}_{what}": (_i, [_vp] + args) for k, cfg in (("ft8", Ft8Cfg), ("ft4", Ft4Cfg)) for what, args in (
-        ("keep", [C.POINTER(PassCfg)]),
-        ("subtract", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), _i, C.POINTER(C.c_int32)]),
-        ("rescan", [_i, _i, C.c_longlong, C.c_longlong, C.POINTER(cfg), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-        ("pass_decode", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, C.POINTER(LdpcCfg), C.POINTER(C.c_int32), C.POINTER(C.c_uint8), _pf,
-                         C.POINTER(OsdCfg), C.POINTER(C.c_int32)]),
-        ("pass_llr", [C.POINTER(C.c_int32), C.POINTER(C.c_longlong), _i, _pf]),
-        ("pass_state", [_pf, _pf, C.POINTER(C.c_longlong)]))},
+    "pysdr_fsk_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll, _pf, _p32]),
+    "pysdr_fsk_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_fsk_state": (_i, [_vp, _pf, _p32]),
+    "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
+    "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
+    "pysdr_report_plan": (_i, [_i, _p32]),
+    "pysdr_pass_plan": (_i, [_i, _i, _i, _i, _i, _p32]),
+    # the FT8 and the FT4 skimmer (ft.py): one set of entry points per mode, told apart by the name and the cfg struct
+    **{f"pysdr_{k}_{what}": (res, args) for k, cfg in (("ft8", Ft8Cfg), ("ft4", Ft4Cfg)) for what, res, args in (
+        ("plan", _i, [_i, _i, _i, C.POINTER(cfg), _p32]),
+        ("create", _i, [_vp, _i, C.POINTER(cfg), _pf, _i, C.POINTER(_vp)]),
+        ("destroy", None, [_vp]),
+        ("reset", _i, [_vp]),
+        ("sync", _i, [_vp]),
+        ("process", _i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll, _pll]),
+        ("fetch", _i, [_vp, _pi, _i, _p32, _ll]),
+        ("state", _i, [_vp, _pf, _p32, _pf, _pll]),
+        ("llr", _i, [_vp] + _cands + [_pf]),
+        ("decode", _i, [_vp] + _cands + _decoded),
+        ("decode_osd", _i, [_vp] + _cands + _decoded + _osd),
+        ("decode_llr", _i, [_vp, _pf, _i] + _decoded),
+        ("decode_llr_osd", _i, [_vp, _pf, _i] + _decoded + _osd),
+        ("report", _i, [_vp, _p32, _pll, _pu8, _i, _pf, _p32]),
+        ("floor", _i, [_vp, _ll, _i, _pf]),
+        ("keep", _i, [_vp, C.POINTER(PassCfg)]),
+        ("subtract", _i, [_vp, _p32, _pll, _pu8, _p32, _i, _p32]),
+        ("rescan", _i, [_vp, _i, _i, _ll, _ll, C.POINTER(cfg), _p32, _p32]),
+        ("pass_decode", _i, [_vp] + _cands + _decoded + _osd),
+        ("pass_llr", _i, [_vp] + _cands + [_pf]),
+        ("pass_state", _i, [_vp, _pf, _pf, _pll]))},
     "pysdr_dev_alloc": (_i, [_i, _sz, C.POINTER(_vp)]),
     "pysdr_dev_free": (_i, [_i, _vp]),
     "pysdr_dev_upload": (_i, [_i, _vp, _vp, _sz]),

@@ -4,21 +4,22 @@ arrays.  A channelizer with M / D = 4 delivers rows at ``S`` samples per symbol;
 run on the device, one every 10.4 Hz, so that the fine rows ``F = a NSUB + j`` form one uniform raster over all rows.  The
 device finds every frame by its sync score and hands out its 174 soft bits in transmission order; with ``decode=True`` it
 also runs the LDPC(174,91) decoder and the CRC-14 on them and a record carries ``ok`` and the 77
-bits as decoded; the bit scrambler FT4 applies before the CRC is not here, so ``text`` is None.  The decoder bank and the skimmer are ``ft8.py``'s, told this mode's constants,
-settings, plan and tables; the finder and the soft bits' helpers are ``ft8.py``'s as they are."""
+bits as decoded; the bit scrambler FT4 applies before the CRC is not here, so ``text`` is None.  This file is the mode: its
+constants, settings and waveform.  The decoder bank and the skimmer are ``ft.py``'s, told this module as their ``MODE``;
+``ft8.py`` is the other mode, and neither knows the other."""
 from __future__ import annotations
 
 import sys
 
 import numpy as np
 
+from . import ft as _ft
+from . import ft_report as _report
 from . import psk as _psk
 from ._lib import Ft4Cfg
-from . import ft8 as _ft8
-from .ft8 import FT8_Decoders, FT8_Skimmer, hard_bits, owners, unit_llr, unpack  # noqa: F401  (this mode's too)
-from .ft8 import cfg_dict, steps_done, tables  # noqa: F401  (no mode's number is in them)
-from .ft8 import pack91, pass_lut, pass_plan, pass_pulse, trial_grid  # noqa: F401  (the second pass's host half, DESIGN.md 3 item 27)
-from .ft8 import delta, noise_floor, noise_of, refine, snr_db, spots  # noqa: F401  (the frame report's host half, DESIGN.md 3 item 26)
+from .ft import KEEP, LLR_MAX, cfg_dict, hard_bits, owners, steps_done, tables, unit_llr, unpack  # noqa: F401  (importable from here, as they always were)
+from .ft_report import CAL, FLOOR_QUANTILE, FLOOR_ROWS, delta, noise_floor, noise_of, refine, snr_db, spots  # noqa: F401
+from .ft_pass import pack91, pass_lut, pass_plan, pass_pulse, trial_grid  # noqa: F401
 
 NAME, PLAN_CALL = "FT4", "pysdr_ft4_plan"
 _MODE = sys.modules[__name__]
@@ -31,37 +32,32 @@ FRAME_SECONDS, SLOT_SECONDS, NOMINAL_START = SYMBOLS / BAUD, 7.5, 0.5
 STEPS_PER_SYMBOL = 4
 EMIT_LAG = 412                                   # an event t0 is emitted at step t0 + 412 ...
 HOLD = 417                                       # ... and released once step t0 + 416 is complete: every rival has arrived
-KEEP = 9
 SHAPES = (48, 72)                                # row samples per symbol
 NB_EXTRA = 6                                     # NB = NSUB + 6: decoder j uses bins j + 2 tone, tone 0 to 3
-LLR_MAX = 4096
 UNPACK = None                                    # FT4 XORs its 77 bits with a fixed scrambler before the CRC; that vector is not here
 REPORT_MODE = 1                                  # PYSDR_REPORT_FT4
 TONES = 4
-FLOOR_QUANTILE = 0.02                            # a row's floor: this quantile of its NB bin means, all but the least of them
-FLOOR_ROWS = (4, 8)                              # a candidate's noise: the median floor of the rows this far away: behind the prototype's stop band
 PULSE_SYMBOLS = 5                                # symbols the frequency pulse of ``waveform`` spans (BT = 1)
 PULSE_K = np.pi * np.sqrt(2 / np.log(2))
 REACH_T = 40                                     # steps a rescan looks to either side of a subtracted frame
-TRIAL_DN = 0.25                                  # steps between the trial times (``ft8.py``)
-TRIAL_DF = 1.0                                   # Hz between the trial frequencies: ``ft8.py``'s 0.3 Hz scaled by the baud
-CAL = -0.7                                       # dB: the bias of so low a quantile, measured (tests/test_report_oracle.py)
+TRIAL_DN = 0.25                                  # steps between the trial times
+TRIAL_DF = 1.0                                   # Hz between the trial frequencies: FT8's 0.3 Hz scaled by the baud
 
 
 def report_plan():
-    """``ft8.report_plan`` for this mode: 103 symbols"""
-    return _ft8.report_plan(REPORT_MODE)
+    """``ft_report.report_plan`` for this mode: 103 symbols"""
+    return _report.report_plan(REPORT_MODE)
 
 
 def spot_line(rec, f_centre=0.0):
-    """``ft8.spot_line`` on this mode's 7.5 s slots"""
-    return _ft8.spot_line(rec, f_centre, SLOT_SECONDS)
+    """``ft_report.spot_line`` on this mode's 7.5 s slots"""
+    return _report.spot_line(rec, f_centre, SLOT_SECONDS)
 
 
 def shape(fs):
     """-> (S, D, M): S = 48 row samples per symbol if fs / (48 baud) is an integer D and the channelizer accepts M = 4 D,
-    otherwise S = 72 likewise, otherwise ValueError (``ft8.shape``'s rules)."""
-    return _ft8.mode_shape(_MODE, fs)
+    otherwise S = 72 likewise, otherwise ValueError."""
+    return _ft.mode_shape(_MODE, fs)
 
 
 def prototype(fs, M, S):
@@ -74,7 +70,7 @@ def fine_channelizer(fs, band, device=0, max_in=1 << 22):
     """A ``fine.FineChannelizer`` for ``FT4_Skimmer(fs, chan=...)`` at a rate ``shape`` refuses: rows S baud / 4 apart whose
     centres lie in ``band = (f_lo, f_hi)`` Hz from the centre, S = 48 where ``fine.shape`` finds a shape, else 72; M2 / D2 =
     4, the second prototype is ``prototype`` at the first stage's output rate, the first ``fine.prototype1``."""
-    return _ft8.mode_fine_channelizer(_MODE, fs, band, device, max_in)
+    return _ft.mode_fine_channelizer(_MODE, fs, band, device, max_in)
 
 
 def params(smin=4.0, hmin=12, pmax=1e18):
@@ -86,7 +82,7 @@ def plan(nk, S, max_out, cfg):
     """What a skimmer of this shape launches (no device needed): dict of rows per workgroup, threads, LDS bytes, tile
     samples, event cap per decoder and call, workgroups, decoders per row, ring depth in steps.  Raises PysdrError
     outside the rules."""
-    return _ft8.mode_plan(_MODE, nk, S, max_out, cfg)
+    return _ft.mode_plan(_MODE, nk, S, max_out, cfg)
 
 
 def tones(bits):
@@ -130,18 +126,15 @@ def waveform(tones, f0, fs, gfsk=True, ramps=True, phase=0.0):
     return w
 
 
-class FT4_Decoders(FT8_Decoders):
-    """The decoder bank on a borrowed ``Channelizer``: ``FT8_Decoders``' calls on ``pysdr_ft4_*`` with this module's
+class FT4_Decoders(_ft.FT_Decoders):
+    """The decoder bank on a borrowed ``Channelizer``: ``ft.FT_Decoders``' calls on ``pysdr_ft4_*`` with this module's
     constants (an event's t0 is ``t_first + unpack(words)[0] - 412``)."""
     KIND, DESTROY = "ft4", "pysdr_ft4_destroy"
-    MODE = sys.modules[__name__]
+    MODE = _MODE
 
 
-class FT4_Skimmer(FT8_Skimmer):
-    """Wideband IQ at ``fs`` -> a channelizer of M = 4 D rows S baud / 4 apart at S baud = 1000 or 1500 samples per second ->
-    NSUB = S / 2 sync decoders inside every row, fine row F with tone 0 at ``freqs_fine[F]`` Hz (signed) -> a record for
-    every frame found, ``FT8_Skimmer``'s: ``t0`` (steps of a quarter symbol since create / reset; the first Costas symbol,
-    one symbol behind the start of the transmission's ramp), ``F``, ``freq``, ``time``, ``score``, ``hits`` and ``llr``
-    float32 [174]; with ``t_first`` (UTC seconds of sample 0) also ``slot`` (7.5 s) and ``dt`` (against 0.5 s).  The hold,
-    the finder and the release are ``FT8_Skimmer``'s code."""
+class FT4_Skimmer(_ft.FT_Skimmer):
+    """``ft.FT_Skimmer`` (which describes the records) on this mode: 103 symbols of 4 tones at 125 / 6 baud, rows at S baud =
+    1000 or 1500 samples per second; ``t0`` is the first Costas symbol, one symbol behind the start of the transmission's
+    ramp; 7.5 s slots, ``dt`` against 0.5 s; ``text`` is None."""
     DECODERS = FT4_Decoders

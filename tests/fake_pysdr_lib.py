@@ -4,6 +4,8 @@ library, which needs no device for them.  The handle-taking calls of the channel
 answered from a tiny model: ``create`` hands out a token, a NULL or dead handle returns -1 as the C code does, ``process``
 computes ``n_out`` from the model's own count of input samples and the D it was created with, and everything a call writes
 (samples, counts, event words, qn, open, state) comes from a generator seeded by the call number, counts never above the cap.
+The ``pysdr_ft8_*`` and ``pysdr_ft4_*`` handle calls (tests/test_ft_py_trace.py) have a model of their own further down: steps
+by the quarter-symbol rule, two-word events, the refusals of the C code by call size, by ``keep`` and by the ring.
 
 Every call is recorded in ``trace`` as one string: the name, every scalar argument, ``crc/bytes`` of what the function's
 contract says it reads behind each input pointer (of the bytes; of ``quant`` of the values for taps and tables), and
@@ -377,6 +379,255 @@ class FakeLib:
         _put(f, rng.random((4, d.nrows), np.float32))
         _put(ints, rng.integers(0, 1000, (5, d.nrows)).astype(np.int32))
         return 0
+
+
+    # ---- FT8 / FT4 decoder banks (tests/test_ft_py_trace.py): the numbers of include/pysdr_hip.h, written out here
+    FT = {"ft8": dict(lag=316, hold=321, nb_extra=14, pulse=3, sync=21), "ft4": dict(lag=412, hold=417, nb_extra=6, pulse=5, sync=16)}
+    FT_MAX, FT_FRAMES, FT_ROWS, FT_WINDOW, FT_EVENTS = 4096, 256, 256, 256, 52
+
+    @staticmethod
+    def _ft_steps(n_out, S):
+        """steps complete once a row has n_out outputs: step t needs outputs QS t .. QS t + S - 1, QS = S / 4"""
+        return (n_out - S) // (S // 4) + 1 if n_out >= S else 0
+
+    @staticmethod
+    def _ft_done(d):
+        return FakeLib._ft_steps(-(-d.chan.n_in // d.chan.D), d.S)
+
+    @staticmethod
+    def _ft_words(rng, u, sync):
+        """events at the ascending step indices ``u`` -> [len(u)][2]: (u << 5) | hits, the bits of a positive float32 score"""
+        hits = rng.integers(sync // 2, sync + 1, len(u))
+        score = (3.0 + 9.0 * rng.random(len(u))).astype(np.float32)
+        return np.stack(((np.asarray(u, np.int64) << 5) | hits, score.view(np.int32).astype(np.int64)), axis=1).astype(np.int32)
+
+    def _ft_cands(self, d, F, t0, n, ring2=False):
+        """-> the candidates' CRCs for the trace, and whether the call stands: n in [0, 4096], every F on the raster and (first
+        ring) every frame whole, not before step 0 and still in the ring"""
+        text = (_in(F, 4 * max(n, 0)), _in(t0, 8 * max(n, 0)), n)
+        if d is None or not 0 <= n <= self.FT_MAX or (ring2 and not d.kept):
+            return text, False
+        f = np.frombuffer(C.string_at(_addr(F), 4 * n), np.int32) if n else np.zeros(0, np.int32)
+        t = np.frombuffer(C.string_at(_addr(t0), 8 * n), np.int64) if n else np.zeros(0, np.int64)
+        ok = not (len(f) and (f.min() < 0 or f.max() >= d.nfine))
+        if ok and not ring2 and len(t):
+            done = self._ft_done(d)
+            ok = bool((t >= 0).all() and (t + d.lag - 4 < done).all() and (done - t <= d.tr).all())
+        return text, ok
+
+    def _ft_create(self, kind, hc, S, cfg, tw, max_out, ph):
+        self._rec(f"pysdr_{kind}_create", self._h(hc), S, _in(cfg, 12), _in(tw, 4 * S * 2 * 4, np.float32), max_out, _out(ph))
+        ch = self._get(hc, "chan")
+        if ch is None:
+            return -1
+        ch.n_in = 0
+        k, qs = self.FT[kind], S // 4
+        cap = (max_out // qs + 1) // 5 + 1
+        return self._new(ph, _Obj(kind, chan=ch, S=S, qs=qs, nsub=S // 2, nb=S // 2 + k["nb_extra"], nfine=ch.nk * (S // 2), max_out=max_out,
+                                  cap=cap, lag=k["lag"], hold=k["hold"], sync=k["sync"], pulse=k["pulse"], tr=k["hold"] + 2 * (max_out // qs + 1),
+                                  slots=np.zeros((ch.nk * (S // 2), 2 * cap), np.int32), kept=False, trials=0, tr2=0, ty=0))
+
+    def _ft_destroy(self, kind, h):
+        self._destroy(f"pysdr_{kind}_destroy", h, kind)
+
+    def _ft_reset(self, kind, h):
+        return self._dec_simple(f"pysdr_{kind}_reset", kind, h, True)
+
+    def _ft_sync(self, kind, h):
+        return self._dec_simple(f"pysdr_{kind}_sync", kind, h, False)
+
+    def _ft_process(self, kind, h, x, n, on_dev, pn, counts, ev, pitch, steps):
+        rng = self._rec(f"pysdr_{kind}_process", self._h(h), _addr(x) if on_dev else _in(x, 8 * n), n, on_dev, _out(pn), _out(counts),
+                        _out(ev), pitch, _out(steps))
+        d = self._get(h, kind)
+        if d is None or pitch < 2 * d.cap:
+            return -1
+        t_first = self._ft_done(d)
+        n_out = self._advance(d.chan, n)
+        assert n_out <= d.max_out, (n_out, d.max_out)
+        ns = self._ft_done(d) - t_first
+        first = max(0, d.lag - t_first)                                 # only events with t_first + u - lag >= 0, as the device does
+        most = min(d.cap, max(ns - first, 0))
+        cnt = rng.integers(0, most + 1, d.nfine) * (rng.random(d.nfine) < 1.0 / d.nfine)
+        d.slots = np.zeros((d.nfine, 2 * d.cap), np.int32)
+        for r in np.flatnonzero(cnt):
+            u = np.sort(rng.choice(np.arange(first, ns), cnt[r], replace=False))
+            d.slots[r, :2 * cnt[r]] = self._ft_words(rng, u, d.sync).reshape(-1)
+        _set(pn, n_out)
+        _put(counts, cnt.astype(np.int32))
+        _put_rows(ev, d.slots, pitch)
+        _put(steps, np.array([t_first, ns], np.int64))
+        return 0
+
+    def _ft_fetch(self, kind, h, rows, nrows, ev, pitch):
+        self._rec(f"pysdr_{kind}_fetch", self._h(h), _in(rows, 4 * nrows), nrows, _out(ev), pitch)
+        d = self._get(h, kind)
+        if d is None or pitch < 2 * d.cap:
+            return -1
+        r = np.frombuffer(C.string_at(_addr(rows), 4 * nrows), np.int32) if nrows else np.zeros(0, np.int32)
+        if len(r) and (r.min() < 0 or r.max() >= d.nfine):
+            return -1
+        _put_rows(ev, d.slots[r], pitch)
+        return 0
+
+    def _ft_state(self, kind, h, sc, hits, ring, done):
+        rng = self._rec(f"pysdr_{kind}_state", self._h(h), _out(sc), _out(hits), _out(ring), _out(done))
+        d = self._get(h, kind)
+        if d is None:
+            return -1
+        _put(sc, rng.random((9, d.nfine), np.float32))
+        _put(hits, rng.integers(0, d.sync + 1, (9, d.nfine)).astype(np.int32))
+        _put(ring, rng.random((d.chan.nk, d.tr, d.nb), np.float32))
+        _set(done, self._ft_done(d))
+        return 0
+
+    def _ft_llr(self, kind, h, F, t0, n, out, what="llr"):
+        d = self._get(h, kind)
+        text, ok = self._ft_cands(d, F, t0, n, what == "pass_llr")
+        rng = self._rec(f"pysdr_{kind}_{what}", self._h(h), *text, _out(out))
+        if not ok:
+            return -1
+        _put(out, rng.standard_normal((n, 174)).astype(np.float32))
+        return 0
+
+    def _ft_pass_llr(self, kind, h, F, t0, n, out):
+        return self._ft_llr(kind, h, F, t0, n, out, "pass_llr")
+
+    def _ft_answer(self, rng, n, st, bits, post, osd, detail):
+        """what the four decode calls and pass_decode write: status 2 in about half the rows, 0 and 1 in a quarter each; the
+        second stage, where asked for, runs on the rows without a message and decodes half of them"""
+        s = np.zeros((n, 4), np.int32)
+        s[:, 0] = rng.choice([0, 1, 2, 2], n)
+        s[:, 1] = rng.integers(0, 30, n)
+        s[:, 2] = rng.integers(0, 40, n)
+        b = rng.integers(0, 256, (n, 12)).astype(np.uint8)
+        b[:, 11] &= 0xE0                                                 # 91 bits, MSB first: the last 5 are padding
+        det = np.tile(np.array([-1, -1, -1, 0], np.int32), (n, 1))
+        if osd:
+            ran = s[:, 0] != 2
+            s[ran, 3] = rng.integers(1, 4, int(ran.sum()))
+            s[ran & (rng.random(n) < 0.5), 0] = 2
+            det[ran] = rng.integers(0, 4187, (int(ran.sum()), 4))
+        _put(st, s)
+        _put(bits, b)
+        _put(post, rng.standard_normal((n, 174)).astype(np.float32))
+        _put(detail, det)
+
+    def _ft_decode(self, kind, h, F, t0, n, cfg, st, bits, post, osd=None, detail=None, what="decode"):
+        d = self._get(h, kind)
+        text, ok = self._ft_cands(d, F, t0, n, what == "pass_decode")
+        more = () if what == "decode" else (_in(osd, 4), _out(detail))
+        rng = self._rec(f"pysdr_{kind}_{what}", self._h(h), *text, _in(cfg, 8), _out(st), _out(bits), _out(post), *more)
+        if not ok or not _addr(cfg) or not _addr(st) or not _addr(bits) or (what == "decode_osd" and not _addr(osd)) or (_addr(detail) and not _addr(osd)):
+            return -1
+        self._ft_answer(rng, n, st, bits, post, _addr(osd), detail)
+        return 0
+
+    def _ft_decode_osd(self, kind, h, F, t0, n, cfg, st, bits, post, osd, detail):
+        return self._ft_decode(kind, h, F, t0, n, cfg, st, bits, post, osd, detail, "decode_osd")
+
+    def _ft_pass_decode(self, kind, h, F, t0, n, cfg, st, bits, post, osd, detail):
+        return self._ft_decode(kind, h, F, t0, n, cfg, st, bits, post, osd, detail, "pass_decode")
+
+    def _ft_decode_llr(self, kind, h, llr, n, cfg, st, bits, post, osd=None, detail=None, what="decode_llr"):
+        more = () if what == "decode_llr" else (_in(osd, 4), _out(detail))
+        rng = self._rec(f"pysdr_{kind}_{what}", self._h(h), _in(llr, 174 * 4 * max(n, 0)), n, _in(cfg, 8), _out(st), _out(bits), _out(post), *more)
+        if self._get(h, kind) is None or not 0 <= n <= self.FT_MAX or (what != "decode_llr" and not _addr(osd)):
+            return -1
+        if n and not np.isfinite(np.frombuffer(C.string_at(_addr(llr), 174 * 4 * n), np.float32)).all():
+            return -1
+        self._ft_answer(rng, n, st, bits, post, _addr(osd), detail)
+        return 0
+
+    def _ft_decode_llr_osd(self, kind, h, llr, n, cfg, st, bits, post, osd, detail):
+        return self._ft_decode_llr(kind, h, llr, n, cfg, st, bits, post, osd, detail, "decode_llr_osd")
+
+    def _ft_report(self, kind, h, F, t0, bits, n, power, errs):
+        d = self._get(h, kind)
+        text, ok = self._ft_cands(d, F, t0, n)
+        rng = self._rec(f"pysdr_{kind}_report", self._h(h), text[0], text[1], _in(bits, 12 * max(n, 0)), n, _out(power), _out(errs))
+        if not ok:
+            return -1
+        _put(power, (0.5 + rng.random((n, 10))).astype(np.float32) * np.float32(100.0))
+        _put(errs, rng.integers(0, 8, (n, 2)).astype(np.int32))
+        return 0
+
+    def _ft_floor(self, kind, h, t_end, nsym, out):
+        t_end = t_end.value if hasattr(t_end, "value") else t_end
+        rng = self._rec(f"pysdr_{kind}_floor", self._h(h), t_end, nsym, _out(out))
+        d = self._get(h, kind)
+        if d is None or not 1 <= nsym <= 128:
+            return -1
+        done, t_lo = self._ft_done(d), t_end - 4 * (nsym - 1)
+        if t_end >= done or t_lo < 0 or done - t_lo > d.tr:
+            return -1
+        _put(out, (0.5 + rng.random((d.chan.nk, d.nb))).astype(np.float32))
+        return 0
+
+    def _ft_keep(self, kind, h, cfg):
+        c = cfg._obj if _addr(cfg) else None
+        d = self._get(h, kind)
+        size = d.pulse * d.S if d is not None else 0
+        self._rec(f"pysdr_{kind}_keep", self._h(h), "NULL" if c is None else
+                  f"reach_t={c.reach_t} trials={c.trials} pulse={crc((np.frombuffer(C.string_at(_addr(c.pulse), 4 * size), np.uint32) >> 8).tobytes())}/{4 * size} "
+                  f"lut={_in(c.lut, 4096 * 2 * 4, np.float32)}")
+        if d is None or c is None or d.chan.n_in > 0 or not 1 <= c.reach_t <= 120 or not 1 <= c.trials <= 9:
+            return -1
+        d.kept, d.trials = True, c.trials
+        d.tr2 = d.hold + 2 * c.reach_t + 4 + d.max_out // d.qs + 1
+        d.ty = -(-(d.qs * d.tr2 + d.S) // 16) * 16
+        return 0
+
+    def _ft_subtract(self, kind, h, F, t0, bits, trials, n, out):
+        d = self._get(h, kind)
+        nt = d.trials if d is not None else 0
+        rng = self._rec(f"pysdr_{kind}_subtract", self._h(h), _in(F, 4 * max(n, 0)), _in(t0, 8 * max(n, 0)), _in(bits, 12 * max(n, 0)),
+                        _in(trials, 8 * nt * max(n, 0)), n, _out(out))
+        if d is None or not d.kept or not 0 <= n <= self.FT_FRAMES:
+            return -1
+        o = np.zeros((n, 2, 4), np.int32)
+        o[:, :, :2] = (1.0 + rng.random((n, 2, 2))).astype(np.float32).view(np.int32)
+        o[:, :, 2] = rng.integers(0, d.trials, (n, 2))
+        o[:, :, 3] = rng.integers(1, 80, (n, 2))
+        _put(out, o)
+        return 0
+
+    def _ft_rescan(self, kind, h, F_lo, F_hi, t_lo, t_hi, cfg, counts, ev):
+        t_lo, t_hi = (t.value if hasattr(t, "value") else t for t in (t_lo, t_hi))
+        rng = self._rec(f"pysdr_{kind}_rescan", self._h(h), F_lo, F_hi, t_lo, t_hi, _in(cfg, 12), _out(counts), _out(ev))
+        d = self._get(h, kind)
+        nF, nT = F_hi - F_lo + 1, t_hi - t_lo + 1
+        if d is None or not d.kept or not 1 <= nF <= self.FT_ROWS or not 1 <= nT + 8 <= self.FT_WINDOW or F_lo < 0 or F_hi >= d.nfine or t_lo < 0:
+            return -1
+        cnt = rng.integers(1, min(3, nT, self.FT_EVENTS) + 1, nF) * (rng.random(nF) < 0.2)     # a few events in a few rows
+        words = np.zeros((nF, self.FT_EVENTS, 2), np.int32)
+        for r in np.flatnonzero(cnt):
+            words[r, :cnt[r]] = self._ft_words(rng, np.sort(rng.choice(nT, cnt[r], replace=False)), d.sync)
+        _put(counts, cnt.astype(np.int32))
+        _put(ev, words)
+        return 0
+
+    def _ft_pass_state(self, kind, h, yk, ring2, info):
+        rng = self._rec(f"pysdr_{kind}_pass_state", self._h(h), _out(yk), _out(ring2), _out(info))
+        d = self._get(h, kind)
+        if d is None or not d.kept:
+            return -1
+        _put(yk, self._samples(rng, d.chan.nk, d.ty))
+        _put(ring2, rng.random((d.chan.nk, d.tr2, d.nb), np.float32))
+        _put(info, np.array([-(-d.chan.n_in // d.chan.D), d.ty, d.tr2], np.int64))
+        return 0
+
+
+def _for_kind(fn, kind):
+    def call(self, *a):
+        return fn(self, kind, *a)
+    return call
+
+
+for _name, _fn in list(vars(FakeLib).items()):
+    if _name.startswith("_ft_") and _name not in ("_ft_steps", "_ft_done", "_ft_words", "_ft_cands", "_ft_answer"):
+        for _kind in FakeLib.FT:
+            setattr(FakeLib, f"pysdr_{_kind}_{_name[4:]}", _for_kind(_fn, _kind))
 
 
 def _noting_failure(fn):
