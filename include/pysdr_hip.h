@@ -222,6 +222,17 @@ int pysdr_front_end_plan(int nrx, int up, int down, int ntaps, int tile_bytes, i
  * DOWN, taps per polyphase branch}.  *count (if not null) = entries of the family; index outside 0 .. count-1 with a
  * null `out` only counts. */
 int pysdr_front_end_shapes(int family, int index, int32_t out[4], int* count);
+/* Which of its three kernels the PYSDR_FORM_SMALL resampler (broadcast FM's fs1 -> FS_OUT stage) runs for a decimator
+ * UP/DOWN with an ntaps-tap prototype, and with what launch.  Pure arithmetic like pysdr_front_end_plan, and the helper
+ * the launch itself takes its decision from.  plain = PYSDR_RESAMP_PLAIN as pysdr_get_resamp_tuning reports it (0: the
+ * production choice, 1: one output per thread, 2: no wave-per-branch form).
+ * out = {eligible for PYSDR_FORM_SMALL 0/1, kernel (0 a wave per polyphase branch, 1 one output per thread, 2 a half-wave
+ *        per branch; -1 if not eligible), threads per workgroup, dynamic LDS bytes, outputs per tile,
+ *        kpad (taps per polyphase branch, padded to 16), hist_len (input samples kept between calls), input samples of
+ *        one tile's LDS span}. */
+int pysdr_resamp_plan(int up, int down, int ntaps, int plain, int32_t out[8]);
+/* out = {PYSDR_RESAMP_PLAIN, PYSDR_MIXDEC_GRID (0: not held)} as the context read them at create (under PYSDR_TUNING=1) */
+int pysdr_get_resamp_tuning(pysdr_ctx* ctx, int32_t out[2]);
 
 /* ---- signal_generator.quad_mixer (receiver.py:552-553,822) --------------------
  * y = x * exp(+j*phi_n), 32-bit phase accumulator, returns phase after n samples */

@@ -123,6 +123,8 @@ PROTOTYPES = {
     "pysdr_get_tuning": (_i, [_vp, _p32]),
     "pysdr_front_end_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p32]),
     "pysdr_front_end_shapes": (_i, [_i, _i, _p32, _pi]),
+    "pysdr_resamp_plan": (_i, [_i, _i, _i, _i, _p32]),
+    "pysdr_get_resamp_tuning": (_i, [_vp, _p32]),
     "pysdr_quad_mixer": (_i, [_i, _pf, _pf, _sz, _u32, _u32, C.POINTER(_u32)]),
     "pysdr_freq_word": (_u32, [_d, _d, _pd]),
     "pysdr_fir_real": (_i, [_i, _pf, _pf, _i, _pf, _sz]),

@@ -313,7 +313,7 @@ int decim_init(Decim& d, int up, int down, int ntaps, int max_rx, hipStream_t st
   d.up = up; d.down = down; d.ntaps = ntaps; d.max_rx = max_rx;
   d.kdec = (ntaps + up - 1) / up;
   d.kpad = (d.kdec + 15) / 16 * 16;
-  d.hist_len = d.kpad + 2;
+  d.hist_len = decim_hist_len(d.kpad);
   d.h_taps.assign((size_t)max_rx * d.per(), make_float2(0.f, 0.f));
   PYSDR_HIP_CHECK(d.d_hist.alloc_both_zeroed((size_t)d.hist_len, st));
   PYSDR_HIP_CHECK(d.d_taps.alloc_zeroed((size_t)max_rx * d.per(), st));      // (the last one: a decimator with taps is complete)
@@ -1098,6 +1098,23 @@ int pysdr_front_end_shapes(int family, int index, int32_t out[4], int* count) {
   if (index < 0 || index >= n) return (out == nullptr && count != nullptr) ? PYSDR_OK : PYSDR_ERR_ARG;
   if (!out) return PYSDR_ERR_ARG;
   for (int j = 0; j < 4; ++j) out[j] = tab[index][j];
+  return PYSDR_OK;
+}
+
+int pysdr_resamp_plan(int up, int down, int ntaps, int plain, int32_t out[8]) {
+  if (!out || up < 1 || down < 1 || ntaps < 1 || plain < 0 || plain > 2) return PYSDR_ERR_ARG;
+  // the shape as decim_init derives it, the decision as launch_resamp_small takes it
+  const int kdec = (ntaps + up - 1) / up;
+  const int kpad = (kdec + 15) / 16 * 16;
+  const ResampPlan p = plan_resamp_small(up, down, kpad, plain);
+  out[0] = p.eligible ? 1 : 0; out[1] = p.kernel; out[2] = p.threads; out[3] = (int32_t)p.lds; out[4] = p.tile_out;
+  out[5] = kpad; out[6] = decim_hist_len(kpad); out[7] = p.span;
+  return PYSDR_OK;
+}
+
+int pysdr_get_resamp_tuning(pysdr_ctx* c, int32_t out[2]) {
+  if (!c || !out) return PYSDR_ERR_ARG;
+  out[0] = c->tune.resamp_plain; out[1] = c->tune.grid_override;
   return PYSDR_OK;
 }
 

@@ -82,6 +82,7 @@ struct MixDecArgs {
                           // registers for the whole launch and reads them from memory once (plan_mixdec: the host guarantees hold mode)
 };
 // the plan and the launch of the mix + decimate kernel: mixdec_plan.h
+inline int decim_hist_len(int kpad) { return kpad + 2; }   // raw-sample history a decimator keeps between calls (MixDecArgs::hist_len)
 
 // one RX, short prototype, small DOWN/UP, no raw peak (resamp_small.hip): the fs1 -> FS_OUT stage of broadcast FM
 constexpr int kRsThreads = 256;                      // threads = outputs per workgroup of its one-output-per-thread form
@@ -92,6 +93,57 @@ inline int resamp_small_span(int up, int down, int kpad) {
   const long bytes = (span + (long)up * (kpad + 1)) * (long)sizeof(float2);
   if (span > 4096 || bytes > 60 * 1024) return 0;
   return (int)span;
+}
+constexpr int kRbL = 32;                             // half-wave-per-branch form: outputs per branch and tile = lanes per half-wave
+constexpr int kRbPre = 6;                            //   pieces of the next tile's span a thread holds in registers
+// LDS of the wave-per-branch form: input span of UP x 64 outputs + the outputs; 0 = not eligible
+inline size_t resamp_wave_lds(int up, int down, int kpad, int* span_out) {
+  if (up > 32 || up < 2) return 0;
+  const long span = 64L * down + kpad + 4;
+  const size_t bytes = ((size_t)span + (size_t)up * 64) * sizeof(float2);
+  if (bytes > 78 * 1024) return 0;                   // two workgroups per CU
+  *span_out = (int)span;
+  return bytes;
+}
+// LDS of the half-wave-per-branch form: input span of UP x 32 outputs + the outputs + the tap table; 0 = not eligible
+inline size_t resamp_branch_lds(int up, int down, int kpad, int* span_out) {
+  if (up > 32 || up < 2) return 0;
+  const long span = (long)kRbL * down + kpad + 4;
+  const size_t bytes = ((size_t)span + (size_t)up * kRbL + (size_t)up * (kpad + 1)) * sizeof(float2);
+  if (bytes > 64 * 1024 || span > (long)kRbPre * up * kRbL) return 0;
+  *span_out = (int)span;
+  return bytes;
+}
+// Which of the resampler's three kernels a decimator of this shape runs, and with what launch.  A function of the shape and of
+// the context's `plain` switch (Tuning::resamp_plain) only -- never of the call: every call of a stream takes the same path, and
+// all three sum every output in the same order anyway.  launch_resamp_small launches what this says and pysdr_resamp_plan
+// reports it: one helper, so the two cannot drift.
+constexpr int kRsKernelWave = 0, kRsKernelThread = 1, kRsKernelHalfWave = 2;
+struct ResampPlan {
+  bool eligible;   // the shape fits PYSDR_FORM_SMALL at all (resamp_small_span > 0)
+  int kernel;      // kRsKernelWave: resamp_wave_kernel, kRsKernelThread: resamp_small_kernel, kRsKernelHalfWave: resamp_branch_kernel
+  int threads;     // per workgroup
+  size_t lds;      // dynamic LDS bytes
+  int tile_out;    // outputs per tile (per group of the one-output-per-thread kernel)
+  int span;        // input samples the LDS holds per tile
+};
+inline ResampPlan plan_resamp_small(int up, int down, int kpad, int plain) {
+  ResampPlan p{false, -1, 0, 0, 0, 0};
+  const int span = resamp_small_span(up, down, kpad);
+  if (span <= 0) return p;
+  p.eligible = true;
+  int wspan = 0, bspan = 0;
+  const size_t wlds = resamp_wave_lds(up, down, kpad, &wspan);
+  const size_t blds = resamp_branch_lds(up, down, kpad, &bspan);
+  if (wlds > 0 && plain == 0) {                      // a wave per branch, two branches per wave
+    p.kernel = kRsKernelWave; p.threads = 64 * ((up + 1) / 2); p.lds = wlds; p.tile_out = up * 64; p.span = wspan;
+  } else if (blds > 0 && plain != 1) {               // a half-wave per branch whenever its tile fits
+    p.kernel = kRsKernelHalfWave; p.threads = up * kRbL; p.lds = blds; p.tile_out = up * kRbL; p.span = bspan;
+  } else {                                           // one output per thread
+    p.kernel = kRsKernelThread; p.threads = kRsThreads; p.lds = ((size_t)span + (size_t)up * (kpad + 1)) * sizeof(float2);
+    p.tile_out = kRsThreads; p.span = span;
+  }
+  return p;
 }
 int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st);   // grid_cap > 0: at most that many workgroups (tests); plain: 0 = wave per branch with scalar taps, 1 = one output per thread, 2 = half-wave per branch (A/B)
 

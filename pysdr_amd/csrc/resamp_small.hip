@@ -93,8 +93,7 @@ __global__ __launch_bounds__(kRsThreads) void resamp_small_kernel(const MixDecAr
 // DOWN apart -- an odd DOWN puts them on 32 different bank pairs -- so a tap costs ~8 LDS cycles and the FMAs bound the
 // kernel.  The outputs go through LDS once more to leave as contiguous 8-byte-per-lane stores (lane l's own outputs are UP
 // outputs apart).  Same arithmetic per output as resamp_small_kernel, in the same order: bit for bit its results.
-constexpr int kRbL = 32;                           // outputs per branch and tile = lanes per half-wave
-constexpr int kRbPre = 6;                          // pieces of the next tile's span a thread holds in registers
+// (kRbL = 32 outputs per branch and tile, kRbPre = 6 register pieces of the next tile's span: common.h)
 
 // (six waves per SIMD = two workgroups of 24 x 32 threads per CU: 84 registers)
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(6))) void resamp_branch_kernel(const MixDecArgs a, int span_cap, int ntiles) {
@@ -258,40 +257,21 @@ __global__ __launch_bounds__(1024) void resamp_wave_kernel(const MixDecArgs a, i
 
 }  // namespace
 
-// LDS of the wave-per-branch form: input span of UP x 64 outputs + the outputs; 0 = not eligible
-static size_t resamp_wave_lds(int up, int down, int kpad, int* span_out) {
-  if (up > 32 || up < 2) return 0;
-  const long span = 64L * down + kpad + 4;
-  const size_t bytes = ((size_t)span + (size_t)up * 64) * sizeof(float2);
-  if (bytes > 78 * 1024) return 0;                 // two workgroups per CU
-  *span_out = (int)span;
-  return bytes;
-}
-
-// LDS of the branch-major form: input span of UP x 32 outputs + the outputs + the tap table; 0 = not eligible
-static size_t resamp_branch_lds(int up, int down, int kpad, int* span_out) {
-  if (up > 32 || up < 2) return 0;
-  const long span = (long)kRbL * down + kpad + 4;
-  const size_t bytes = ((size_t)span + (size_t)up * kRbL + (size_t)up * (kpad + 1)) * sizeof(float2);
-  if (bytes > 64 * 1024 || span > (long)kRbPre * up * kRbL) return 0;
-  *span_out = (int)span;
-  return bytes;
-}
-
+// (resamp_wave_lds, resamp_branch_lds and the choice among the three kernels, plan_resamp_small: common.h)
 int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_t st) {
-  const int span = resamp_small_span(a.up, a.down, a.kpad);
-  if (span <= 0 || a.nrx != 1) {
+  const ResampPlan p = plan_resamp_small(a.up, a.down, a.kpad, plain);
+  if (!p.eligible || a.nrx != 1) {
     set_last_error("resamp_small: up %d down %d kpad %d nrx %d not eligible", a.up, a.down, a.kpad, a.nrx);
     return PYSDR_ERR_ARG;
   }
   if (a.n_out <= 0) return PYSDR_OK;
-  // the branch-major form whenever its tile fits (a choice by the decimator's shape only: every call of a stream takes the
-  // same path -- and both paths sum every output in the same order anyway)
-  int bspan = 0;
-  const size_t blds = resamp_branch_lds(a.up, a.down, a.kpad, &bspan);
-  int wspan = 0;
-  const size_t wlds = resamp_wave_lds(a.up, a.down, a.kpad, &wspan);
-  if (wlds > 0 && plain == 0) {
+  const int ntiles = (a.n_out + p.tile_out - 1) / p.tile_out;
+  // wave / half-wave forms: two workgroups per CU, one stages while the other multiplies; one output per thread: ~8
+  // workgroups per CU, each stages the tap table once
+  const int grid_max = p.kernel == kRsKernelThread ? 2048 : 512;
+  int grid = ntiles < grid_max ? ntiles : grid_max;
+  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;      // tests: many tiles per workgroup in a small call
+  if (p.kernel == kRsKernelWave) {
     static std::mutex attr_mu;
     static uint64_t attr_done = 0;
     {
@@ -304,29 +284,12 @@ int launch_resamp_small(const MixDecArgs& a, int grid_cap, int plain, hipStream_
         attr_done |= 1ull << (dev & 63);
       }
     }
-    const int tile_out = a.up * 64;
-    const int ntiles = (a.n_out + tile_out - 1) / tile_out;
-    int wgrid = ntiles < 512 ? ntiles : 512;
-    if (grid_cap > 0 && wgrid > grid_cap) wgrid = grid_cap;
-    const int nw = (a.up + 1) / 2;                         // two branches per wave
-    hipLaunchKernelGGL(resamp_wave_kernel, dim3(wgrid), dim3(64 * nw), wlds, st, a, wspan, ntiles);
-    PYSDR_HIP_CHECK(hipGetLastError());
-    return PYSDR_OK;
+    hipLaunchKernelGGL(resamp_wave_kernel, dim3(grid), dim3(p.threads), p.lds, st, a, p.span, ntiles);
+  } else if (p.kernel == kRsKernelHalfWave) {
+    hipLaunchKernelGGL(resamp_branch_kernel, dim3(grid), dim3(p.threads), p.lds, st, a, p.span, ntiles);
+  } else {
+    hipLaunchKernelGGL(resamp_small_kernel, dim3(grid), dim3(p.threads), p.lds, st, a, p.span, ntiles);
   }
-  if (blds > 0 && plain != 1) {
-    const int tile_out = a.up * kRbL;
-    const int ntiles = (a.n_out + tile_out - 1) / tile_out;
-    int bgrid = ntiles < 512 ? ntiles : 512;               // two workgroups per CU: one stages while the other multiplies
-    if (grid_cap > 0 && bgrid > grid_cap) bgrid = grid_cap;   // tests: many tiles per workgroup in a small call
-    hipLaunchKernelGGL(resamp_branch_kernel, dim3(bgrid), dim3(a.up * kRbL), blds, st, a, bspan, ntiles);
-    PYSDR_HIP_CHECK(hipGetLastError());
-    return PYSDR_OK;
-  }
-  const size_t lds = ((size_t)span + (size_t)a.up * (a.kpad + 1)) * sizeof(float2);
-  const int ngroups = (a.n_out + kRsThreads - 1) / kRsThreads;
-  int grid = ngroups < 2048 ? ngroups : 2048;              // ~8 workgroups per CU, each stages the tap table once
-  if (grid_cap > 0 && grid > grid_cap) grid = grid_cap;
-  hipLaunchKernelGGL(resamp_small_kernel, dim3(grid), dim3(kRsThreads), lds, st, a, span, ngroups);
   PYSDR_HIP_CHECK(hipGetLastError());
   return PYSDR_OK;
 }

@@ -1692,6 +1692,13 @@ int launch_wfm_disc(const WfmArgs& a, hipStream_t st) {
     for (int r = 0; r < a.nrx; ++r)            // one buffer (every live context): the roll in stream order behind its only reader
       if (a.y1dst[r] == a.y1base[r])
         PYSDR_HIP_CHECK(hipMemcpyAsync(a.y1base[r] + 1, a.y1base[r] + 2 + (a.n1 - 1), sizeof(float2), hipMemcpyDeviceToDevice, st));
+  } else {
+    // a call without a single IF sample starts no kernel: the history it inherited is the next call's too, and when the calls
+    // overlap the next call reads it from the OTHER buffer of the pair (left alone, that one still holds the history of two
+    // calls back: one wrong discriminator sample, tests/test_gpu_wfm_sweep.py)
+    for (int r = 0; r < a.nrx; ++r)
+      if (a.y1dst[r] != a.y1base[r])
+        PYSDR_HIP_CHECK(hipMemcpyAsync(a.y1dst[r] + 1, a.y1base[r] + 1, sizeof(float2), hipMemcpyDeviceToDevice, st));
   }
   return PYSDR_OK;
 }
