@@ -709,6 +709,40 @@ int  pysdr_ft4_decode_osd(pysdr_ft4* ft4, const int32_t* F, const long long* t0,
 int  pysdr_ft4_decode_llr_osd(pysdr_ft4* ft4, const float* llr, int n, const pysdr_ldpc_cfg* cfg, int32_t* status, uint8_t* bits,
                               float* post, const pysdr_osd_cfg* osd, int32_t* detail);
 
+/* ---- A-priori decoding -----------------------------------------------------------------------------
+ * The decoder of item 24 told some message bits in advance, once per hypothesis.  A hypothesis is two words of 12 bytes,
+ * mask then value, packed as `bits`: message bit i is bit 7 - (i & 7) of byte i >> 3; only bits 0 .. 76 may be set in the
+ * mask, the mask is not empty, and value & ~mask == 0.  A call names n candidates (as pysdr_*_decode or pysdr_*_decode_llr
+ * takes them), a table hyps [H][24] and pairs [P][2] = (candidate, hypothesis): n in [0, 4096], H in [1, 4096], P in
+ * [0, 65536], the pairs strictly increasing in (candidate, hypothesis), candidate in [0, n), hypothesis in [0, H); a
+ * candidate may have no pair.  Per pair: amax = the greatest |llr| of the candidate's 174 soft bits, A = f32(mag amax),
+ * every soft bit k under the mask becomes +A (hypothesised 1) or -A (0), and item 24's decoder runs on that word
+ * unchanged (iters and alpha of cfg).  nerr counts the positions OUTSIDE the mask where llr > 0 differs from the final
+ * hard bit, nap the positions inside it where the final hard bit differs from the value.  The pair's status is 2 for a
+ * codeword with a matching CRC-14, a message that is not all zero, nap == 0 and nerr <= nerr_max; 1 for any other
+ * codeword; 0 for none.  Per candidate: among its pairs of status 2 the least nerr, ties to the lower pair index;
+ * ap [n][4] = {that pair or -1, its iterations, its nerr, the candidate's pairs of status 2} (zeros behind a -1),
+ * bits [n][12] = the picked pair's 91 bits, zero where there is none; detail (or NULL) [P][4] = {status, iterations,
+ * nerr, nap} of every pair.  One workgroup of 192 threads per pair, then one thread per candidate, on the skimmer's
+ * stream.  Candidates come from the first spectrum ring only, and no second stage runs behind these calls.
+ * pysdr_ap_plan needs no device: PYSDR_ERR_ARG for a NULL cfg or out, a mag that is not in [0.25, 16] (a NaN is not) or
+ * a nerr_max outside [0, 174], else out = {threads per pair, LDS bytes, pairs per call, hypotheses per call}.
+ * The four calls refuse what pysdr_*_decode / pysdr_*_decode_llr refuse, and a bad ap cfg, table or pair list
+ * (PYSDR_ERR_ARG); every check comes before any launch, and a refusal launches nothing and changes no output. */
+typedef struct pysdr_ap_cfg {
+  float mag;                /* the clamp, in units of the word's greatest |llr|, [0.25, 16] */
+  int32_t nerr_max;         /* most hard errors outside the mask of an accepted pair, [0, 174] */
+} pysdr_ap_cfg;
+int  pysdr_ap_plan(const pysdr_ap_cfg* cfg, int32_t out[4]);
+int  pysdr_ft8_decode_ap(pysdr_ft8* ft8, const int32_t* F, const long long* t0, int n, const uint8_t* hyps, int H, const int32_t* pairs,
+                         int P, const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail);
+int  pysdr_ft8_decode_llr_ap(pysdr_ft8* ft8, const float* llr, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                             const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail);
+int  pysdr_ft4_decode_ap(pysdr_ft4* ft4, const int32_t* F, const long long* t0, int n, const uint8_t* hyps, int H, const int32_t* pairs,
+                         int P, const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail);
+int  pysdr_ft4_decode_llr_ap(pysdr_ft4* ft4, const float* llr, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                             const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail);
+
 /* ---- Frame report and row floor ------------------------------------------------------------------
  * What the spectrum ring says about a frame whose 91 bits are known.  float32, every operation rounded on its own.
  * pysdr_ft8_report / pysdr_ft4_report: n <= 4096 candidates (F[i], t0[i]) under pysdr_*_llr's rules and refusals, and

@@ -68,6 +68,10 @@ class OsdCfg(C.Structure):
     _fields_ = [("order", C.c_int32)]
 
 
+class ApCfg(C.Structure):
+    _fields_ = [("mag", C.c_float), ("nerr_max", C.c_int32)]
+
+
 class PassCfg(C.Structure):
     _fields_ = [("reach_t", C.c_int32), ("trials", C.c_int32), ("pulse", C.POINTER(C.c_uint32)), ("lut", C.POINTER(C.c_float))]
 
@@ -83,6 +87,8 @@ _ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int
 _cands = [_p32, _pll, _i]                                               # FT8 / FT4: candidates (F, t0, n) ...
 _decoded = [C.POINTER(LdpcCfg), _p32, _pu8, _pf]                        # ... the decoder's cfg, status, bits and post ...
 _osd = [C.POINTER(OsdCfg), _p32]                                        # ... and the second stage's cfg and detail
+# a-priori decoding: the table (hyps, H), the pairs (pairs, P), both cfgs, ap, bits and detail
+_ap = [_pu8, _i, _p32, _i, C.POINTER(LdpcCfg), C.POINTER(ApCfg), _p32, _pu8, _p32]
 
 # name -> (restype, argtypes); every symbol include/pysdr_hip.h declares
 PROTOTYPES = {
@@ -202,6 +208,7 @@ PROTOTYPES = {
     "pysdr_fsk_state": (_i, [_vp, _pf, _p32]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
     "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
+    "pysdr_ap_plan": (_i, [C.POINTER(ApCfg), _p32]),
     "pysdr_report_plan": (_i, [_i, _p32]),
     "pysdr_pass_plan": (_i, [_i, _i, _i, _i, _i, _p32]),
     # the FT8 and the FT4 skimmer (ft.py): one set of entry points per mode, told apart by the name and the cfg struct
@@ -219,6 +226,8 @@ PROTOTYPES = {
         ("decode_osd", _i, [_vp] + _cands + _decoded + _osd),
         ("decode_llr", _i, [_vp, _pf, _i] + _decoded),
         ("decode_llr_osd", _i, [_vp, _pf, _i] + _decoded + _osd),
+        ("decode_ap", _i, [_vp] + _cands + _ap),
+        ("decode_llr_ap", _i, [_vp, _pf, _i] + _ap),
         ("report", _i, [_vp, _p32, _pll, _pu8, _i, _pf, _p32]),
         ("floor", _i, [_vp, _ll, _i, _pf]),
         ("keep", _i, [_vp, C.POINTER(PassCfg)]),

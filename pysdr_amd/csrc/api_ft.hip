@@ -6,7 +6,8 @@
 // skimmers' shared core, which reset, sync and fetch forward to directly; here is what only this kind has: its struct,
 // buffers, plan, the step count that a process call keeps, the soft bits and the state call.  Every device resource is
 // an owner (host_res.h): deleting the object frees it.  The decoder's calls are ldpc_host.h's, the frame report's and
-// the row floor's report_host.h's; both read the mode from the skimmer.
+// the row floor's report_host.h's, a-priori decoding's ap_host.h's; all read the mode from the skimmer.
+#include "ap_host.h"
 #include "ft_plan.h"
 #include "ldpc_host.h"
 #include "pass_host.h"
@@ -32,6 +33,7 @@ struct FtSkimmer : SkimmerBase {    // rows = nfine, words = cap * kFtEventWords
   LdpcBufs ldpc;                    // the decoder's results (ldpc_host.h)
   ReportBufs report;                // the frame report's and the row floor's (report_host.h)
   PassBufs pass;                    // the second pass's rings and tables, once kept (pass_host.h)
+  ApBufs ap;                        // a-priori decoding's tables and results, once called (ap_host.h)
   FtC* feed_rows() { return d_y.get() + Mode::kHpad; }
 };
 
@@ -237,6 +239,14 @@ int pysdr_ft8_decode_llr_osd(pysdr_ft8* w, const float* llr, int n, const pysdr_
                              float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
   return ldpc_decode_llr(w, "pysdr_ft8_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
 }
+int pysdr_ft8_decode_ap(pysdr_ft8* w, const int32_t* F, const long long* t0, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                        const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail) {
+  return ap_decode_ring(w, "pysdr_ft8_decode_ap", F, t0, n, cfg, ApCall{hyps, H, pairs, P, apcfg, detail}, ap, bits);
+}
+int pysdr_ft8_decode_llr_ap(pysdr_ft8* w, const float* llr, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                            const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail) {
+  return ap_decode_llr(w, "pysdr_ft8_decode_llr_ap", llr, n, cfg, ApCall{hyps, H, pairs, P, apcfg, detail}, ap, bits);
+}
 int pysdr_ft8_report(pysdr_ft8* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
   return report_frames(w, "pysdr_ft8_report", F, t0, bits, n, power, errs);
 }
@@ -294,6 +304,14 @@ int pysdr_ft4_decode_llr_osd(pysdr_ft4* w, const float* llr, int n, const pysdr_
                              float* post, const pysdr_osd_cfg* osd, int32_t* detail) {
   return ldpc_decode_llr(w, "pysdr_ft4_decode_llr_osd", llr, n, cfg, status, bits, post, OsdCall{true, osd, detail});
 }
+int pysdr_ft4_decode_ap(pysdr_ft4* w, const int32_t* F, const long long* t0, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                        const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail) {
+  return ap_decode_ring(w, "pysdr_ft4_decode_ap", F, t0, n, cfg, ApCall{hyps, H, pairs, P, apcfg, detail}, ap, bits);
+}
+int pysdr_ft4_decode_llr_ap(pysdr_ft4* w, const float* llr, int n, const uint8_t* hyps, int H, const int32_t* pairs, int P,
+                            const pysdr_ldpc_cfg* cfg, const pysdr_ap_cfg* apcfg, int32_t* ap, uint8_t* bits, int32_t* detail) {
+  return ap_decode_llr(w, "pysdr_ft4_decode_llr_ap", llr, n, cfg, ApCall{hyps, H, pairs, P, apcfg, detail}, ap, bits);
+}
 int pysdr_ft4_report(pysdr_ft4* w, const int32_t* F, const long long* t0, const uint8_t* bits, int n, float* power, int32_t* errs) {
   return report_frames(w, "pysdr_ft4_report", F, t0, bits, n, power, errs);
 }
@@ -333,6 +351,17 @@ int pysdr_osd_plan(const pysdr_osd_cfg* cfg, int32_t out[4]) {
     return PYSDR_ERR_ARG;
   }
   out[0] = kOsdThreads; out[1] = kOsdLdsBytes; out[2] = osd_patterns(cfg->order); out[3] = kLdpcMax;
+  return PYSDR_OK;
+}
+
+int pysdr_ap_plan(const pysdr_ap_cfg* cfg, int32_t out[4]) {
+  if (!out) { set_last_error("pysdr_ap_plan: out is NULL"); return PYSDR_ERR_ARG; }
+  if (!ap_cfg_ok(cfg)) {
+    set_last_error("pysdr_ap_plan: a cfg outside the rules (NULL; mag finite and in [%g, %g]; nerr_max in [0, %d])", (double)kApMagMin,
+                   (double)kApMagMax, kLdpcN);
+    return PYSDR_ERR_ARG;
+  }
+  out[0] = kLdpcThreads; out[1] = kApLdsBytes; out[2] = kApPairMax; out[3] = kApHypMax;
   return PYSDR_OK;
 }
 

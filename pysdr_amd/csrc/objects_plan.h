@@ -206,6 +206,10 @@ int launch_ldpc_decode(int source, const LdpcArgs& a, hipStream_t st);   // sour
 struct OsdArgs;
 int launch_osd_decode(int source, const OsdArgs& a, hipStream_t st);     // source: LdpcSource, the min-sum launch's
 
+// ---- a-priori decoding (ap.hip, host half ap_host.h; rules, steps and kernel arguments: ap_plan.h) -------------------------
+struct ApArgs;
+int launch_ap_decode(int source, const ApArgs& a, hipStream_t st);       // every pair's decode, then the pick; source: LdpcSource
+
 // ---- frame report and row floor (report.hip, host half report_host.h; steps and kernel arguments: report_plan.h) ---------
 struct ReportArgs;
 struct FloorArgs;
