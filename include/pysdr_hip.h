@@ -570,6 +570,55 @@ int  pysdr_fsk_process(pysdr_fsk* fsk, const void* iq, int n, int on_device, int
 int  pysdr_fsk_fetch(pysdr_fsk* fsk, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_fsk_state(pysdr_fsk* fsk, float* f, int32_t* ints);
 
+/* ---- packet skimmer: an AX.25 decoder on every row of an NFM raster (a build feature with a
+ * definition of its own: the reference holds no packet decoder) -------------------------------------------------------
+ * 1200 baud AFSK (Bell 202: mark 1200 Hz, space 2200 Hz) on narrow-band FM, HDLC framing, AX.25 UI frames: APRS.  The sixth
+ * client of a channelizer (either kind; rows at any fs_out from 9600 to 48000 Hz, which need not be a multiple of the
+ * baud rate).  Every row a < nk is discriminated (d[m] = Im(y[m] conj(y[m - 1])), no division), d is mixed down by the
+ * two tones (table tw[1024][2] = (cos, -sin)(2 pi k / 1024), indexed by the top ten bits of (m w) mod 2^32 of the
+ * absolute output index m), both go through the bit window g[L], L = round(fs_out / 1200) in [8, 40], and their powers
+ * are compared by eight slicers, gain[s] P_space > P_mark: decoder dec = a * 8 + s.  Each decoder has a 32-bit bit clock
+ * (+ w_baud per output, pulled towards 0 by clk >> pll_shift at every change of its slicer, a bit sampled where it turns
+ * negative), an NRZI / HDLC receiver with bit de-stuffing, the CRC-16 of AX.25 and a frame buffer of 83 words.  All float
+ * arithmetic is float32 with every operation rounded on its own, the rest is integer; DESIGN.md 3 item 29 is the
+ * normative text, step by step.  Any cut of a stream into calls gives the same events and the same state; a call that
+ * completes no output launches nothing and changes no state.
+ * pysdr_pkt_plan needs no device: PYSDR_ERR_ARG for L outside [8, 40], nk < 1, 8 nk > 2^18, max_out outside [1, 2^20] or a
+ * cfg outside its rules (every gain > 0, 0 < pmax <= 1e18, all finite; the three words > 0 and w_baud <= 2^29; pll_shift
+ * in [1, 4]), else out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, slicers per row,
+ * words of a frame buffer}; the event cap 84 + (ceil(max_out / (2^31 / w_baud + 1)) - 1) / 24, in words, is the most one
+ * decoder can emit in a call of max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and g are host arrays of 1024 x 2 and L floats, copied.  reset also resets the channelizer.
+ * process: as pysdr_fsk_process without its two further outputs; counts[8 nk] are the words of every decoder in this
+ * call, events[dec * ev_pitch + i], i < counts[dec].  A frame's event is a header word, (index within the call of the
+ * output that completed the closing flag) << 10 | n, and then (n + 3) / 4 words with the frame's n bytes, FCS left out,
+ * the first byte in the low bits, zero-padded; only frames of 15 <= n <= 330 bytes with a good FCS are events.
+ * PYSDR_ERR_STATE: n > max_in of the channelizer, the call would complete more than max_out outputs, or ev_pitch smaller
+ * than the event cap; the stream does not advance.
+ * fetch: the last call's event words of the named decoders, events[i * pitch + k] for rows[i], pitch >= the event cap.
+ * state: ints [10][8 nk] = clk, xprev, xlast, sr, ones, inframe, byte, nb, nbytes, crc and frames [8 nk][83], the frame
+ * buffers (bytes four to a word; a byte that opens a word clears the rest of it); NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_pkt_cfg {
+  float gain[8];            /* the slicers' weights of the space tone's power */
+  float pmax;               /* tone powers above this (or not finite) are blanked */
+  uint32_t w_mark, w_space; /* the tones' phase per row output, in turns / 2^32 */
+  uint32_t w_baud;          /* the bit clock's */
+  int32_t pll_shift;        /* the clock's pull at a change of the slicer: clk -= clk >> pll_shift */
+} pysdr_pkt_cfg;
+typedef struct pysdr_pkt pysdr_pkt;
+int  pysdr_pkt_plan(int nk, int L, int max_out, const pysdr_pkt_cfg* cfg, int32_t out[8]);
+int  pysdr_pkt_create(pysdr_chan* ch, int L, const pysdr_pkt_cfg* cfg, const float* tw, const float* g, int max_out,
+                      pysdr_pkt** out);
+void pysdr_pkt_destroy(pysdr_pkt* pkt);
+int  pysdr_pkt_reset(pysdr_pkt* pkt);
+int  pysdr_pkt_sync(pysdr_pkt* pkt);
+int  pysdr_pkt_process(pysdr_pkt* pkt, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch);
+int  pysdr_pkt_fetch(pysdr_pkt* pkt, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_pkt_state(pysdr_pkt* pkt, int32_t* ints, uint32_t* frames);
+
 /* ---- FT8 skimmer: Costas sync and soft bits on a fine raster of the band --------------------
  * The fourth client of a channelizer (either kind, M / D = 4, rows at S = 64 or 96 samples per symbol of 6.25 baud).
  * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 14 bins baud / 2 apart whose powers are

@@ -81,6 +81,11 @@ class FskCfg(C.Structure):
                 ("pmax", C.c_float), ("n0", C.c_int32)]
 
 
+class PktCfg(C.Structure):
+    _fields_ = [("gain", C.c_float * 8), ("pmax", C.c_float), ("w_mark", C.c_uint32), ("w_space", C.c_uint32),
+                ("w_baud", C.c_uint32), ("pll_shift", C.c_int32)]
+
+
 _vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 _ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
@@ -206,6 +211,14 @@ PROTOTYPES = {
     "pysdr_fsk_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll, _pf, _p32]),
     "pysdr_fsk_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
     "pysdr_fsk_state": (_i, [_vp, _pf, _p32]),
+    "pysdr_pkt_plan": (_i, [_i, _i, _i, C.POINTER(PktCfg), _p32]),
+    "pysdr_pkt_create": (_i, [_vp, _i, C.POINTER(PktCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_pkt_destroy": (None, [_vp]),
+    "pysdr_pkt_reset": (_i, [_vp]),
+    "pysdr_pkt_sync": (_i, [_vp]),
+    "pysdr_pkt_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
+    "pysdr_pkt_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_pkt_state": (_i, [_vp, _p32, C.POINTER(_u32)]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
     "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
     "pysdr_ap_plan": (_i, [C.POINTER(ApCfg), _p32]),

@@ -192,6 +192,10 @@ int launch_psk_decode(int S, const PskArgs& a, hipStream_t st);
 struct FskArgs;
 int launch_fsk_decode(int S, const FskArgs& a, hipStream_t st);
 
+// ---- packet skimmer (pkt.hip, host half api_pkt.hip; plan, steps and kernel arguments: pkt_plan.h) ----------------------
+struct PktArgs;
+int launch_pkt_decode(const PktArgs& a, hipStream_t st);
+
 // ---- FT8 and FT4 skimmers (ft.hip, host half api_ft.hip; modes, plan, steps and kernel arguments: ft_plan.h) ----------------
 struct FtArgs;
 struct FtLlrArgs;
