@@ -619,6 +619,69 @@ int  pysdr_pkt_process(pysdr_pkt* pkt, const void* iq, int n, int on_device, int
 int  pysdr_pkt_fetch(pysdr_pkt* pkt, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_pkt_state(pysdr_pkt* pkt, int32_t* ints, uint32_t* frames);
 
+/* ---- SSTV skimmer: a VIS and image decoder on every row of a raster (a build feature with a
+ * definition of its own: the reference holds no SSTV decoder) -----------------------------------------------------------
+ * Analogue slow-scan television: the VIS header, an anchor on the end of line 0's sync pulse, a free-running line clock
+ * and the pixels.  The seventh client of a channelizer (either kind; rows at any fs_out from 8000 to 48000 Hz).  Every
+ * row a < nk is detected (det 0, FM: the discriminator d[m] = Im(y[m] conj(y[m - 1])) as a real signal, w_sub the phase
+ * word of 1900 Hz; det 1, USB: the row itself, its centre where 1900 Hz of audio lands), mixed by the table
+ * tw[1024][2] = (cos, -sin)(2 pi k / 1024) indexed by the top ten bits of (m w_sub) mod 2^32 of the absolute output index
+ * m, low-passed by g[L], L in [9, 96], and turned into lag products c[m] = u[m] conj(u[m - 1]), 0 where a power is above
+ * pmax or not finite.  Sums of lag products give frequencies through a five-term arctangent polynomial: of every 10 ms
+ * tick into a ring of 64, on which the VIS header is matched while the row is idle; of every pixel once a picture runs,
+ * `lag` outputs behind the stream, from the anchor that hard decisions against 1350 Hz fix at the end of the first sync
+ * pulse.  All float arithmetic is float32 with every operation rounded on its own, the rest is integer; DESIGN.md 3 item
+ * 30 is the normative text, step by step.  Any cut of a stream into calls gives the same events and the same state; a
+ * call that completes no output launches nothing and changes no state.
+ * pysdr_sstv_plan needs no device: PYSDR_ERR_ARG for L outside [9, 96], nk outside [1, 2^15], max_out outside [1, 2^20],
+ * nk times the event cap above 2^28 words, or a cfg outside its rules (det 0 or 1; 0 < pmax <= 1e18; R0 in [80, 480] with
+ * |R0 w_tick - 2^32| <= w_tick; |5 W - R0| <= 3; lag = 2 R0 + W + 1; k_hz = fs_out / 2 pi and k_rho = 1024 / fs_out to
+ * within R0's rounding; 1 to 16 modes with distinct codes in [0, 127], 1 to 4 scans, width in [1, 800], lines in
+ * [1, 4096], scan_q >= width 2^16 -- a pixel of at least one sample -- and a line of at least three samples and less
+ * than 2^16), else out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, history samples
+ * in front of a row, words of a line buffer}.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and g are host arrays of 1024 x 2 and L floats, copied.  reset also resets the channelizer.
+ * process: as pysdr_pkt_process; counts[nk] are the words of every row in this call, events[a * ev_pitch + i],
+ * i < counts[a].  An event is a header word, (index within the call of the output that completed it) << 12 | kind << 10 |
+ * payload words, and its payload: kind 1, start: mode index, VIS code, f_lead (float bits, Hz from the subcarrier), the
+ * low 32 bits of the anchor e0; kind 2, line: the sent line's number, then the bytes of its scans in order, four to a
+ * word, the first in the low bits, zero-padded; kind 3, end: the number of sent lines.
+ * fetch: the last call's event words of the named rows, events[i * pitch + k] for rows[i], pitch >= the event cap.
+ * state: ints [7][nk] = ticks, phase (0 idle, 1 waiting for the anchor, 2 picture), mode, m_a, e0, line, pix; floats
+ * [7][nk] = the open tick's sum (re, im), the last tick's, f_lead, the open pixel's sum; ring [nk][64]; lines [nk][800],
+ * the line buffers (a byte that opens a word clears the rest of it); NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_sstv_mode {
+  int32_t code;             /* the VIS code's seven data bits */
+  int32_t scans;            /* scans of a sent line */
+  int32_t width;            /* pixels of a scan */
+  int32_t lines;            /* sent lines */
+  uint32_t sync_q, porch_q, scan_q, sep_q;   /* row samples in Q16: sync pulse, porch, one scan, the separator behind a scan */
+} pysdr_sstv_mode;
+typedef struct pysdr_sstv_cfg {
+  int32_t det;              /* 0: FM, 1: USB */
+  int32_t nmodes;
+  uint32_t w_sub;           /* the subcarrier's phase per row output, in turns / 2^32 */
+  uint32_t w_tick;          /* the 100 Hz tick's */
+  float k_hz;               /* fs_out / 2 pi: radians per output -> Hz */
+  float k_rho;              /* 1024 / fs_out: Hz -> table index */
+  float pmax;               /* powers above this (or not finite) blank their lag products */
+  int32_t W, R0, lag;       /* the anchor's half window, 10 ms, and the pixels' lag, in row outputs */
+  pysdr_sstv_mode modes[16];
+} pysdr_sstv_cfg;
+typedef struct pysdr_sstv pysdr_sstv;
+int  pysdr_sstv_plan(int nk, int L, int max_out, const pysdr_sstv_cfg* cfg, int32_t out[8]);
+int  pysdr_sstv_create(pysdr_chan* ch, int L, const pysdr_sstv_cfg* cfg, const float* tw, const float* g, int max_out,
+                       pysdr_sstv** out);
+void pysdr_sstv_destroy(pysdr_sstv* sstv);
+int  pysdr_sstv_reset(pysdr_sstv* sstv);
+int  pysdr_sstv_sync(pysdr_sstv* sstv);
+int  pysdr_sstv_process(pysdr_sstv* sstv, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                        long long ev_pitch);
+int  pysdr_sstv_fetch(pysdr_sstv* sstv, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_sstv_state(pysdr_sstv* sstv, int32_t* ints, float* floats, float* ring, uint32_t* lines);
+
 /* ---- FT8 skimmer: Costas sync and soft bits on a fine raster of the band --------------------
  * The fourth client of a channelizer (either kind, M / D = 4, rows at S = 64 or 96 samples per symbol of 6.25 baud).
  * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 14 bins baud / 2 apart whose powers are

@@ -86,6 +86,16 @@ class PktCfg(C.Structure):
                 ("w_baud", C.c_uint32), ("pll_shift", C.c_int32)]
 
 
+class SstvMode(C.Structure):
+    _fields_ = [("code", C.c_int32), ("scans", C.c_int32), ("width", C.c_int32), ("lines", C.c_int32), ("sync_q", C.c_uint32),
+                ("porch_q", C.c_uint32), ("scan_q", C.c_uint32), ("sep_q", C.c_uint32)]
+
+
+class SstvCfg(C.Structure):
+    _fields_ = [("det", C.c_int32), ("nmodes", C.c_int32), ("w_sub", C.c_uint32), ("w_tick", C.c_uint32), ("k_hz", C.c_float),
+                ("k_rho", C.c_float), ("pmax", C.c_float), ("W", C.c_int32), ("R0", C.c_int32), ("lag", C.c_int32), ("modes", SstvMode * 16)]
+
+
 _vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 _ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
@@ -219,6 +229,14 @@ PROTOTYPES = {
     "pysdr_pkt_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
     "pysdr_pkt_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
     "pysdr_pkt_state": (_i, [_vp, _p32, C.POINTER(_u32)]),
+    "pysdr_sstv_plan": (_i, [_i, _i, _i, C.POINTER(SstvCfg), _p32]),
+    "pysdr_sstv_create": (_i, [_vp, _i, C.POINTER(SstvCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_sstv_destroy": (None, [_vp]),
+    "pysdr_sstv_reset": (_i, [_vp]),
+    "pysdr_sstv_sync": (_i, [_vp]),
+    "pysdr_sstv_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
+    "pysdr_sstv_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_sstv_state": (_i, [_vp, _p32, _pf, _pf, C.POINTER(_u32)]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
     "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
     "pysdr_ap_plan": (_i, [C.POINTER(ApCfg), _p32]),

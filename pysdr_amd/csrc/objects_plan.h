@@ -196,6 +196,10 @@ int launch_fsk_decode(int S, const FskArgs& a, hipStream_t st);
 struct PktArgs;
 int launch_pkt_decode(const PktArgs& a, hipStream_t st);
 
+// ---- SSTV skimmer (sstv.hip, host half api_sstv.hip; plan, steps and kernel arguments: sstv_plan.h) -------------------------
+struct SstvArgs;
+int launch_sstv_decode(const SstvArgs& a, hipStream_t st);
+
 // ---- FT8 and FT4 skimmers (ft.hip, host half api_ft.hip; modes, plan, steps and kernel arguments: ft_plan.h) ----------------
 struct FtArgs;
 struct FtLlrArgs;
