@@ -682,6 +682,50 @@ int  pysdr_sstv_process(pysdr_sstv* sstv, const void* iq, int n, int on_device, 
 int  pysdr_sstv_fetch(pysdr_sstv* sstv, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_sstv_state(pysdr_sstv* sstv, int32_t* ints, float* floats, float* ring, uint32_t* lines);
 
+/* ---- RDS skimmer: station names on every row of an FM broadcast raster (a build feature with a
+ * definition of its own: the reference holds no RDS decoder) ------------------------------------------------------------
+ * RDS / RBDS: 1187.5 bit/s, differentially encoded biphase symbols on a suppressed 57 kHz subcarrier of the FM multiplex,
+ * blocks of 16 + 10 bits, groups of four blocks.  The eighth client of a channelizer (either kind; rows at any fs_out
+ * from 228 to 512 kHz).  Every row a < nk is discriminated (d[m] = arg(y[m] conj(y[m - 1])) in radians, four quadrants,
+ * through a five-term arctangent polynomial and one division; 0 where the product is zero or not finite), d is mixed
+ * down by 57 kHz (table tw[1024][2] = (cos, -sin)(2 pi k / 1024), indexed by the top ten bits of (3 m w19) mod 2^32 of
+ * the absolute output index m), and at every chip -- a sixteenth of a bit: the outputs m with (m w19) mod 2^32 < w19 --
+ * the matched pulse g[L], L = 2 floor(fs_out / 1187.5) + 1, is applied once, in segments of 64 taps summed in order.  The
+ * row counts its chips; chip count c belongs to timing phase c & 15, decoder dec = a * 16 + phase, whose bit is
+ * Re(z[c] conj(z[c - 16])) < 0 and goes into a register of the last 104 bits.  A group is emitted whenever the register's
+ * four 26-bit blocks leave the remainders of the offset words A, B, C or C', D modulo x^10 + x^8 + x^7 + x^5 + x^4 + x^3 +
+ * 1: no error correction, no flywheel.  All float arithmetic is float32 with every operation rounded on its own, the
+ * rest is integer; DESIGN.md 3 item 31 is the normative text, step by step.  Any cut of a stream into calls gives the
+ * same events and the same state; a call that completes no output launches nothing and changes no state.
+ * pysdr_rds_plan needs no device: PYSDR_ERR_ARG for L even or outside [385, 863], nk < 1, 16 nk > 2^18, max_out outside
+ * [1, 2^20] or a cfg outside its rules (w19 in [159383552, 357913942], and L the length that belongs to it:
+ * (L - 1) / 2 = floor((16 2^32 + 512) / w19), the 512 for w19's rounding), else out = {rows per workgroup, threads, LDS bytes, tile
+ * samples, event cap, workgroups, decoders per row, segments of the matched filter}; the event cap
+ * 3 ceil((floor(max_out w19 / 2^32) + 1) / 16), in words, is the most one decoder can emit in a call of max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and g are host arrays of 1024 x 2 and L floats, copied.  reset also resets the channelizer.
+ * process: as pysdr_pkt_process; counts[16 nk] are the words of every decoder in this call, events[dec * ev_pitch + i],
+ * i < counts[dec].  A group's event is three words: (index within the call of the output that completed the group) << 5
+ * | phase << 1 | (1 if the third block carries offset C'), then A << 16 | B and C << 16 | D, the blocks' information words.
+ * fetch: the last call's event words of the named decoders, events[i * pitch + k] for rows[i], pitch >= the event cap.
+ * state: regs [4][16 nk], the registers' blocks, the oldest first; chips [nk], the chips since reset (mod 2^32); ring
+ * [nk][16][2], z of the last chip of every phase; NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_rds_cfg {
+  uint32_t w19;             /* 19 kHz per row output, in turns / 2^32: the chip grid, and a third of the subcarrier */
+} pysdr_rds_cfg;
+typedef struct pysdr_rds pysdr_rds;
+int  pysdr_rds_plan(int nk, int L, int max_out, const pysdr_rds_cfg* cfg, int32_t out[8]);
+int  pysdr_rds_create(pysdr_chan* ch, int L, const pysdr_rds_cfg* cfg, const float* tw, const float* g, int max_out,
+                      pysdr_rds** out);
+void pysdr_rds_destroy(pysdr_rds* rds);
+int  pysdr_rds_reset(pysdr_rds* rds);
+int  pysdr_rds_sync(pysdr_rds* rds);
+int  pysdr_rds_process(pysdr_rds* rds, const void* iq, int n, int on_device, int* n_out, int32_t* counts, int32_t* events,
+                       long long ev_pitch);
+int  pysdr_rds_fetch(pysdr_rds* rds, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_rds_state(pysdr_rds* rds, uint32_t* regs, uint32_t* chips, float* ring);
+
 /* ---- FT8 skimmer: Costas sync and soft bits on a fine raster of the band --------------------
  * The fourth client of a channelizer (either kind, M / D = 4, rows at S = 64 or 96 samples per symbol of 6.25 baud).
  * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 14 bins baud / 2 apart whose powers are

@@ -96,6 +96,10 @@ class SstvCfg(C.Structure):
                 ("k_rho", C.c_float), ("pmax", C.c_float), ("W", C.c_int32), ("R0", C.c_int32), ("lag", C.c_int32), ("modes", SstvMode * 16)]
 
 
+class RdsCfg(C.Structure):
+    _fields_ = [("w19", C.c_uint32)]
+
+
 _vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 _ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
@@ -237,6 +241,14 @@ PROTOTYPES = {
     "pysdr_sstv_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
     "pysdr_sstv_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
     "pysdr_sstv_state": (_i, [_vp, _p32, _pf, _pf, C.POINTER(_u32)]),
+    "pysdr_rds_plan": (_i, [_i, _i, _i, C.POINTER(RdsCfg), _p32]),
+    "pysdr_rds_create": (_i, [_vp, _i, C.POINTER(RdsCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_rds_destroy": (None, [_vp]),
+    "pysdr_rds_reset": (_i, [_vp]),
+    "pysdr_rds_sync": (_i, [_vp]),
+    "pysdr_rds_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
+    "pysdr_rds_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_rds_state": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), _pf]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
     "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
     "pysdr_ap_plan": (_i, [C.POINTER(ApCfg), _p32]),

@@ -200,6 +200,10 @@ int launch_pkt_decode(const PktArgs& a, hipStream_t st);
 struct SstvArgs;
 int launch_sstv_decode(const SstvArgs& a, hipStream_t st);
 
+// ---- RDS skimmer (rds.hip, host half api_rds.hip; plan, steps and kernel arguments: rds_plan.h) -----------------------------
+struct RdsArgs;
+int launch_rds_decode(const RdsArgs& a, hipStream_t st);
+
 // ---- FT8 and FT4 skimmers (ft.hip, host half api_ft.hip; modes, plan, steps and kernel arguments: ft_plan.h) ----------------
 struct FtArgs;
 struct FtLlrArgs;
