@@ -726,6 +726,54 @@ int  pysdr_rds_process(pysdr_rds* rds, const void* iq, int n, int on_device, int
 int  pysdr_rds_fetch(pysdr_rds* rds, const int* rows, int nrows, int32_t* events, long long pitch);
 int  pysdr_rds_state(pysdr_rds* rds, uint32_t* regs, uint32_t* chips, float* ring);
 
+/* ---- ACARS skimmer: aircraft messages on every row of an airband raster (a build feature with a
+ * definition of its own: the reference holds no ACARS decoder) ---------------------------------------------------------
+ * 2400 bit/s MSK (1200 / 2400 Hz) inside the envelope of an AM carrier, characters of seven bits with odd parity, a
+ * CRC-16 behind every block.  The ninth client of a channelizer (either kind; rows at any fs_out from 19200 to 50000 Hz).
+ * Every row a < nk: the envelope power p[m] = |y[m]|^2 (0 where it is not <= pmax; no square root), a complex band-pass
+ * at +1800 Hz of NT = 4 L + 1 taps c (L = round(fs_out / 2400) in [8, 21]; their mean is zero, which nulls the carrier), a
+ * mix-down by the table tw[1024][2] = (cos, -sin)(2 pi k / 1024) indexed by the top ten bits of (m w_car) mod 2^32 of the
+ * absolute output index m, and a differential detector over one bit, x = Im(a[m] conj(a[m - L])) > 0.  One decoder per
+ * row: packet's 32-bit bit clock (+ w_baud per output, pulled towards 0 by clk >> pll_shift at every change of x, a bit
+ * sampled where it turns negative), the tone rule lev ^= 1 - x, a 16-bit sync register (SYN SYN, or its inverse, which
+ * flips lev), SOH, the text with odd parity on every byte, ETX or ETB and the two bytes of the block check.  All float
+ * arithmetic is float32 with every operation rounded on its own, the rest is integer; DESIGN.md 3 item 32 is the normative
+ * text, step by step.  Any cut of a stream into calls gives the same events and the same state; a call that completes no
+ * output launches nothing and changes no state.
+ * pysdr_acars_plan needs no device: PYSDR_ERR_ARG for L outside [8, 21], nk outside [1, 2^15], max_out outside [1, 2^20]
+ * or a cfg outside its rules (0 < pmax <= 1e18, finite; both words > 0 and w_baud <= 2^29; pll_shift in [1, 4]), else
+ * out = {rows per workgroup, threads, LDS bytes, tile samples, event cap, workgroups, taps, words of a frame buffer}; the
+ * event cap 61 + (ceil(max_out / (2^31 / w_baud + 1)) - 1) / 24, in words, is the most one decoder can emit in a call of
+ * max_out outputs.
+ * create borrows ch, which must outlive the skimmer, and resets it; while a skimmer exists, feed ch only through it.  tw
+ * and c are host arrays of 1024 x 2 and (4 L + 1) x 2 floats, copied.  reset also resets the channelizer.
+ * process: as pysdr_pkt_process; counts[nk] are the words of every row in this call, events[a * ev_pitch + i],
+ * i < counts[a].  A frame's event is a header word, (index within the call of the output that completed the block
+ * check) << 10 | n, and then (n + 3) / 4 words with the frame's n bytes, mode character to ETX / ETB, parity bits
+ * included, the first byte in the low bits, zero-padded; only frames of 13 <= n <= 238 bytes whose every byte has odd
+ * parity and whose block check is good are events.
+ * fetch: the last call's event words of the named rows, events[i * pitch + k] for rows[i], pitch >= the event cap.
+ * state: ints [9][nk] = clk, xprev, lev, sr, st, byte, nb, nbytes, crc and frames [nk][60], the frame buffers (bytes four
+ * to a word; a byte that opens a word clears the rest of it); NULL skips.
+ * Calls on one handle exclude each other; an error leaves the handle usable. */
+typedef struct pysdr_acars_cfg {
+  float pmax;               /* envelope powers above this (or not finite) are blanked */
+  uint32_t w_car;           /* 1800 Hz: the mixer's phase per row output, in turns / 2^32 */
+  uint32_t w_baud;          /* the bit clock's */
+  int32_t pll_shift;        /* the clock's pull at a change of the detector: clk -= clk >> pll_shift */
+} pysdr_acars_cfg;
+typedef struct pysdr_acars pysdr_acars;
+int  pysdr_acars_plan(int nk, int L, int max_out, const pysdr_acars_cfg* cfg, int32_t out[8]);
+int  pysdr_acars_create(pysdr_chan* ch, int L, const pysdr_acars_cfg* cfg, const float* tw, const float* c, int max_out,
+                        pysdr_acars** out);
+void pysdr_acars_destroy(pysdr_acars* acars);
+int  pysdr_acars_reset(pysdr_acars* acars);
+int  pysdr_acars_sync(pysdr_acars* acars);
+int  pysdr_acars_process(pysdr_acars* acars, const void* iq, int n, int on_device, int* n_out, int32_t* counts,
+                         int32_t* events, long long ev_pitch);
+int  pysdr_acars_fetch(pysdr_acars* acars, const int* rows, int nrows, int32_t* events, long long pitch);
+int  pysdr_acars_state(pysdr_acars* acars, int32_t* ints, uint32_t* frames);
+
 /* ---- FT8 skimmer: Costas sync and soft bits on a fine raster of the band --------------------
  * The fourth client of a channelizer (either kind, M / D = 4, rows at S = 64 or 96 samples per symbol of 6.25 baud).
  * Inside every row NSUB = S / 2 decoders, one every baud / 2, over NB = NSUB + 14 bins baud / 2 apart whose powers are

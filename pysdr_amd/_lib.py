@@ -100,6 +100,10 @@ class RdsCfg(C.Structure):
     _fields_ = [("w19", C.c_uint32)]
 
 
+class AcarsCfg(C.Structure):
+    _fields_ = [("pmax", C.c_float), ("w_car", C.c_uint32), ("w_baud", C.c_uint32), ("pll_shift", C.c_int32)]
+
+
 _vp, _i, _sz, _d, _f, _u32 =C.c_void_p, C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_uint32
 _pd, _pf, _pi = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int)
 _ll, _pll, _p32, _pu8 = C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)
@@ -249,6 +253,14 @@ PROTOTYPES = {
     "pysdr_rds_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
     "pysdr_rds_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
     "pysdr_rds_state": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), _pf]),
+    "pysdr_acars_plan": (_i, [_i, _i, _i, C.POINTER(AcarsCfg), _p32]),
+    "pysdr_acars_create": (_i, [_vp, _i, C.POINTER(AcarsCfg), _pf, _pf, _i, C.POINTER(_vp)]),
+    "pysdr_acars_destroy": (None, [_vp]),
+    "pysdr_acars_reset": (_i, [_vp]),
+    "pysdr_acars_sync": (_i, [_vp]),
+    "pysdr_acars_process": (_i, [_vp, _vp, _i, _i, _pi, _p32, _p32, _ll]),
+    "pysdr_acars_fetch": (_i, [_vp, _pi, _i, _p32, _ll]),
+    "pysdr_acars_state": (_i, [_vp, _p32, C.POINTER(_u32)]),
     "pysdr_ldpc_plan": (_i, [C.POINTER(LdpcCfg), _p32]),
     "pysdr_osd_plan": (_i, [C.POINTER(OsdCfg), _p32]),
     "pysdr_ap_plan": (_i, [C.POINTER(ApCfg), _p32]),

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpysdr_hip.so")
 LIB_DIAG = os.path.join(HERE, "libpysdr_hip_diag.so")   # loaded only when PYSDR_USE_DIAG_LIB=1
-SOURCES = ["api.hip", "api_objects.hip", "mixdec.hip", "mixdec_mfma.hip", "resamp_small.hip", "stage2.hip", "pllseed.hip", "misc.hip", "psdfft.hip", "waterfall.hip", "rtty.hip", "chan.hip", "bank.hip", "cw.hip", "api_cw.hip", "psk.hip", "api_psk.hip", "fine.hip", "api_fine.hip", "fsk.hip", "api_fsk.hip", "pkt.hip", "api_pkt.hip", "sstv.hip", "api_sstv.hip", "rds.hip", "api_rds.hip", "ft.hip", "api_ft.hip", "ldpc.hip", "osd.hip", "report.hip", "pass.hip", "ap.hip"]
+SOURCES = ["api.hip", "api_objects.hip", "mixdec.hip", "mixdec_mfma.hip", "resamp_small.hip", "stage2.hip", "pllseed.hip", "misc.hip", "psdfft.hip", "waterfall.hip", "rtty.hip", "chan.hip", "bank.hip", "cw.hip", "api_cw.hip", "psk.hip", "api_psk.hip", "fine.hip", "api_fine.hip", "fsk.hip", "api_fsk.hip", "pkt.hip", "api_pkt.hip", "sstv.hip", "api_sstv.hip", "rds.hip", "api_rds.hip", "acars.hip", "api_acars.hip", "ft.hip", "api_ft.hip", "ldpc.hip", "osd.hip", "report.hip", "pass.hip", "ap.hip"]
 # Flags every build uses (measured choices, part of the shipped configuration):
 #   stage2.hip   -fno-slp-vectorize: packed-f32 pairs built by the SLP vectoriser run at half rate on gfx950 and are fed
 #                by v_mov shuffles; the AF FIR is written for plain FMAs with its own v_pk_fma_f32

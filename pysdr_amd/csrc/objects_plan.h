@@ -204,6 +204,10 @@ int launch_sstv_decode(const SstvArgs& a, hipStream_t st);
 struct RdsArgs;
 int launch_rds_decode(const RdsArgs& a, hipStream_t st);
 
+// ---- ACARS skimmer (acars.hip, host half api_acars.hip; plan, steps and kernel arguments: acars_plan.h) ---------------------
+struct AcArgs;
+int launch_acars_decode(const AcArgs& a, hipStream_t st);
+
 // ---- FT8 and FT4 skimmers (ft.hip, host half api_ft.hip; modes, plan, steps and kernel arguments: ft_plan.h) ----------------
 struct FtArgs;
 struct FtLlrArgs;
